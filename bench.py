@@ -8,16 +8,24 @@ Infinity-Cache-resident bytes. With N GPUs every GPU runs its own independent 25
 (configs[4], C5: no data-path collective and no RCCL), so value = N x bytes per step / max time
 (weak scaling). Two ways to drive N GPUs, both measuring the same thing:
 
-    python bench.py                                    # N=1 (+ C3/C4 extra configs, CPU baseline)
+    python bench.py                                    # N=1: the headline's timed steps only
+    python bench.py --full                             # N=1 + C3/C4 extra configs, C1, CPU baseline, ...
     torchrun --nproc-per-node N bench.py --gpus N      # one process per GPU; gloo (CPU) barrier/max
     python bench.py --gpus N                           # one process: nexrReduceCopyMultiDeviceSets,
                                                        #   a host thread + stream per GPU
-Either N > 1 way also times an N=1 leg on GPU 0 in the same run, and every GPU alone, and reports
-them beside the aggregate under `c5`.
+A plain run sets up, warms up, times `--steps` steps and prints the line. With `--full` it goes on,
+after the timed region, to everything else the benchmark measures or checks: the bit-exact check of
+the last output against the oracle, the per-set kernel times, the extra configurations, C1, the CPU
+baseline and the host-inclusive rates at N=1; at N > 1 an N=1 leg on GPU 0 and every GPU alone,
+reported beside the aggregate under `c5`, and the xGMI probe.
 
-Prints ONE JSON line on rank 0 (keys per the driver contract, plus `roofline`, `cpu_baseline`,
-`h2d_inclusive`, `extra_configs` / `c1_ring` at N=1 and `per_gpu` / `c5` / `xgmi_probe` /
-`phase_s` at N>1).
+`--dump-outputs DIR` writes what the last timed step computed (every output buffer of that step, or
+a fixed seeded sample of it: at most 48 MiB in all) as DIR/<name>.npy, float32 or float64. The inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line on rank 0 (keys per the driver contract, plus `roofline`; with `--full` also
+`exact`, `cpu_baseline`, `h2d_inclusive`, `extra_configs` / `c1_ring` at N=1 and `c5` / `xgmi_probe`
+at N>1; `per_gpu` / `phase_s` in every N>1 line).
 """
 from __future__ import annotations
 
@@ -193,6 +201,34 @@ def comparator_sequence(ns: int, rounds: int, order: str) -> list:
     raise ValueError(f"order {order!r}")
 
 
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: all .npy files of a run together (under 64 MB with headers)
+DUMP_BLOCK = 4096  # elements per sampled run
+DUMP_SEED = 20240  # the sample is a function of (element count, budget) only
+
+
+def dump_sample_starts(n: int, max_elts: int, block: int = DUMP_BLOCK, seed: int = DUMP_SEED) -> tuple:
+    """(starts, run length) of the elements --dump-outputs writes from a buffer of `n`: all of it when
+    n <= max_elts, else runs of `block` elements at seeded random block positions, the first and the
+    last run of the buffer always among them, in ascending order."""
+    import numpy as np
+    if n <= max(max_elts, block):
+        return [0], n
+    runs = max(2, max_elts // block)
+    rng = np.random.default_rng(seed)
+    picked = rng.choice(n // block, size=min(runs, n // block), replace=False)[:runs - 2] * block
+    return sorted({0, n - block} | {int(s) for s in picked if s + block <= n}), block
+
+
+def dump_as_float(raw, dt: int):
+    """The bytes of elements of datatype `dt` as float32, or float64 for the 32- and 64-bit types."""
+    import numpy as np
+    if dt == 9:  # bf16: the upper half of a float32
+        return (raw.view(np.uint16).astype(np.uint32) << 16).view(np.float32)
+    store = {0: np.int8, 1: np.uint8, 2: np.int32, 3: np.uint32, 4: np.int64, 5: np.uint64, 6: np.float16,
+             7: np.float32, 8: np.float64}[dt]
+    return raw.view(store).astype(np.float64 if dt in (2, 3, 4, 5, 8) else np.float32)
+
+
 class DeviceWorkload:
     """R rotating buffer sets of one configuration on one GPU, and the timed launch loop over them."""
 
@@ -299,6 +335,32 @@ class DeviceWorkload:
         return {"exact": bool(ok), "checked_elements": len(starts) * block, "checked_set": i % len(self.sets),
                 "check": "bit-exact vs the C oracle (oracle/nexr_oracle.c) on a strided sample of the last "
                          "launch's output, after the timed region"}
+
+    def dump_outputs(self, i: int, directory: str, prefix: str, max_bytes: int) -> dict:
+        """--dump-outputs, after the timed region: every output buffer of set `i` (it holds what the
+        last launch on that set wrote) as `directory`/<prefix>dst<j>.npy, float32 (float64 for the 32-
+        and 64-bit types, whose values float32 cannot hold), at most `max_bytes` in all: the whole
+        buffer when it fits, else the runs of elements dump_sample_starts picks (the same for every
+        run with the same configuration). Returns {file name: elements written}."""
+        import numpy as np
+        import torch
+        cfg, esz = self.cfg, ESZ[self.cfg["dt"]]
+        _, _, _, dsts = self.sets[i % len(self.sets)]
+        wide = cfg["dt"] in (2, 3, 4, 5, 8)
+        starts, block = dump_sample_starts(self.n, max_bytes // len(dsts) // (8 if wide else 4))
+        os.makedirs(directory, exist_ok=True)
+        written = {}
+        on_gpu = self.dev.type == "cuda"
+        with torch.cuda.device(self.dev) if on_gpu else contextlib.nullcontext():
+            if on_gpu:
+                torch.cuda.synchronize(self.dev)
+            for j, d in enumerate(dsts):
+                b = d.view(torch.uint8)
+                raw = torch.cat([b[s * esz:(s + block) * esz] for s in starts]).cpu().numpy()
+                name = f"{prefix}dst{j}.npy"
+                np.save(os.path.join(directory, name), dump_as_float(raw, cfg["dt"]))
+                written[name] = len(starts) * block
+        return written
 
     def run(self, steps: int, warmup: int, dist, per_launch: bool = False):
         """Returns (local wall s, max-over-ranks wall s, average kernel s from HIP events recorded on
@@ -912,14 +974,21 @@ def main_ranks(args, cfg, pkg) -> dict | None:
     bytes_step = algorithmic_bytes(cfg)
     value = dist.world * bytes_step * args.steps / max_s / 1e9
     ranks = dist.gather([local_s, kernel_s], wl.dev)
-    # After the timed region: every rank checks its own last output bit-exactly against the oracle;
-    # rank 0 also times each of its rotating sets.
-    exact = side_leg(wl.check_exact, wl.last_set)
-    exact_ranks = [f[0] == 1.0 for f in dist.gather([1.0 if exact.get("exact") is True else 0.0], wl.dev)]
-    sets = side_leg(wl.per_set) if dist.rank == 0 else None
-    ph.mark("exact_checks_and_per_set")
+    dumped = None
+    if args.dump_outputs:
+        dumped = wl.dump_outputs(wl.last_set, args.dump_outputs, f"rank{dist.rank}_" if dist.world > 1 else "",
+                                 DUMP_MAX_BYTES // dist.world)
+        ph.mark("dump_outputs")
+    exact = exact_ranks = sets = None
+    if args.full:
+        # After the timed region: every rank checks its own last output bit-exactly against the oracle;
+        # rank 0 also times each of its rotating sets.
+        exact = side_leg(wl.check_exact, wl.last_set)
+        exact_ranks = [f[0] == 1.0 for f in dist.gather([1.0 if exact.get("exact") is True else 0.0], wl.dev)]
+        sets = side_leg(wl.per_set) if dist.rank == 0 else None
+        ph.mark("exact_checks_and_per_set")
     c5 = None
-    if dist.world > 1:
+    if dist.world > 1 and args.full:
         # Same-run legs: rank 0's GPU alone (the N=1 reference), then every GPU alone in turn.
         solo = []
         for r in range(dist.world):
@@ -930,7 +999,7 @@ def main_ranks(args, cfg, pkg) -> dict | None:
         c5 = c5_summary(dist.world, bytes_step, args.steps, max_s, solo[0], solo)
         ph.mark("solo_legs")
     h2d_all = None
-    if dist.world > 1 and not args.no_h2d:
+    if dist.world > 1 and args.full and not args.no_h2d:
         wl.free()
         h2d_all = h2d_pinned_all_ranks(pkg, cfg, dist, wl.dev)
         ph.mark("h2d_all_ranks")
@@ -942,12 +1011,18 @@ def main_ranks(args, cfg, pkg) -> dict | None:
                            (f"; REHEARSAL: {dist.world} ranks folded onto {torch.cuda.device_count()} GPU(s)"
                             if torch.cuda.device_count() < dist.world else ""))
         result["roofline"] = roofline(cfg, args.config, kernel_s, per_launch)
-        result["roofline"].update(sets if "error" not in sets else {"per_set_error": sets})
-        result["exact"] = all(exact_ranks)
-        result["exact_check"] = dict(exact, per_rank=exact_ranks)
-        result["cpu_baseline"] = None
-        result["h2d_inclusive"] = None
-        if dist.world == 1:
+        result["full"] = bool(args.full)
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
+        if dist.world > 1:
+            result["per_gpu"] = per_gpu_summary(ranks, bytes_step, args.steps)
+        if args.full:  # everything below was measured, or is measured here, after the timed region
+            result["roofline"].update(sets if "error" not in sets else {"per_set_error": sets})
+            result["exact"] = all(exact_ranks)
+            result["exact_check"] = dict(exact, per_rank=exact_ranks)
+            result["cpu_baseline"] = None
+            result["h2d_inclusive"] = None
+        if args.full and dist.world == 1:
             if not args.no_extra:
                 wl.free()
                 result["extra_configs"] = side_leg(extra_configs, pkg)
@@ -956,13 +1031,13 @@ def main_ranks(args, cfg, pkg) -> dict | None:
                 result["cpu_baseline"] = side_leg(cpu_baseline_entry, cfg, args.cpu_seconds)
             if not args.no_h2d:
                 result["h2d_inclusive"] = side_leg(h2d_inclusive, pkg, cfg)
-        else:
-            result["per_gpu"] = per_gpu_summary(ranks, bytes_step, args.steps)
+        elif args.full:
             result["c5"] = c5
             result["h2d_inclusive"] = h2d_all
             if not args.no_xgmi:
                 result["xgmi_probe"] = xgmi_probe(probe_budget(ph.elapsed()))
                 ph.mark("xgmi_probe")
+        if dist.world > 1:
             result["phase_s"] = ph.summary()
         print(json.dumps(result), flush=True)
     dist.barrier()
@@ -999,13 +1074,27 @@ def main_fanout(args, cfg, pkg) -> dict:
 
     agg_s = timed(works, devices)
     ph.mark("timed_region")
-    solo = [timed([works[i]], [devices[i]]) for i in range(args.gpus)]
-    ph.mark("solo_legs")
     value = args.gpus * bytes_step * args.steps / agg_s / 1e9
     result = base_line(cfg, args.gpus, args.steps, args.warmup, value, agg_s,
                        f"independent chunks x{args.gpus} (no collective), one process, "
                        f"nexrReduceCopyMultiDeviceSets (a host thread + stream per GPU, {FANOUT_SETS} rotating sets)" +
                        (f"; REHEARSAL: {args.gpus} chunks folded onto {n_vis} GPU(s)" if n_vis < args.gpus else ""))
+    result["full"] = bool(args.full)
+    if args.dump_outputs:
+        # the last of the `steps` timed launches of every GPU ran set (steps - 1) mod FANOUT_SETS
+        result["dumped_outputs"] = {}
+        for d, wl in enumerate(wls):
+            result["dumped_outputs"].update(wl.dump_outputs((args.steps - 1) % FANOUT_SETS, args.dump_outputs,
+                                                            f"gpu{d}_", DUMP_MAX_BYTES // args.gpus))
+        ph.mark("dump_outputs")
+    if not args.full:  # a plain run: the timed region and nothing after it
+        for wl in wls:
+            wl.free()
+        result["phase_s"] = ph.summary()
+        print(json.dumps(result), flush=True)
+        return result
+    solo = [timed([works[i]], [devices[i]]) for i in range(args.gpus)]
+    ph.mark("solo_legs")
     # Every GPU's output against the oracle (outside the timed legs; each set holds its last output).
     checks = [side_leg(wl.check_exact, 0) for wl in wls]
     result["exact"] = all(c.get("exact") is True for c in checks)
@@ -1043,6 +1132,13 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything else the benchmark measures or checks: the exact "
+                         "check against the oracle, per-set kernel times, the extra configurations, C1, the CPU "
+                         "baseline, host-inclusive rates; at N > 1 the solo legs and the xGMI probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (or a fixed seeded sample of them) as "
+                         "DIR/<name>.npy, float32 or float64")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-h2d", action="store_true")

@@ -51,8 +51,10 @@ class _FakePkg:
 
 
 def _args(**kw):
+    # full=True: these tests are about the legs `--full` adds after the timed region (the plain line
+    # has tests of its own below)
     a = dict(gpus=4, steps=20, warmup=5, config="c2", cpu_seconds=1.0, no_cpu=True, no_h2d=True, no_extra=True,
-             no_xgmi=True, events="region")
+             no_xgmi=True, events="region", full=True, dump_outputs=None)
     a.update(kw)
     return argparse.Namespace(**a)
 
@@ -418,3 +420,158 @@ def test_comparator_sequence_orders():
             assert (same == 0) if order == "grouped" else (same == 5 * ns)
     with pytest.raises(ValueError):
         bench.comparator_sequence(3, 1, "other")
+
+
+# ---- the plain line (no --full) and --dump-outputs ---------------------------------------------
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                 "vs_baseline", "dtype", "data", "config")
+FULL_ONLY_KEYS = ("exact", "exact_check", "extra_configs", "c1_ring", "cpu_baseline", "h2d_inclusive", "c5",
+                  "xgmi_probe")
+
+
+def _forbid_side_legs(monkeypatch):
+    """Every leg that belongs behind --full raises when a plain run reaches it."""
+    def forbidden(*a, **k):
+        raise AssertionError("a plain run started a leg that belongs behind --full")
+
+    for name in ("extra_configs", "c1_ring", "cpu_baseline_entry", "h2d_inclusive", "h2d_pinned_all_ranks",
+                 "xgmi_probe"):
+        monkeypatch.setattr(bench, name, forbidden)
+    monkeypatch.setattr(_FakeWorkload, "check_exact", forbidden)
+    monkeypatch.setattr(_FakeWorkload, "per_set", forbidden)
+
+
+def test_plain_n1_line_is_the_timed_steps_only(monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: one workload, one timed run, the
+    headline keys with the values the timed run gives, and none of the legs --full adds (not even
+    with the --no-* switches left off)."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *a, **k: None)
+    monkeypatch.setattr(bench, "DeviceWorkload", _FakeWorkload)
+    _forbid_side_legs(monkeypatch)
+    _FakeWorkload.made = []
+    cfg = bench.CONFIGS["c2"]
+    res = bench.main_ranks(_args(gpus=1, full=False, no_cpu=False, no_h2d=False, no_extra=False, no_xgmi=False),
+                           cfg, _FakePkg())
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line == json.loads(json.dumps(res))
+    for key in HEADLINE_KEYS:
+        assert key in line, key
+    for key in FULL_ONLY_KEYS:
+        assert key not in line, key
+    assert line["full"] is False and _FakeWorkload.made == [0]
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["n_gpus"] == 1
+    assert line["metric"] == bench.METRIC and line["unit"] == "GB/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32"
+    assert line["ms_per_step"] == pytest.approx(2.5e-3 / 20 * 1e3, abs=1e-4)
+    assert line["value"] == pytest.approx(bench.algorithmic_bytes(cfg) * 20 / 2.5e-3 / 1e9, rel=1e-4)
+    assert line["roofline"]["avg_kernel_us"] == 125.0 and "per_set_us" not in line["roofline"]
+
+
+def test_plain_fanout_line_is_the_timed_region_only(monkeypatch, capsys):
+    """The one-process N > 1 line without --full: W untimed and `steps` timed launches on all GPUs
+    together and nothing else (no solo legs, no roofline workload, no checks, no probe)."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 4)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(bench, "DeviceWorkload", _FakeWorkload)
+    _forbid_side_legs(monkeypatch)
+    _FakeWorkload.made = []
+    pkg = _FakePkg()
+    cfg = bench.CONFIGS["c2"]
+    bench.main_fanout(_args(full=False, no_xgmi=False), cfg, pkg)
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert pkg.calls == [([0, 1, 2, 3], 5), ([0, 1, 2, 3], 20)] and _FakeWorkload.made == [0, 1, 2, 3]
+    for key in HEADLINE_KEYS:
+        assert key in line, key
+    for key in FULL_ONLY_KEYS:
+        assert key not in line, key
+    agg_s = 0.125e-3 * 1.02 * 20
+    assert line["ms_per_step"] == pytest.approx(agg_s / 20 * 1e3, abs=1e-4)
+    assert line["value"] == pytest.approx(4 * bench.algorithmic_bytes(cfg) * 20 / agg_s / 1e9, rel=1e-4)
+    assert "timed_region" in line["phase_s"] and "solo_legs" not in line["phase_s"]
+
+
+def test_full_is_off_by_default_and_dump_outputs_takes_a_directory(monkeypatch):
+    seen = {}
+    monkeypatch.setattr(bench, "main_ranks", lambda args, cfg, pkg: seen.update(vars(args)))
+    monkeypatch.setattr(bench.importlib, "import_module", lambda name: types.SimpleNamespace(lib=lambda: None))
+    bench.main(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert seen["full"] is False and seen["dump_outputs"] is None and seen["steps"] == 7 and seen["warmup"] == 2
+    bench.main(["--full", "--dump-outputs", "some/dir"])
+    assert seen["full"] is True and seen["dump_outputs"] == "some/dir"
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs' sample: a function of the element count and the budget only, whole runs of
+    elements in ascending order with the buffer's first and last run among them, never more than the
+    budget; a buffer that fits is written whole."""
+    n = (256 << 20) // 4
+    budget = bench.DUMP_MAX_BYTES // 4
+    starts, block = bench.dump_sample_starts(n, budget)
+    assert (starts, block) == bench.dump_sample_starts(n, budget)
+    assert block == bench.DUMP_BLOCK and starts == sorted(set(starts)) and starts[0] == 0 and starts[-1] == n - block
+    assert all(0 <= s and s + block <= n for s in starts)
+    assert budget * 0.9 < len(starts) * block <= budget
+    assert len({s // (n // 8) for s in starts}) == 8  # spread over the whole buffer
+    assert bench.dump_sample_starts(1000, budget) == ([0], 1000)
+    assert bench.dump_sample_starts(budget, budget) == ([0], budget)
+    odd, block = bench.dump_sample_starts(budget + 12345, budget)  # not a multiple of the run length
+    assert odd[0] == 0 and odd[-1] == budget + 12345 - block and len(odd) * block <= budget
+    assert bench.DUMP_MAX_BYTES + 128 * 64 < 64 * 1000 * 1000  # with a header per file: under 64 MB
+
+
+def test_dump_as_float_keeps_every_value():
+    import numpy as np
+    bf16 = np.array([0x3F80, 0xC000, 0x0000, 0x7F80], dtype=np.uint16)  # 1, -2, 0, inf
+    out = bench.dump_as_float(bf16.view(np.uint8), 9)
+    assert out.dtype == np.float32 and out.tolist() == [1.0, -2.0, 0.0, float("inf")]
+    f16 = np.array([1.5, -0.25, 65504.0], dtype=np.float16)
+    out = bench.dump_as_float(f16.view(np.uint8), 6)
+    assert out.dtype == np.float32 and out.tolist() == [1.5, -0.25, 65504.0]
+    i8 = np.array([-128, -1, 127], dtype=np.int8)
+    out = bench.dump_as_float(i8.view(np.uint8), 0)
+    assert out.dtype == np.float32 and out.tolist() == [-128.0, -1.0, 127.0]
+    i32 = np.array([-2**31, 2**31 - 1, 16777217], dtype=np.int32)  # the last is not a float32
+    out = bench.dump_as_float(i32.view(np.uint8), 2)
+    assert out.dtype == np.float64 and out.tolist() == [-2.0**31, 2.0**31 - 1, 16777217.0]
+    f32 = np.array([0.1, -3.0], dtype=np.float32)
+    out = bench.dump_as_float(f32.view(np.uint8), 7)
+    assert out.dtype == np.float32 and np.array_equal(out, f32)
+
+
+@pytest.mark.parametrize("name,n", [("c2", 100_003), ("c3_bf16", 1 << 16), ("c4_i32_min", 5000)])
+def test_dump_outputs_writes_the_sampled_elements(tmp_path, name, n):
+    """DeviceWorkload.dump_outputs itself (CPU tensors standing in for HBM): one .npy per output
+    buffer, holding exactly the elements dump_sample_starts picks, whole when the budget allows."""
+    import numpy as np
+    import torch
+    cfg = dict(bench.CONFIGS[name], m=2)
+    esz = bench.ESZ[cfg["dt"]]
+    cfg["buf_bytes"] = n * esz
+    rng = np.random.default_rng(5)
+    if cfg["dt"] == 9:
+        raw = [(rng.standard_normal(n).astype(np.float32).view(np.uint32) >> 16).astype(np.uint16) for _ in range(2)]
+    else:
+        store = {7: np.float32, 2: np.int32}[cfg["dt"]]
+        raw = [rng.integers(-1000, 1000, n).astype(store) for _ in range(2)]
+    dsts = [torch.from_numpy(r.view(np.uint8).copy()) for r in raw]
+    wl = object.__new__(bench.DeviceWorkload)
+    wl.cfg, wl.n, wl.dev = cfg, n, torch.device("cpu")
+    wl.sets = [([0] * cfg["k"], [0, 0], [], dsts)]
+    out_item = 8 if cfg["dt"] == 2 else 4
+    for budget in (1 << 30, 2 * 3 * bench.DUMP_BLOCK * out_item):  # everything; three runs per buffer
+        d = tmp_path / f"dump{budget}"
+        written = wl.dump_outputs(0, str(d), "", budget)
+        assert sorted(written) == ["dst0.npy", "dst1.npy"] == sorted(p.name for p in d.iterdir())
+        starts, block = bench.dump_sample_starts(n, budget // 2 // out_item)
+        assert (len(starts) * block == n) == (budget == 1 << 30 or n <= 3 * bench.DUMP_BLOCK)
+        total = 0
+        for j, r in enumerate(raw):
+            got = np.load(d / f"dst{j}.npy")
+            exp = bench.dump_as_float(r.view(np.uint8), cfg["dt"])
+            assert got.dtype == (np.float64 if cfg["dt"] == 2 else np.float32)
+            assert np.array_equal(got, np.concatenate([exp[s:s + block] for s in starts]))
+            assert written[f"dst{j}.npy"] == got.size
+            total += got.nbytes
+        assert total <= budget
