@@ -34,6 +34,8 @@ extern "C" {
 
 #define NEXR_API __attribute__((visibility("default")))
 
+/* 0.3.0 also covers the LL flag rule (nexrLLFlagRule, nexrReduceCopyLLStepsRule, nexrLLCleanSlot):
+ * additions only, no existing entry point or struct layout changed, so the version stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
 #define NEXR_VERSION_PATCH 0
@@ -281,6 +283,12 @@ typedef struct {
  * reads *status every 64 tries and gives up when it is non-zero (another step timed out, or the
  * caller wrote it to abort: checkAbort, primitives.h:142-156). src/dst are any-aligned device
  * pointers (nullable: at least one input and one output); line buffers must be 16-B aligned.
+ *
+ * Flag wrap: the caller resolves the flags and owns the credits, so it also owns the reference's slot
+ * cleanup (incSend, prims_ll.h:85-93). On a send step s that cleans under its flag rule
+ * ((s & cleanMask) == cleanMask, nexrLLFlagRule below) the contract is: queue nexrReduceCopyLL, then
+ * nexrLLCleanSlot(nSend, sendLines, sendFlags, ceil(nElts*size/8), slotLines, stream) on the same
+ * stream, before the step is published. A step with nElts == 0 on a cleaning step still cleans.
  */
 NEXR_API nexrResult_t nexrReduceCopyLL(const void* src, int srcIsInput, int nRecv, const void* const* recvLines,
                                        const uint32_t* recvFlags, void* dst, int nSend, void* const* sendLines,
@@ -364,6 +372,51 @@ typedef struct {
 NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* conns, const nexrLLStep* steps, int nSteps,
                                             int datatype, int devRedOp, uint64_t redOpArg, uint32_t* status,
                                             uint32_t timeoutUs, nexrStream_t stream);
+
+/*
+ * The LL flag rule and the flag-wrap slot cleanup (reference src/device/prims_ll.h:85-93 incSend,
+ * src/include/device.h:719-728). An LL line is accepted when both its 32-bit flags equal
+ * NCCL_LL_FLAG(step + 1), so a line written once and never overwritten would match again when the flag
+ * comes round. The reference therefore rewrites, on every send step s with (s & NCCL_LL_CLEAN_MASK) ==
+ * NCCL_LL_CLEAN_MASK, every line of the step's slot behind the step's data as {0, flag, 0, flag}: with
+ * the production mask 0x7ffffff8 and NCCL_STEPS = 8 that is eight steps in a row every 2^31 steps, one
+ * per slot. The rule is a parameter here so that the cleanup can be exercised without 2^31 steps of
+ * traffic: {0x100, 0x78} is the reference's compile-time TEST_LL_CLEANUP mode.
+ *
+ * A rule is valid for nSlots slots when flagMax is 0 or a power of two, cleanMask != 0,
+ * cleanMask % nSlots == 0 (the reference's static_assert) and the cleaning period
+ * 2^(msb(cleanMask) + 1) is at most the flag period (flagMax, or 2^32 when flagMax == 0). NULL is the
+ * production rule {0, 0x7ffffff8}. An invalid rule returns nexrInvalidArgument before any launch.
+ */
+typedef struct {
+  uint32_t flagMax;   /* 0: NCCL_LL_FLAG(a) = (uint32_t)a;  else NCCL_LL_FLAG(a) = a % flagMax */
+  uint32_t cleanMask; /* NCCL_LL_CLEAN_MASK: a send step s cleans when (s & cleanMask) == cleanMask */
+} nexrLLFlagRule;
+
+/*
+ * nexrReduceCopyLLStepsRule — nexrReduceCopyLLSteps with the flag rule given (nexrReduceCopyLLSteps is
+ * this call with rule = NULL, the production rule). The flags of every step come from the rule applied
+ * to the 64-bit step counters, and on a cleaning send step the launch also writes lines
+ * [ceil(nElts*size/8), slotBytes/16) of the step's slot of EVERY send connection as {0, flag, 0, flag}
+ * (the reference calls incSend for every send), each line by the wave that owns it under the run's
+ * credit map, after that wave's waitSend. A cleaning step with nElts == 0 cleans the whole slot. The
+ * library ends a launch at every cleaning step and the kernel cleans behind its last step, so the
+ * other steps carry no cost for it.
+ */
+NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* conns, const nexrLLStep* steps, int nSteps,
+                                                int datatype, int devRedOp, uint64_t redOpArg,
+                                                const nexrLLFlagRule* rule, uint32_t* status, uint32_t timeoutUs,
+                                                nexrStream_t stream);
+
+/*
+ * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
+ * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
+ * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.
+ * sendLines[i] are the slot bases the step's nexrReduceCopyLL wrote to (non-NULL, 16-B aligned, else
+ * nexrInvalidArgument); firstLine is the step's line count. firstLine >= slotLines is a successful no-op.
+ */
+NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,
+                                      size_t slotLines, nexrStream_t stream);
 
 /*
  * Reduction semantics — which nex-nccl the library reproduces bit for bit. Process-wide, like an

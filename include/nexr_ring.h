@@ -140,6 +140,22 @@ NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t comm, int* word);
  * or more rank streams on a GPU than it has hardware queues beside the default stream's). */
 NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
 
+/* The LL flag rule of this communicator (nexrLLFlagRule, include/nexr.h; NULL or {0, 0x7ffffff8}: the
+ * production rule, the default; {0x100, 0x78}: the reference's TEST_LL_CLEANUP), for every channel. Its LL
+ * steps take their flags from it, and on a cleaning send step rewrite the rest of the step's slot as
+ * {0, flag, 0, flag} (reference incSend, src/device/prims_ll.h:85-93) in every mode: host-sequenced and
+ * queued steps after the step's llFn and before its tail is published (nexrLLCleanSlot on the rank's
+ * stream for device-memory FIFOs, CPU stores for host-memory ones), runs on the device inside the
+ * launch (nexrReduceCopyLLStepsRule). LL128 is not affected (64-bit flags; the reference does no
+ * cleanup there). Only before the communicator's first collective: nexrInvalidUsage afterwards; an
+ * invalid rule (for the FIFO's 8 slots) returns nexrInvalidArgument. */
+NEXR_API nexrResult_t nexrRingCommSetLLFlagRule(nexrRingComm_t comm, const nexrLLFlagRule* rule);
+
+/* Diagnostics of that cleanup. *minSendStep: the smallest send-step counter among the connections that
+ * have sent (0 when none has); *cleanedSteps: cleaning send steps since creation, over all connections
+ * and channels (one per connection and step). */
+NEXR_API nexrResult_t nexrRingCommGetLLCleanup(nexrRingComm_t comm, uint64_t* minSendStep, uint64_t* cleanedSteps);
+
 NEXR_API nexrResult_t nexrRingCommDestroy(nexrRingComm_t comm);
 
 /*

@@ -85,7 +85,8 @@ TYPE_SIZE = {DataType.Int8: 1, DataType.Uint8: 1, DataType.Int32: 4, DataType.Ui
 # ABI symbols declared in include/nexr.h (checked by tests/test_abi.py)
 ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevice", "nexrReduceCopyMultiDeviceSets",
                "nexrReduceCopyHost", "nexrHostToDevRedOp", "nexrLaunchOneRank",
-               "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
+               "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrReduceCopyLLStepsRule",
+               "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
 
@@ -149,6 +150,39 @@ class LLConnSet(ctypes.Structure):
                 ("recvStep", ctypes.c_uint64 * 3), ("sendFifo", ctypes.c_void_p * 3),
                 ("sendHead", ctypes.c_void_p * 3), ("sendStep", ctypes.c_uint64 * 3),
                 ("slotBytes", ctypes.c_uint64), ("nSlots", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class LLFlagRule(ctypes.Structure):
+    """Mirror of nexrLLFlagRule (include/nexr.h): flagMax 0 means NCCL_LL_FLAG(a) = (uint32_t)a, else
+    a % flagMax; a send step s cleans its slot when (s & cleanMask) == cleanMask."""
+    _fields_ = [("flagMax", ctypes.c_uint32), ("cleanMask", ctypes.c_uint32)]
+
+
+LL_PRODUCTION_RULE = (0, 0x7FFFFFF8)  # NCCL_LL_CLEAN_MASK with 32-bit flags
+LL_TEST_RULE = (0x100, 0x78)          # the reference's TEST_LL_CLEANUP (src/include/device.h:719-728)
+
+
+def _ll_rule(rule) -> LLFlagRule:
+    """An LLFlagRule from None (the production rule), an LLFlagRule or a (flag_max, clean_mask) pair."""
+    if rule is None:
+        rule = LL_PRODUCTION_RULE
+    if isinstance(rule, LLFlagRule):
+        return rule
+    flag_max, clean_mask = rule
+    return LLFlagRule(int(flag_max), int(clean_mask))
+
+
+def ll_flag(step: int, rule=None) -> int:
+    """The flag the lines of step `step` carry: NCCL_LL_FLAG(step + 1) under the rule."""
+    r = _ll_rule(rule)
+    a = int(step) + 1
+    return a % r.flagMax if r.flagMax else a & 0xFFFFFFFF
+
+
+def ll_cleans(step: int, rule=None) -> bool:
+    """Whether send step `step` cleans its slot: (step & cleanMask) == cleanMask (incSend, prims_ll.h:85-93)."""
+    r = _ll_rule(rule)
+    return (int(step) & r.cleanMask) == r.cleanMask
 
 
 _lib = None
@@ -233,6 +267,11 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopyLL128.restype = i32
     L.nexrReduceCopyLLSteps.argtypes = [P(LLConnSet), P(LLStep), i32, i32, i32, u64, vp, ctypes.c_uint32, vp]
     L.nexrReduceCopyLLSteps.restype = i32
+    L.nexrReduceCopyLLStepsRule.argtypes = [P(LLConnSet), P(LLStep), i32, i32, i32, u64, P(LLFlagRule), vp,
+                                            ctypes.c_uint32, vp]
+    L.nexrReduceCopyLLStepsRule.restype = i32
+    L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
+    L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
     L.nexrTypeSize.restype = sz
     L.nexrGetErrorString.argtypes = [i32]
@@ -478,9 +517,11 @@ def ll_step(src_buf: int = -1, src_ix: int = 0, dst_buf: int = -1, dst_ix: int =
 def reduce_copy_ll_steps(input_ptr: int, output_ptr: int, recv: Sequence[tuple], send: Sequence[tuple],
                          slot_bytes: int, steps: Sequence[LLStep], datatype: int, dev_red_op: int,
                          red_op_arg: int = 0, n_slots: int = 8, status: int = 0, timeout_us: int = 0,
-                         stream: int = 0) -> None:
+                         stream: int = 0, rule=None) -> None:
     """A run of LL steps with device credits (nexrReduceCopyLLSteps, reference prims_ll.h:55-83 and
-    :249-318). recv / send: (fifo pointer, head-words pointer, step counter) per connection."""
+    :249-318). recv / send: (fifo pointer, head-words pointer, step counter) per connection. rule: an
+    LLFlagRule or (flag_max, clean_mask) routes to nexrReduceCopyLLStepsRule; None is the plain call
+    (the production rule)."""
     cs = LLConnSet()
     cs.input, cs.output = int(input_ptr) or None, int(output_ptr) or None
     cs.nRecv, cs.nSend = len(recv), len(send)
@@ -490,11 +531,27 @@ def reduce_copy_ll_steps(input_ptr: int, output_ptr: int, recv: Sequence[tuple],
         cs.sendFifo[i], cs.sendHead[i], cs.sendStep[i] = int(fifo), int(head), int(step)
     cs.slotBytes, cs.nSlots = int(slot_bytes), int(n_slots)
     arr = (LLStep * max(1, len(steps)))(*steps)
-    rc = lib().nexrReduceCopyLLSteps(ctypes.byref(cs), arr, len(steps), int(datatype), int(dev_red_op),
-                                     int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
-                                     ctypes.c_void_p(int(status)) if status else None, int(timeout_us),
-                                     ctypes.c_void_p(int(stream)) if stream else None)
-    _check(rc, "nexrReduceCopyLLSteps")
+    tail = (ctypes.c_void_p(int(status)) if status else None, int(timeout_us),
+            ctypes.c_void_p(int(stream)) if stream else None)
+    if rule is None:
+        rc = lib().nexrReduceCopyLLSteps(ctypes.byref(cs), arr, len(steps), int(datatype), int(dev_red_op),
+                                         int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, *tail)
+        _check(rc, "nexrReduceCopyLLSteps")
+    else:
+        rc = lib().nexrReduceCopyLLStepsRule(ctypes.byref(cs), arr, len(steps), int(datatype), int(dev_red_op),
+                                             int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(_ll_rule(rule)),
+                                             *tail)
+        _check(rc, "nexrReduceCopyLLStepsRule")
+
+
+def ll_clean_slot(send_lines: Sequence[int], send_flags: Sequence[int], first_line: int, slot_lines: int,
+                  stream: int = 0) -> None:
+    """nexrLLCleanSlot: lines [first_line, slot_lines) of each slot become {0, flag, 0, flag} — what the
+    caller of the single-step reduce_copy_ll queues behind it on a cleaning step (ll_cleans)."""
+    sf = (ctypes.c_uint32 * max(1, len(send_flags)))(*[int(f) & 0xFFFFFFFF for f in send_flags])
+    rc = lib().nexrLLCleanSlot(len(send_lines), _ptr_array(send_lines), sf, int(first_line), int(slot_lines),
+                               ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrLLCleanSlot")
 
 
 def version() -> int:

@@ -1469,13 +1469,34 @@ bool rangesConflict(const std::vector<UserRange>& seen, const UserRange& r) {
 }
 }  // namespace
 
+// A flag rule is valid for nSlots slots (include/nexr.h): flagMax 0 or a power of two, cleanMask != 0 and a
+// multiple of nSlots (the reference's static_assert, prims_ll.h), and the cleaning period
+// 2^(msb(cleanMask) + 1) within the flag period, so that every line is rewritten before its flag recurs.
+static bool llRuleValid(const nexrLLFlagRule& r, uint32_t nSlots) {
+  if (r.flagMax & (r.flagMax - 1)) return false;
+  if (r.cleanMask == 0 || nSlots == 0 || r.cleanMask % nSlots) return false;
+  const uint64_t cleanPeriod = 2ull << (31 - __builtin_clz(r.cleanMask));
+  const uint64_t flagPeriod = r.flagMax ? (uint64_t)r.flagMax : 1ull << 32;
+  return cleanPeriod <= flagPeriod;
+}
+
 NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps,
                                             int datatype, int devRedOp, uint64_t redOpArg, uint32_t* status,
                                             uint32_t timeoutUs, nexrStream_t stream) {
+  return nexrReduceCopyLLStepsRule(cs, steps, nSteps, datatype, devRedOp, redOpArg, nullptr, status, timeoutUs,
+                                   stream);
+}
+
+NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps,
+                                                int datatype, int devRedOp, uint64_t redOpArg,
+                                                const nexrLLFlagRule* rulePtr, uint32_t* status, uint32_t timeoutUs,
+                                                nexrStream_t stream) {
   if (!cs || nSteps < 0 || (nSteps > 0 && !steps)) return nexrInvalidArgument;
   if (cs->nRecv < 0 || cs->nRecv > NEXR_LL_STEPS_MAX_PEERS || cs->nSend < 0 || cs->nSend > NEXR_LL_STEPS_MAX_PEERS)
     return nexrInvalidArgument;
   if (cs->slotBytes == 0 || cs->slotBytes % 16 || cs->nSlots == 0) return nexrInvalidArgument;
+  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
+  if (!llRuleValid(rule, cs->nSlots)) return nexrInvalidArgument;
   if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
     return nexrInvalidArgument;
   if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
@@ -1525,6 +1546,7 @@ NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* cs, const nexrL
   P.nRecv = cs->nRecv;
   P.nSend = cs->nSend;
   P.nSlots = (int)cs->nSlots;
+  P.flagMask = rule.flagMax ? rule.flagMax - 1 : 0xffffffffu;
   // One workgroup per line tile of a full slot (the same grid on both ends of every connection).
   const uint64_t slotTiles = (cs->slotBytes / 16 + kLLTileLines - 1) / kLLTileLines;
   const int grid = (int)(slotTiles < 1 ? 1 : slotTiles > (uint64_t)kLLStepsMaxGrid ? kLLStepsMaxGrid : slotTiles);
@@ -1558,12 +1580,51 @@ NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* cs, const nexrL
     P.step[P.nSteps++] = s;
     if (rd.end) seen.push_back(rd);
     if (wr.end) seen.push_back(wr);
+    // incSend's cleanup (prims_ll.h:85-93): a send step whose counter has every bit of the mask set cleans
+    // its slot, per send connection. The launch ends at such a step and its kernel cleans after its last
+    // step (nexr_ll.hip), so the step loop itself carries nothing for it.
+    uint32_t cleans = 0;
+    if (s.send)
+      for (int j = 0; j < cs->nSend; j++)
+        if (((uint32_t)ss[j] & rule.cleanMask) == rule.cleanMask) {
+          cleans |= 1u << j;
+          P.cleanStep[j] = ss[j];
+        }
     if (s.recv)
       for (uint64_t& v : rs) v++;
     if (s.send)
       for (uint64_t& v : ss) v++;
+    if (cleans) {
+      P.cleanLast = cleans;
+      nexrResult_t r = launch();
+      P.cleanLast = 0;
+      if (r != nexrSuccess) return r;
+    }
   }
   return launch();
+}
+
+NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,
+                                      size_t slotLines, nexrStream_t stream) {
+  if (nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;
+  if (nSend && (!sendLines || !sendFlags)) return nexrInvalidArgument;
+  LLCleanParams a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < nSend; i++) {
+    if (!sendLines[i] || ((uintptr_t)sendLines[i] & 15)) return nexrInvalidArgument;
+    a.send[i] = (char*)sendLines[i];
+    a.flag[i] = sendFlags[i];
+  }
+  if (nSend == 0 || firstLine >= slotLines) return nexrSuccess;
+  a.firstLine = firstLine;
+  a.slotLines = slotLines;
+  a.nSend = nSend;
+  // One workgroup per line tile from the first one that holds a clean line (the kernel skips those before it).
+  const uint64_t slotTiles = (slotLines + kLLTileLines - 1) / kLLTileLines;
+  uint64_t grid = slotTiles - firstLine / kLLTileLines;
+  if (grid > 1024) grid = 1024;
+  NEXR_HIP(launch_ll_clean(a, (int)grid, (hipStream_t)stream));
+  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrReduceCopyLL128(const void* src, int srcIsInput, int nRecv, const void* const* recvWire,

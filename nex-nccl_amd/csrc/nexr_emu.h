@@ -125,6 +125,22 @@ inline PeerLink* peerLink(void* base, int n, int from, int to) {
   return (PeerLink*)((char*)base + sizeof(PeerHeader) + (size_t)n * sizeof(PeerSlot)) + (size_t)from * n + to;
 }
 
+// The LL flag rule (nexrLLFlagRule, include/nexr.h; reference src/include/device.h:719-728): the flag a
+// value carries, whether a send step cleans its slot (incSend, prims_ll.h:85-93), and the rule's validity
+// for this FIFO's kSteps slots (the same conditions as nexrReduceCopyLLStepsRule checks).
+constexpr nexrLLFlagRule kLLProductionRule{0u, 0x7ffffff8u};
+inline uint32_t llFlag(const nexrLLFlagRule& r, uint64_t a) {
+  return r.flagMax ? (uint32_t)(a % r.flagMax) : (uint32_t)a;
+}
+inline bool llCleans(const nexrLLFlagRule& r, uint64_t sendStep) {
+  return ((uint32_t)sendStep & r.cleanMask) == r.cleanMask;
+}
+inline bool llRuleValid(const nexrLLFlagRule& r) {
+  if ((r.flagMax & (r.flagMax - 1)) || r.cleanMask == 0 || r.cleanMask % kSteps) return false;
+  const uint64_t cleanPeriod = 2ull << (31 - __builtin_clz(r.cleanMask));
+  return cleanPeriod <= (r.flagMax ? (uint64_t)r.flagMax : 1ull << 32);
+}
+
 inline int64_t divUp(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t alignUp(int64_t a, int64_t b) { return divUp(a, b) * b; }
 
@@ -173,6 +189,12 @@ struct nexrRingComm {
   // 0 host-sequenced, 1 queued launches (Prims::enableLLAsync), 2 runs with device credits (enableLLRun).
   int lastLLMode = 0;
   bool ownQueues = true;  // every rank stream has a hardware queue of its own (createRankStream)
+  // LL flag rule of this channel (nexrRingCommSetLLFlagRule, only before the first collective: the flags
+  // of steps in flight must not change under them) and the cleaning send steps it has run, over all of
+  // its connections (nexrRingCommGetLLCleanup).
+  nexrLLFlagRule llRule{0u, 0x7ffffff8u};
+  std::atomic<bool> started{false};
+  std::atomic<uint64_t> cleanedSteps{0};
   // Frees what the extras library attached to this communicator (set by its first resident call).
   void (*freeExtras)(nexrRingComm*) = nullptr;
   // Resident ring (nexrRingAllReduceResident), made by its first call: for every device hosting ranks
@@ -463,8 +485,8 @@ struct Prims {
     cs.slotBytes = c->stepBytes;
     cs.nSlots = kSteps;
     const uint32_t tmo = (uint32_t)((c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000) * 1000u);
-    const nexrResult_t r = nexrReduceCopyLLSteps(&cs, run.data(), (int)run.size(), datatype, devOp, redOpArgs[0],
-                                                 status, tmo, (nexrStream_t)stream);
+    const nexrResult_t r = nexrReduceCopyLLStepsRule(&cs, run.data(), (int)run.size(), datatype, devOp, redOpArgs[0],
+                                                     &c->llRule, status, tmo, (nexrStream_t)stream);
     run.clear();
     if (r != nexrSuccess) {
       sh->fail(r);
@@ -637,7 +659,10 @@ struct Prims {
       s.postOp = postOp ? 1 : 0;
       run.push_back(s);
       for (int i = 0; i < nr; i++) recv[i]->recvStep += 1;
-      for (int i = 0; i < ns; i++) send[i]->sendStep += 1;
+      for (int i = 0; i < ns; i++) {  // the run's kernel cleans the slot on such a step (flushRun passes the rule)
+        if (llCleans(c->llRule, send[i]->sendStep)) c->cleanedSteps.fetch_add(1, std::memory_order_relaxed);
+        send[i]->sendStep += 1;
+      }
       return run.size() < kLLRunFlush || flushRun();
     }
     for (int i = 0; i < ns; i++) {
@@ -646,7 +671,13 @@ struct Prims {
     }
     for (int i = 0; i < nr; i++)
       if (!waitAtLeast(recv[i]->st->tail, recv[i]->recvStep + 1)) return false;
-    if (nelem > 0) {
+    // incSend's cleanup (prims_ll.h:85-93), LL only: bit i set when this step of send connection i cleans
+    // its slot. It runs whatever nelem is, as the reference's incSend does.
+    uint32_t cleans = 0;
+    if (proto == nexrRingProtoLL)
+      for (int i = 0; i < ns; i++)
+        if (llCleans(c->llRule, send[i]->sendStep)) cleans |= 1u << i;
+    if (nelem > 0 || cleans) {
       const void* recvLines[kMaxArity];
       void* sendLines[kMaxArity];
       uint32_t rf32[kMaxArity], sf32[kMaxArity];
@@ -654,25 +685,42 @@ struct Prims {
       for (int i = 0; i < nr; i++) {
         recvLines[i] = recv[i]->fifo + (recv[i]->recvStep % kSteps) * slot(recv[i]);
         rf64[i] = recv[i]->recvStep + 1;
-        rf32[i] = (uint32_t)rf64[i];
+        rf32[i] = llFlag(c->llRule, rf64[i]);
       }
       for (int i = 0; i < ns; i++) {
         sendLines[i] = send[i]->fifo + (send[i]->sendStep % kSteps) * slot(send[i]);
         sf64[i] = send[i]->sendStep + 1;
-        sf32[i] = (uint32_t)sf64[i];
+        sf32[i] = llFlag(c->llRule, sf64[i]);
       }
       const void* src = srcBuf != kNone ? buf(srcBuf) + srcIx * esz : nullptr;
       void* dst = dstBuf != kNone ? buf(dstBuf) + dstIx * esz : nullptr;
       const int srcIsInput = srcBuf == kInput ? 1 : 0;
       if (status && !llAsync) *status = 0;
       const uint32_t tmo = (uint32_t)((c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000) * 1000u);
-      nexrResult_t r;
-      if (proto == nexrRingProtoLL128)
+      nexrResult_t r = nexrSuccess;
+      if (nelem <= 0)
+        ;  // nothing to move: the step only cleans
+      else if (proto == nexrRingProtoLL128)
         r = ll128Fn(src, srcIsInput, nr, recvLines, rf64, dst, ns, sendLines, sf64, (size_t)nelem, datatype, devOp,
                     redOpArgs[0], postOp ? 1 : 0, status, tmo, (nexrStream_t)stream);
       else
         r = llFn(src, srcIsInput, nr, recvLines, rf32, dst, ns, sendLines, sf32, (size_t)nelem, datatype, devOp,
                  redOpArgs[0], postOp ? 1 : 0, status, tmo, (nexrStream_t)stream);
+      // The cleanup: after the step's llFn and before its tail is published, lines [nLines, slotLines) of
+      // every cleaning connection's slot become {0, flag, 0, flag} — on the rank's stream behind the
+      // step's kernel when the FIFOs are device memory, with plain stores when they are host memory (the
+      // receiver reads them only after the tail's release).
+      for (int i = 0; i < ns && r == nexrSuccess; i++) {
+        if (!(cleans >> i & 1)) continue;
+        const size_t nLines = (size_t)divUp(nelem * (int64_t)esz, 8), slotLines = slot(send[i]) / 16;
+        if (device) {
+          r = nexrLLCleanSlot(1, &sendLines[i], &sf32[i], nLines, slotLines, (nexrStream_t)stream);
+        } else {
+          nexrLLFifoLine* line = (nexrLLFifoLine*)sendLines[i];
+          for (size_t l = nLines; l < slotLines; l++) line[l] = nexrLLFifoLine{0u, sf32[i], 0u, sf32[i]};
+        }
+        c->cleanedSteps.fetch_add(1, std::memory_order_relaxed);
+      }
       if (!llAsync) {
         if (r == nexrSuccess && device && !streamDone()) r = nexrUnhandledCudaError;
         if (r == nexrSuccess && status && __atomic_load_n(status, __ATOMIC_ACQUIRE) != 0) r = nexrInternalError;
@@ -700,7 +748,7 @@ struct Prims {
       recv[i]->recvStep += 1;
       recv[i]->st->head.store(recv[i]->recvStep, std::memory_order_release);
     }
-    for (int i = 0; i < ns; i++) {  // incSend (:85-93); the flag-wrap cleanup at NCCL_LL_CLEAN_MASK needs ~2^31 steps
+    for (int i = 0; i < ns; i++) {  // incSend (:85-93): its flag-wrap cleanup ran above, before this publish
       send[i]->sendStep += 1;
       send[i]->st->tail.store(send[i]->sendStep, std::memory_order_release);
     }

@@ -72,6 +72,12 @@ struct LLStepsParams {
   uint64_t timeoutTicks;
   int nRecv, nSend, nSlots, nSteps;
   int firstWins;
+  // The flag rule (nexrLLFlagRule): NCCL_LL_FLAG(a) = (uint32_t)a & flagMask (flagMax - 1, or all ones).
+  // A send step s also cleans its slot when (s & cleanMask) == cleanMask: the host ends the launch at such
+  // a step; bit j of cleanLast says that send connection j cleans at the launch's last step, whose send
+  // counter on that connection is cleanStep[j].
+  uint32_t flagMask, cleanLast;
+  uint64_t cleanStep[NEXR_LL_STEPS_MAX_PEERS];
 #ifdef NEXR_LL_STEPS_TRACE
   uint64_t* trace;  // tuning harness only (tools/ll_steps_trace.hip)
 #endif
@@ -79,6 +85,16 @@ struct LLStepsParams {
 };
 static_assert(sizeof(LLStepsParams) <= 4096, "kernel argument block");
 hipError_t launch_ll_steps(int dt, const LLStepsParams& a, int op, int grid, hipStream_t s);
+
+// The flag-wrap cleanup of one step for callers of the single-step kernel (nexrLLCleanSlot): lines
+// [firstLine, slotLines) of every slot become {0, flag, 0, flag} (reference incSend, prims_ll.h:85-93).
+struct LLCleanParams {
+  char* send[NEXR_MAX_DSTS];
+  uint32_t flag[NEXR_MAX_DSTS];
+  uint64_t firstLine, slotLines;
+  int nSend;
+};
+hipError_t launch_ll_clean(const LLCleanParams& a, int grid, hipStream_t s);
 
 // Launch parameters of one LL128-protocol step (nexr_ll.hip; reference src/device/prims_ll128.h).
 // Wire: 2 KiB slices of 16 x 128-B lines carrying 1920 data bytes; word 15 of every line is the flag.

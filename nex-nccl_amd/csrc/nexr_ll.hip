@@ -262,6 +262,45 @@ __device__ __forceinline__ bool ll_tile(const A& a, uint64_t tile, uint64_t nByt
   return arrived;
 }
 
+// The flag-wrap cleanup of one slot (reference incSend, prims_ll.h:85-93): lines [nLines, slotLines) of
+// the slot become {0, f, 0, f}, through the same 16-byte store as the data lines. Tiles t0, t0 + stride,
+// ... of the slot, and in a tile the lines ll_tile gives this lane (wave v: lines [128v, 128v + 128) of
+// every 512), so in a run every clean line is written by the wave whose credit covers it; the tile that
+// is part data and part clean is split at nLines, and tiles that are all data are skipped.
+__device__ __forceinline__ void ll_clean_tiles(char* slot, uint32_t f, uint64_t nLines, uint64_t slotLines,
+                                               uint64_t t0, uint64_t stride) {
+  const uint32_t o0 = (threadIdx.x >> 6) * 128 + (threadIdx.x & 63);
+  const uint64_t slotTiles = (slotLines + kLLTileLines - 1) / kLLTileLines;
+  const u32x4 v = (u32x4){0u, f, 0u, f};
+  for (uint64_t t = t0; t < slotTiles; t += stride) {
+    const uint64_t L0 = t * kLLTileLines;
+    if (L0 + kLLTileLines <= nLines) continue;
+    const uint32_t tileLines = (uint32_t)(slotLines - L0 < (uint64_t)kLLTileLines ? slotLines - L0 : kLLTileLines);
+    const uint32_t first = nLines > L0 ? (uint32_t)(nLines - L0) : 0u;
+    const auto r = wire_rsrc(slot + L0 * 16, (uint64_t)tileLines * 16);
+#pragma unroll
+    for (int u = 0; u < kLLU; u++) {
+      const uint32_t m0 = u * kLLSubLines + o0;
+      if (m0 >= first && m0 < tileLines) wire_st(r, m0 * 16, v);
+      if (m0 + 64 >= first && m0 + 64 < tileLines) wire_st(r, (m0 + 64) * 16, v);
+    }
+  }
+}
+
+// nexrLLCleanSlot: the cleanup for callers of the single-step kernel below, who resolve the flags and
+// own the credits themselves.
+__global__ __launch_bounds__(kBlock) void ll_clean_kernel(LLCleanParams a) {
+  for (int i = 0; i < NEXR_MAX_DSTS; i++) {
+    if (i >= a.nSend) break;
+    ll_clean_tiles(a.send[i], a.flag[i], a.firstLine, a.slotLines, blockIdx.x, gridDim.x);
+  }
+}
+
+hipError_t launch_ll_clean(const LLCleanParams& a, int grid, hipStream_t s) {
+  void* args[] = {const_cast<LLCleanParams*>(&a)};
+  return hipLaunchKernel((const void*)&ll_clean_kernel, dim3(grid), dim3(kBlock), args, 0, s);
+}
+
 template <int D, int OP>
 __global__ __launch_bounds__(kBlock) void reduce_copy_ll_kernel(LLParams a) {
   const uint64_t nBytes = a.nElts * (16 / Ty<D>::EPP);
@@ -416,9 +455,9 @@ __global__ __launch_bounds__(kBlock) void reduce_copy_ll_steps_kernel(LLStepsPar
 #pragma unroll
       for (int i = 0; i < MP; i++) {
         a.recv[i] = P.recvFifo[i] + (uint64_t)rSlot[i] * P.slotBytes;
-        a.recvFlag[i] = (uint32_t)(rs[i] + 1);
+        a.recvFlag[i] = (uint32_t)(rs[i] + 1) & P.flagMask;  // NCCL_LL_FLAG(step + 1) under the rule
         a.send[i] = P.sendFifo[i] + (uint64_t)sSlot[i] * P.slotBytes;
-        a.sendFlag[i] = (uint32_t)(ss[i] + 1);
+        a.sendFlag[i] = (uint32_t)(ss[i] + 1) & P.flagMask;
       }
       a.srcIsInput = st.srcBuf == 0 && !P.firstWins;
       a.postOp = st.postOp && !P.firstWins;
@@ -457,6 +496,31 @@ __global__ __launch_bounds__(kBlock) void reduce_copy_ll_steps_kernel(LLStepsPar
       }
     }
     NEXR_TRACE(k, 4);
+  }
+  // incSend's cleanup (prims_ll.h:85-93). The host ends a launch at a cleaning send step and names the
+  // send connections that clean there (P.cleanLast, bit j), so the step loop above carries nothing for
+  // it: inside the loop the block cost C1's LL leg 5-10 % (its scalar registers are spilled already).
+  // Every workgroup that owns a line of the SLOT writes here, not only those that own a data line, and
+  // the grid is one workgroup per tile of a slot (at most kLLStepsMaxGrid), so that is every workgroup
+  // of the launch: each wave waits for its own credit of the step (waitSend; the waves that moved data
+  // have it cached) and then writes the clean lines it owns under ll_tile's map.
+  if (P.cleanLast) {
+    const uint64_t nLines = ((uint64_t)P.step[P.nSteps - 1].nElts * esz + 7) / 8;
+#pragma unroll
+    for (int j = 0; j < MP; j++) {
+      if (!(P.cleanLast >> j & 1)) continue;
+      // The step's send counter comes from the host, and the head is read afresh, so that nothing of the
+      // loop's state lives on behind it (its registers are the parent's).
+      const uint64_t s = P.cleanStep[j];
+      const uint32_t slot = (uint32_t)(s % (uint64_t)P.nSlots);
+      uint64_t head = 0;
+      if (s + 1 > (uint64_t)P.nSlots &&
+          !wait_head(head_word(const_cast<uint64_t*>(P.sendHead[j]), w), s + 1 - P.nSlots, head, P.timeoutTicks,
+                     P.status))
+        return;  // no credit: status set, this wave stops
+      ll_clean_tiles(P.sendFifo[j] + (uint64_t)slot * P.slotBytes, (uint32_t)(s + 1) & P.flagMask, nLines,
+                     P.slotBytes / 16, w, G);
+    }
   }
 #ifdef NEXR_LL_STEPS_TRACE
   if (threadIdx.x == 0)

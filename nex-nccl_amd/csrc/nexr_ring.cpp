@@ -388,6 +388,7 @@ Prims makePrims(nexrRingComm* c, Shared* sh, int rank, const void* sendbuff, voi
   p.done = doneFor(c, stream);
   p.device = c->cfg.memMode == nexrRingDeviceMemory;
   p.proto = c->proto;
+  c->started.store(true, std::memory_order_relaxed);  // steps are about to run: the flag rule is fixed from here on
   return p;
 }
 
@@ -424,7 +425,9 @@ nexrResult_t prepare(nexrRingComm* c, int datatype, int op, size_t* esz, nexrDev
   if (c->broken) return nexrInvalidUsage;
   *esz = nexrTypeSize(datatype);
   if (*esz == 0 || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
-  return nexrHostToDevRedOp(red, op, datatype, c->cfg.nRanks);
+  const nexrResult_t r = nexrHostToDevRedOp(red, op, datatype, c->cfg.nRanks);
+  if (r == nexrSuccess) c->started.store(true, std::memory_order_relaxed);  // a collective: the flag rule is fixed
+  return r;
 }
 
 // Test hook: NEXR_TEST_SPAWN_FAIL_AT=k makes the k-th thread creation (1-based) of the next
@@ -1026,6 +1029,34 @@ NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t c, int* word) {
 NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t c, int* queued) {
   if (!c || !queued) return nexrInvalidArgument;
   *queued = c->lastLLMode;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrRingCommSetLLFlagRule(nexrRingComm_t c, const nexrLLFlagRule* rule) {
+  if (!c) return nexrInvalidArgument;
+  const nexrLLFlagRule r = rule ? *rule : kLLProductionRule;
+  if (!llRuleValid(r)) return nexrInvalidArgument;
+  if (c->started.load(std::memory_order_relaxed)) return nexrInvalidUsage;
+  for (const nexrRingComm* ck : c->channels)
+    if (ck->started.load(std::memory_order_relaxed)) return nexrInvalidUsage;
+  c->llRule = r;
+  for (nexrRingComm* ck : c->channels) ck->llRule = r;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrRingCommGetLLCleanup(nexrRingComm_t c, uint64_t* minSendStep, uint64_t* cleanedSteps) {
+  if (!c || !minSendStep || !cleanedSteps) return nexrInvalidArgument;
+  uint64_t lo = UINT64_MAX, cleaned = 0;
+  const int nCh = 1 + (int)c->channels.size();
+  for (int k = 0; k < nCh; k++) {
+    const nexrRingComm* ck = channelComm(c, k);
+    cleaned += ck->cleanedSteps.load(std::memory_order_relaxed);
+    for (const auto* v : {&ck->conns, &ck->treeUp, &ck->treeDown, &ck->p2pConns, &ck->p2pLLConns})
+      for (const Conn* q : *v)
+        if (q && q->sendStep > 0) lo = std::min(lo, q->sendStep);
+  }
+  *minSendStep = lo == UINT64_MAX ? 0 : lo;
+  *cleanedSteps = cleaned;
   return nexrSuccess;
 }
 

@@ -12,7 +12,7 @@ import ctypes
 import os
 from typing import Optional, Sequence
 
-from . import NexrError, Result, _check, lib
+from . import LLFlagRule, NexrError, Result, _check, lib
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 RING_LIB_PATH = os.path.join(_HERE, "libnexr_ring.so")
@@ -20,7 +20,8 @@ RING_LIB_PATH = os.path.join(_HERE, "libnexr_ring.so")
 EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
                     "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrTreeTopology",
-                    "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommDestroy", "nexrPeerRingCommCreate",
+                    "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLFlagRule",
+                    "nexrRingCommGetLLCleanup", "nexrRingCommDestroy", "nexrPeerRingCommCreate",
                     "nexrPeerRingAllReduce", "nexrPeerRingReduceScatter", "nexrPeerRingAllGather",
                     "nexrPeerRingReduce", "nexrPeerRingBroadcast")
 EXTRAS_ABI_SYMBOLS = ("nexrSendRecv", "nexrPeerSendRecv", "nexrRingAllReduceResident",
@@ -69,6 +70,8 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
+    L.nexrRingCommSetLLFlagRule.argtypes = [vp, ctypes.POINTER(LLFlagRule)]
+    L.nexrRingCommGetLLCleanup.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.nexrPeerRingCommCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(PeerRingConfig)]
     L.nexrRingCommDestroy.argtypes = [vp]
     for name in RING_ABI_SYMBOLS:
@@ -229,6 +232,20 @@ class RingComm:
         w = ctypes.c_int()
         _check(self._L.nexrRingCommGetQueued(self._h, ctypes.byref(w)), "nexrRingCommGetQueued")
         return int(w.value)
+
+    def set_ll_flag_rule(self, flag_max: int, clean_mask: int) -> None:
+        """The LL flag rule of every channel (nexrRingCommSetLLFlagRule): (0, 0x7ffffff8) is the production
+        rule, (0x100, 0x78) the reference's TEST_LL_CLEANUP. Only before the first collective."""
+        rule = LLFlagRule(int(flag_max), int(clean_mask))
+        _check(self._L.nexrRingCommSetLLFlagRule(self._h, ctypes.byref(rule)), "nexrRingCommSetLLFlagRule")
+
+    def ll_cleanup(self):
+        """(min_send_step, cleaned_steps) (nexrRingCommGetLLCleanup): the smallest send-step counter among
+        the connections that have sent, and the cleaning send steps run since creation."""
+        lo, cleaned = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.nexrRingCommGetLLCleanup(self._h, ctypes.byref(lo), ctypes.byref(cleaned)),
+               "nexrRingCommGetLLCleanup")
+        return int(lo.value), int(cleaned.value)
 
     def tree_topology(self, rank: int):
         """(up, [down...]) of `rank` in this communicator's tree (-1 = none)."""
