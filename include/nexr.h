@@ -34,8 +34,9 @@ extern "C" {
 
 #define NEXR_API __attribute__((visibility("default")))
 
-/* 0.3.0 also covers the LL flag rule (nexrLLFlagRule, nexrReduceCopyLLStepsRule, nexrLLCleanSlot):
- * additions only, no existing entry point or struct layout changed, so the version stays. */
+/* 0.3.0 also covers the LL flag rule (nexrLLFlagRule, nexrReduceCopyLLStepsRule, nexrLLCleanSlot) and the
+ * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup): additions only, no existing
+ * entry point or struct layout changed, so the version stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
 #define NEXR_VERSION_PATCH 0
@@ -407,6 +408,58 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* conns, cons
                                                 int datatype, int devRedOp, uint64_t redOpArg,
                                                 const nexrLLFlagRule* rule, uint32_t* status, uint32_t timeoutUs,
                                                 nexrStream_t stream);
+
+/*
+ * nexrReduceCopyLLStepsGroup — the runs of nMembers Primitives (1..NEXR_LL_GROUP_MAX_MEMBERS: e.g. every
+ * rank of a ring that lives on one GPU, times its channels) in the same launches on ONE stream. Member m
+ * runs steps[m][0..nSteps[m]) on conns[m] exactly as nexrReduceCopyLLStepsRule would (the same argument
+ * checks, reduction semantics, flags, credits and cleanup), but both ends of a connection between two
+ * members sit in one grid (workgroup b runs member b / G as its workgroup b % G, G derived from slotBytes
+ * as in nexrReduceCopyLLSteps), so the call needs no stream per member, no hardware queue of its own and
+ * no assumption that separate kernels are scheduled together. slotBytes and nSlots must be equal for all
+ * members (else nexrInvalidArgument). All members report into the one `status` word: a member that times
+ * out ends the others' polls, and the launch never hangs.
+ *
+ * Launch cuts. A launch carries at most 96 steps of a member and, per member, ends where
+ * nexrReduceCopyLLSteps would end it: before a step that touches user bytes an earlier step of the
+ * launch touched at another element position, and behind a cleaning send step. A cut applies to every
+ * member at the same step index (a member's part of a launch may be empty); user-range conflicts are
+ * looked for within a member, not between members. All launches go on `stream`, in order.
+ *
+ * Dry run. Before any device call the library walks every launch on the host: connections whose FIFO
+ * pointer is one member's send FIFO and another member's receive FIFO are internal (the sender's
+ * sendStep must not be behind the receiver's recvStep), and their data and credit counters are stepped
+ * round-robin through the launch's step lists from sendStep / recvStep; one-ended connections (the
+ * peer runs elsewhere, through any of the LL steps calls) count as always ready. If a launch cannot
+ * finish with what it and the launches before it produce — it would wait for a step of a later launch,
+ * which starts only behind it — the call returns nexrInvalidUsage and launches nothing. Schedules where
+ * step k of a member needs only steps <= k of its peers (the five ring collectives) always pass.
+ *
+ * Co-residency. nMembers * G workgroups must be resident at once: at most
+ * hipOccupancyMaxActiveBlocksPerMultiprocessor(kernel, 256 lanes) x the device's CUs, else
+ * nexrInvalidUsage (nothing launched).
+ *
+ * Workspace. Caller-owned device memory, 8-byte aligned, that holds the launches' parameter tables (one
+ * block per member per launch; they do not fit the kernel-argument segment). The library fills one
+ * DISTINCT region per launch of the call, so no table is written while a queued launch may read it: a
+ * call that needs more launches than workspaceBytes holds regions for returns nexrInvalidArgument before
+ * any device call. nexrLLGroupWorkspaceBytes(nMembers) is the size for NEXR_LL_GROUP_LAUNCHES launches
+ * (768 steps per member when nothing cuts); a region is that size / NEXR_LL_GROUP_LAUNCHES, and any
+ * larger workspace serves proportionally more launches (a call never needs more launches than its
+ * longest step list has steps). The tables reach the device by ONE hipMemcpyAsync on `stream` from
+ * pageable host memory, which the runtime stages before it returns, so nothing of the caller's arrays is
+ * read after the call returns; the copy and the launches are stream-ordered. The caller must leave the
+ * workspace alone (and not pass it to a call on another stream) until `stream` has passed the call; a
+ * later call on the SAME stream may reuse it at once, its copy being ordered behind the earlier launches.
+ */
+#define NEXR_LL_GROUP_MAX_MEMBERS 32
+#define NEXR_LL_GROUP_LAUNCHES 8
+NEXR_API nexrResult_t nexrLLGroupWorkspaceBytes(int nMembers, size_t* bytes);
+NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnSet* conns,
+                                                 const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                 int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rule,
+                                                 uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                 size_t workspaceBytes, nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

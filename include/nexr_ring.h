@@ -137,8 +137,25 @@ NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t comm, int* word);
  * to 1). 1: queued, each step's kernel on the rank's stream with no host wait after it, the slots a
  * step read released once a completion ticket behind it lands (one per NEXR_LL_TICKET_EVERY steps,
  * default 4). 0: host-sequenced (SIMPLE, LL128, ranks on several GPUs, host memory, NEXR_LL_ASYNC=0,
- * or more rank streams on a GPU than it has hardware queues beside the default stream's). */
+ * or more rank streams on a GPU than it has hardware queues beside the default stream's). 3: group
+ * launches on one stream (nexrRingCommSetLLGroup, below). */
 NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
+
+/* Opt-in: run the LL steps of every rank (and channel) of a ring collective in group launches on ONE
+ * stream (nexrReduceCopyLLStepsGroup, include/nexr.h). With on != 0, the five ring collectives record
+ * each (channel, rank)'s whole step list on the rank threads, the calling thread then queues the group
+ * launches on one stream of the communicator, waits once and publishes the host counters, and
+ * nexrRingCommGetQueued reports 3. No rank stream needs a hardware queue of its own, so the cap of mode
+ * 1 / 2 (GPU_MAX_HW_QUEUES - 1 rank streams on a GPU) does not apply: 4-8 ranks, or several channels,
+ * run on the device too. The communicator owns the launches' workspace. The flag rule, the cleanup
+ * counter and the status word (a timeout, or 2 for a relayed abort) work as in mode 2, and the option may
+ * be switched between collectives in either direction: every launch of either mode re-stores the device
+ * head words from the step counters both modes keep. A collective falls back to the mode it would have
+ * run without the option when its ranks span several GPUs, the communicator has a caller's llFn, the
+ * collective has more than NEXR_LL_GROUP_MAX_MEMBERS (channel, rank) members, or the group's grid is not
+ * resident at once on the GPU. The tree all-reduce is not affected. nexrInvalidUsage unless the
+ * communicator has thread ranks, the LL protocol and device memory. */
+NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t comm, int on);
 
 /* The LL flag rule of this communicator (nexrLLFlagRule, include/nexr.h; NULL or {0, 0x7ffffff8}: the
  * production rule, the default; {0x100, 0x78}: the reference's TEST_LL_CLEANUP), for every channel. Its LL

@@ -86,7 +86,7 @@ TYPE_SIZE = {DataType.Int8: 1, DataType.Uint8: 1, DataType.Int32: 4, DataType.Ui
 ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevice", "nexrReduceCopyMultiDeviceSets",
                "nexrReduceCopyHost", "nexrHostToDevRedOp", "nexrLaunchOneRank",
                "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrReduceCopyLLStepsRule",
-               "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
+               "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
 
@@ -134,6 +134,8 @@ class ReduceCopyWork(ctypes.Structure):
 
 LL_STEPS_MAX_PEERS = 3  # NEXR_LL_STEPS_MAX_PEERS
 LL_HEAD_BYTES = 4096   # NEXR_LL_HEAD_BYTES
+LL_GROUP_MAX_MEMBERS = 32  # NEXR_LL_GROUP_MAX_MEMBERS
+LL_GROUP_LAUNCHES = 8      # NEXR_LL_GROUP_LAUNCHES: the launches nexrLLGroupWorkspaceBytes sizes for
 
 
 class LLStep(ctypes.Structure):
@@ -270,6 +272,11 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopyLLStepsRule.argtypes = [P(LLConnSet), P(LLStep), i32, i32, i32, u64, P(LLFlagRule), vp,
                                             ctypes.c_uint32, vp]
     L.nexrReduceCopyLLStepsRule.restype = i32
+    L.nexrLLGroupWorkspaceBytes.argtypes = [i32, P(sz)]
+    L.nexrLLGroupWorkspaceBytes.restype = i32
+    L.nexrReduceCopyLLStepsGroup.argtypes = [i32, P(LLConnSet), P(P(LLStep)), P(i32), i32, i32, u64, P(LLFlagRule),
+                                             vp, ctypes.c_uint32, vp, sz, vp]
+    L.nexrReduceCopyLLStepsGroup.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -512,6 +519,59 @@ def ll_step(src_buf: int = -1, src_ix: int = 0, dst_buf: int = -1, dst_ix: int =
     s.recv, s.send, s.srcBuf, s.dstBuf, s.postOp = int(bool(recv)), int(bool(send)), int(src_buf), int(dst_buf), \
         int(bool(post_op))
     return s
+
+
+def ll_conn_set(input_ptr: int, output_ptr: int, recv: Sequence[tuple], send: Sequence[tuple], slot_bytes: int,
+                n_slots: int = 8) -> LLConnSet:
+    """An LLConnSet from (fifo pointer, head-words pointer, step counter) per connection."""
+    cs = LLConnSet()
+    cs.input, cs.output = int(input_ptr) or None, int(output_ptr) or None
+    cs.nRecv, cs.nSend = len(recv), len(send)
+    for i, (fifo, head, step) in enumerate(recv):
+        cs.recvFifo[i], cs.recvHead[i], cs.recvStep[i] = int(fifo), int(head), int(step)
+    for i, (fifo, head, step) in enumerate(send):
+        cs.sendFifo[i], cs.sendHead[i], cs.sendStep[i] = int(fifo), int(head), int(step)
+    cs.slotBytes, cs.nSlots = int(slot_bytes), int(n_slots)
+    return cs
+
+
+def ll_group_workspace_bytes(n_members: int, n_launches: int = LL_GROUP_LAUNCHES) -> int:
+    """Bytes of workspace for `n_launches` launches of a group of `n_members` (nexrLLGroupWorkspaceBytes
+    sizes for LL_GROUP_LAUNCHES; a region per launch is that / LL_GROUP_LAUNCHES)."""
+    b = ctypes.c_size_t(0)
+    _check(lib().nexrLLGroupWorkspaceBytes(int(n_members), ctypes.byref(b)), "nexrLLGroupWorkspaceBytes")
+    return b.value // LL_GROUP_LAUNCHES * max(1, int(n_launches))
+
+
+def reduce_copy_ll_steps_group(members: Sequence[tuple], slot_bytes: int, datatype: int, dev_red_op: int,
+                               red_op_arg: int = 0, n_slots: int = 8, status: int = 0, timeout_us: int = 0,
+                               stream: int = 0, rule=None, workspace=None):
+    """The runs of several Primitives in the same launches on one stream (nexrReduceCopyLLStepsGroup).
+    members: (input_ptr, output_ptr, recv, send, steps) per member, recv / send / steps as in
+    reduce_copy_ll_steps. workspace: (device pointer, bytes), or None to allocate one (a torch uint8
+    tensor sized for as many launches as the longest step list has steps, the most a call can need).
+    Returns the workspace tensor it allocated (None when one was given): keep it alive until the stream
+    has passed the call."""
+    n = len(members)
+    cs = (LLConnSet * max(1, n))(*[ll_conn_set(m[0], m[1], m[2], m[3], slot_bytes, n_slots) for m in members])
+    arrs = [(LLStep * max(1, len(m[4])))(*m[4]) for m in members]
+    ptrs = (ctypes.POINTER(LLStep) * max(1, n))(*[ctypes.cast(a, ctypes.POINTER(LLStep)) for a in arrs])
+    counts = (ctypes.c_int * max(1, n))(*[len(m[4]) for m in members])
+    keep = None
+    if workspace is None and 1 <= n <= LL_GROUP_MAX_MEMBERS:
+        import torch
+        longest = max([len(m[4]) for m in members] + [1])
+        keep = torch.empty(ll_group_workspace_bytes(n, longest), dtype=torch.uint8, device="cuda")
+        workspace = (keep.data_ptr(), keep.numel())
+    ws_ptr, ws_bytes = workspace if workspace is not None else (0, 0)
+    rc = lib().nexrReduceCopyLLStepsGroup(n, cs, ptrs, counts, int(datatype), int(dev_red_op),
+                                          int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                          ctypes.byref(_ll_rule(rule)) if rule is not None else None,
+                                          ctypes.c_void_p(int(status)) if status else None, int(timeout_us),
+                                          ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None, int(ws_bytes),
+                                          ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrReduceCopyLLStepsGroup")
+    return keep
 
 
 def reduce_copy_ll_steps(input_ptr: int, output_ptr: int, recv: Sequence[tuple], send: Sequence[tuple],

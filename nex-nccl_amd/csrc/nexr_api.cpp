@@ -1487,15 +1487,14 @@ NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* cs, const nexrL
                                    stream);
 }
 
-NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps,
-                                                int datatype, int devRedOp, uint64_t redOpArg,
-                                                const nexrLLFlagRule* rulePtr, uint32_t* status, uint32_t timeoutUs,
-                                                nexrStream_t stream) {
+// The argument checks of a run of LL steps of one Primitives (nexrReduceCopyLLStepsRule, and every member
+// of nexrReduceCopyLLStepsGroup): nothing here touches the device.
+static nexrResult_t llStepsValidate(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps, int datatype,
+                                    int devRedOp, uint64_t redOpArg, const nexrLLFlagRule& rule) {
   if (!cs || nSteps < 0 || (nSteps > 0 && !steps)) return nexrInvalidArgument;
   if (cs->nRecv < 0 || cs->nRecv > NEXR_LL_STEPS_MAX_PEERS || cs->nSend < 0 || cs->nSend > NEXR_LL_STEPS_MAX_PEERS)
     return nexrInvalidArgument;
   if (cs->slotBytes == 0 || cs->slotBytes % 16 || cs->nSlots == 0) return nexrInvalidArgument;
-  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
   if (!llRuleValid(rule, cs->nSlots)) return nexrInvalidArgument;
   if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
     return nexrInvalidArgument;
@@ -1526,7 +1525,18 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const n
     if ((s.srcBuf < 0 && !s.recv) || (s.dstBuf < 0 && !s.send)) return nexrInvalidArgument;
     if ((s.recv || s.send) && (uint64_t)s.nElts * esz > slotData) return nexrInvalidArgument;
   }
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps,
+                                                int datatype, int devRedOp, uint64_t redOpArg,
+                                                const nexrLLFlagRule* rulePtr, uint32_t* status, uint32_t timeoutUs,
+                                                nexrStream_t stream) {
+  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
+  const nexrResult_t valid = llStepsValidate(cs, steps, nSteps, datatype, devRedOp, redOpArg, rule);
+  if (valid != nexrSuccess) return valid;
   if (nSteps == 0) return nexrSuccess;
+  const size_t esz = typeSize(datatype);
   int srcIsInput = 1, postOp = 1;
   LLStepsParams P;
   memset(&P, 0, sizeof(P));
@@ -1602,6 +1612,239 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const n
     }
   }
   return launch();
+}
+
+// ---- nexrReduceCopyLLStepsGroup: the runs of several Primitives in one launch ------------------------
+// Three things make a group launch finish: its grid is resident as a whole (the occupancy
+// check below), it needs nothing a later launch would produce (the dry run), and every poll of its
+// kernel is bounded (nexr_ll.hip).
+NEXR_API nexrResult_t nexrLLGroupWorkspaceBytes(int nMembers, size_t* bytes) {
+  if (!bytes || nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS) return nexrInvalidArgument;
+  *bytes = (size_t)nMembers * kLLGroupEntryBytes * NEXR_LL_GROUP_LAUNCHES;
+  return nexrSuccess;
+}
+
+namespace {
+// Workgroups of the group kernel the current device keeps resident (blocks per CU x CUs), looked up once
+// per (device, datatype, op).
+// Test hook: NEXR_TEST_LL_GROUP_RESIDENT=k makes the next calls take k as that number, so that the
+// rejection of a grid that does not fit (and the ring's fall-back) can be tested on a GPU that fits it.
+// Read per call (tests set it between calls).
+nexrResult_t llGroupResident(int dt, int op, int64_t* resident) {
+  if (const char* e = getenv("NEXR_TEST_LL_GROUP_RESIDENT"))
+    if (*e) {
+      *resident = strtoll(e, nullptr, 10);
+      return nexrSuccess;
+    }
+  constexpr int kDevs = 16;
+  static std::atomic<int64_t> cache[kDevs][nexrNumTypes][nexrNumDevRedOps];
+  int dev = 0;
+  NEXR_HIP(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < kDevs;
+  if (cached) {
+    const int64_t v = cache[dev][dt][op].load(std::memory_order_relaxed);
+    if (v > 0) {
+      *resident = v;
+      return nexrSuccess;
+    }
+  }
+  int cus = 0, blocks = 0;
+  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  NEXR_HIP(ll_group_blocks_per_cu(dt, op, &blocks));
+  *resident = (int64_t)blocks * cus;
+  if (cached && *resident > 0) cache[dev][dt][op].store(*resident, std::memory_order_relaxed);
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnSet* conns,
+                                                 const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                 int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rulePtr,
+                                                 uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                 size_t workspaceBytes, nexrStream_t stream) {
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  if (nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || !conns || !steps || !nSteps) return nexrInvalidArgument;
+  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
+  int maxSteps = 0;
+  for (int m = 0; m < nMembers; m++) {
+    const nexrResult_t valid = llStepsValidate(&conns[m], steps[m], nSteps[m], datatype, devRedOp, redOpArg, rule);
+    if (valid != nexrSuccess) return valid;
+    // one G (a workgroup per line tile of a slot) and one credit window serve the launch
+    if (conns[m].slotBytes != conns[0].slotBytes || conns[m].nSlots != conns[0].nSlots) return nexrInvalidArgument;
+    maxSteps = std::max(maxSteps, nSteps[m]);
+  }
+  if (maxSteps == 0) return nexrSuccess;
+  if (!workspace || ((uintptr_t)workspace & 7)) return nexrInvalidArgument;
+  const size_t esz = typeSize(datatype);
+  const uint64_t nSlots = conns[0].nSlots;
+  int srcIsInput = 1, postOp = 1, firstWins = 0;
+  llSemantics(&datatype, &devRedOp, &srcIsInput, &postOp, &firstWins);
+
+  // The launches. A cut applies to every member at the same step index: before a step that would be a
+  // member's 97th of the launch or that conflicts with user bytes the member touched earlier in it
+  // (rangesConflict), and behind a step that cleans on any member (the kernel cleans behind a member's
+  // last step). Entry (launch l, member m) of the table is that member's parameter block of launch l.
+  std::vector<LLStepsParams> table;
+  std::vector<LLStepsParams> cur((size_t)nMembers);
+  for (int m = 0; m < nMembers; m++) {
+    const nexrLLConnSet& cs = conns[m];
+    LLStepsParams& P = cur[(size_t)m];
+    memset(&P, 0, sizeof(P));
+    P.input = (const char*)cs.input;
+    P.output = (char*)cs.output;
+    for (int i = 0; i < MP; i++) {
+      P.recvFifo[i] = (const char*)cs.recvFifo[i];
+      P.recvHead[i] = cs.recvHead[i];
+      P.sendFifo[i] = (char*)cs.sendFifo[i];
+      P.sendHead[i] = cs.sendHead[i];
+      P.recvStep[i] = cs.recvStep[i];
+      P.sendStep[i] = cs.sendStep[i];
+    }
+    P.slotBytes = cs.slotBytes;
+    P.redArg = redOpArg;
+    P.status = status;
+    P.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;
+    P.nRecv = cs.nRecv;
+    P.nSend = cs.nSend;
+    P.nSlots = (int)cs.nSlots;
+    P.firstWins = firstWins;
+    P.flagMask = rule.flagMax ? rule.flagMax - 1 : 0xffffffffu;
+  }
+  std::vector<std::vector<UserRange>> seen((size_t)nMembers);
+  auto cut = [&]() {  // the launch is complete: its blocks go into the table, the next one starts at the counters
+    for (int m = 0; m < nMembers; m++) {
+      LLStepsParams& P = cur[(size_t)m];
+      table.push_back(P);
+      for (int k = 0; k < P.nSteps; k++) {
+        const nexrLLStep& s = P.step[k];
+        for (int i = 0; i < MP; i++) P.recvStep[i] += s.recv ? 1 : 0, P.sendStep[i] += s.send ? 1 : 0;
+      }
+      P.nSteps = 0;
+      P.cleanLast = 0;
+      seen[(size_t)m].clear();
+    }
+  };
+  int inLaunch = 0;  // step indices in the current launch
+  for (int k = 0; k < maxSteps; k++) {
+    bool before = inLaunch == kLLStepsMax, cleans = false;
+    std::vector<UserRange> rd((size_t)nMembers, UserRange{0, 0, false}), wr((size_t)nMembers, UserRange{0, 0, true});
+    for (int m = 0; m < nMembers; m++) {
+      if (k >= nSteps[m]) continue;
+      const nexrLLStep& s = steps[m][k];
+      const nexrLLConnSet& cs = conns[m];
+      if (s.nElts && s.srcBuf >= 0) {
+        rd[(size_t)m].beg = (uintptr_t)(s.srcBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.srcIx * esz;
+        rd[(size_t)m].end = rd[(size_t)m].beg + (uintptr_t)s.nElts * esz;
+      }
+      if (s.nElts && s.dstBuf >= 0) {
+        wr[(size_t)m].beg = (uintptr_t)(s.dstBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.dstIx * esz;
+        wr[(size_t)m].end = wr[(size_t)m].beg + (uintptr_t)s.nElts * esz;
+      }
+      before = before || (rd[(size_t)m].end && rangesConflict(seen[(size_t)m], rd[(size_t)m])) ||
+               (wr[(size_t)m].end && rangesConflict(seen[(size_t)m], wr[(size_t)m]));
+    }
+    if (before && inLaunch) {
+      cut();
+      inLaunch = 0;
+    }
+    for (int m = 0; m < nMembers; m++) {
+      if (k >= nSteps[m]) continue;
+      const nexrLLStep& s = steps[m][k];
+      LLStepsParams& P = cur[(size_t)m];
+      // the member's send counters at this step: those of the launch's start plus its send steps so far
+      uint64_t sent = 0;
+      for (int q = 0; q < P.nSteps; q++) sent += P.step[q].send ? 1 : 0;
+      P.step[P.nSteps++] = s;
+      if (rd[(size_t)m].end) seen[(size_t)m].push_back(rd[(size_t)m]);
+      if (wr[(size_t)m].end) seen[(size_t)m].push_back(wr[(size_t)m]);
+      if (s.send)
+        for (int j = 0; j < conns[m].nSend; j++) {
+          const uint64_t ss = P.sendStep[j] + sent;
+          if (((uint32_t)ss & rule.cleanMask) == rule.cleanMask) {
+            P.cleanLast |= 1u << j;
+            P.cleanStep[j] = ss;
+            cleans = true;
+          }
+        }
+    }
+    inLaunch++;
+    if (cleans) {
+      cut();
+      inLaunch = 0;
+    }
+  }
+  if (inLaunch) cut();
+  const size_t nLaunches = table.size() / (size_t)nMembers;
+
+  // The dry run: every launch must finish with what it and the launches before it produce, because the
+  // next one starts only behind it on the stream. Connections whose FIFO is some member's send FIFO and
+  // another's receive FIFO are internal: their data and credit counters are walked here; the others are
+  // taken as always ready (their peer runs elsewhere).
+  struct Link {
+    uint64_t sent, read;
+  };
+  std::vector<Link> links;
+  std::vector<int> sendLink((size_t)nMembers * MP, -1), recvLink((size_t)nMembers * MP, -1);
+  for (int m = 0; m < nMembers; m++)
+    for (int j = 0; j < conns[m].nSend; j++)
+      for (int r = 0; r < nMembers && sendLink[(size_t)m * MP + j] < 0; r++)
+        for (int i = 0; i < conns[r].nRecv; i++)
+          if (conns[r].recvFifo[i] == conns[m].sendFifo[j] && recvLink[(size_t)r * MP + i] < 0) {
+            if (conns[m].sendStep[j] < conns[r].recvStep[i]) return nexrInvalidUsage;  // more read than sent
+            sendLink[(size_t)m * MP + j] = recvLink[(size_t)r * MP + i] = (int)links.size();
+            links.push_back(Link{conns[m].sendStep[j], conns[r].recvStep[i]});
+            break;
+          }
+  std::vector<int> pos((size_t)nMembers);
+  for (size_t l = 0; l < nLaunches; l++) {
+    const LLStepsParams* L = &table[l * (size_t)nMembers];
+    std::fill(pos.begin(), pos.end(), 0);
+    for (bool progress = true; progress;) {
+      progress = false;
+      for (int m = 0; m < nMembers; m++) {
+        while (pos[(size_t)m] < L[m].nSteps) {
+          const nexrLLStep& s = L[m].step[pos[(size_t)m]];
+          bool ready = true;
+          for (int i = 0; s.recv && i < L[m].nRecv; i++) {  // the line flags: the sender has written the step
+            const int id = recvLink[(size_t)m * MP + i];
+            if (id >= 0 && links[(size_t)id].sent < links[(size_t)id].read + 1) ready = false;
+          }
+          for (int j = 0; s.send && j < L[m].nSend; j++) {  // waitSend: the step nSlots back has been read
+            const int id = sendLink[(size_t)m * MP + j];
+            if (id >= 0 && links[(size_t)id].sent + 1 > links[(size_t)id].read + nSlots) ready = false;
+          }
+          if (!ready) break;
+          for (int i = 0; s.recv && i < L[m].nRecv; i++)
+            if (recvLink[(size_t)m * MP + i] >= 0) links[(size_t)recvLink[(size_t)m * MP + i]].read++;
+          for (int j = 0; s.send && j < L[m].nSend; j++)
+            if (sendLink[(size_t)m * MP + j] >= 0) links[(size_t)sendLink[(size_t)m * MP + j]].sent++;
+          pos[(size_t)m]++;
+          progress = true;
+        }
+      }
+    }
+    for (int m = 0; m < nMembers; m++)
+      if (pos[(size_t)m] < L[m].nSteps) return nexrInvalidUsage;  // this launch would wait for a later one
+  }
+
+  // One region of the workspace per launch: a table is never written while a queued launch may read it.
+  if (workspaceBytes / kLLGroupEntryBytes / (size_t)nMembers < nLaunches) return nexrInvalidArgument;
+
+  // Co-residency: all nMembers * G workgroups at once, or a poll could wait for a workgroup that has no CU.
+  const uint64_t slotTiles = (conns[0].slotBytes / 16 + kLLTileLines - 1) / kLLTileLines;
+  const int G = (int)(slotTiles < 1 ? 1 : slotTiles > (uint64_t)kLLStepsMaxGrid ? kLLStepsMaxGrid : slotTiles);
+  int64_t resident = 0;
+  const nexrResult_t occ = llGroupResident(datatype, devRedOp, &resident);
+  if (occ != nexrSuccess) return occ;
+  if ((int64_t)nMembers * G > resident) return nexrInvalidUsage;
+
+  // Pageable source: the runtime has staged it when the call returns, so `table` may go out of scope.
+  NEXR_HIP(hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(LLStepsParams), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  for (size_t l = 0; l < nLaunches; l++)
+    NEXR_HIP(launch_ll_group(datatype, devRedOp, (const LLStepsParams*)workspace + l * (size_t)nMembers, nMembers, G,
+                             (hipStream_t)stream));
+  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,

@@ -187,7 +187,14 @@ struct nexrRingComm {
   bool stepWaitWord = true;
   // How the last thread-rank ring collective ran its LL steps (diagnostics, nexrRingCommGetQueued):
   // 0 host-sequenced, 1 queued launches (Prims::enableLLAsync), 2 runs with device credits (enableLLRun).
+  // 3: group launches on one stream (nexrRingCommSetLLGroup).
   int lastLLMode = 0;
+  // nexrRingCommSetLLGroup: the option, and the device workspace of the group launches' tables (made by
+  // the first group collective on the ranks' GPU, grown when a collective needs more launches).
+  bool llGroup = false;
+  void* groupWs = nullptr;
+  size_t groupWsBytes = 0;
+  int groupWsDevice = 0;
   bool ownQueues = true;  // every rank stream has a hardware queue of its own (createRankStream)
   // LL flag rule of this channel (nexrRingCommSetLLFlagRule, only before the first collective: the flags
   // of steps in flight must not change under them) and the cleaning send steps it has run, over all of
@@ -464,8 +471,15 @@ struct Prims {
     run.clear();
     __atomic_store_n(status, 0u, __ATOMIC_RELEASE);
   }
-  bool flushRun() {
-    if (run.empty()) return true;
+  // Group launches (nexrRingCommSetLLGroup): the run mode's recording with no flush. The rank thread only
+  // collects its whole step list; the calling thread launches every member's at once (ringCollective).
+  bool llRecord = false;
+  void enableLLRecord() {
+    enableLLRun();
+    llRecord = llRun;
+  }
+  // The connections of this Primitives as the LL steps calls take them, at the run's first step.
+  nexrLLConnSet connSet() const {
     nexrLLConnSet cs;
     memset(&cs, 0, sizeof(cs));
     cs.input = userInput;
@@ -484,6 +498,11 @@ struct Prims {
     }
     cs.slotBytes = c->stepBytes;
     cs.nSlots = kSteps;
+    return cs;
+  }
+  bool flushRun() {
+    if (run.empty()) return true;
+    const nexrLLConnSet cs = connSet();
     const uint32_t tmo = (uint32_t)((c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000) * 1000u);
     const nexrResult_t r = nexrReduceCopyLLStepsRule(&cs, run.data(), (int)run.size(), datatype, devOp, redOpArgs[0],
                                                      &c->llRule, status, tmo, (nexrStream_t)stream);
@@ -663,7 +682,7 @@ struct Prims {
         if (llCleans(c->llRule, send[i]->sendStep)) c->cleanedSteps.fetch_add(1, std::memory_order_relaxed);
         send[i]->sendStep += 1;
       }
-      return run.size() < kLLRunFlush || flushRun();
+      return llRecord || run.size() < kLLRunFlush || flushRun();
     }
     for (int i = 0; i < ns; i++) {
       Conn* q = send[i];

@@ -86,6 +86,13 @@ struct LLStepsParams {
 static_assert(sizeof(LLStepsParams) <= 4096, "kernel argument block");
 hipError_t launch_ll_steps(int dt, const LLStepsParams& a, int op, int grid, hipStream_t s);
 
+// The runs of nMembers Primitives in one launch (nexrReduceCopyLLStepsGroup): `table` is nMembers
+// parameter blocks in device memory (kLLGroupEntryBytes apart), the grid nMembers * G workgroups.
+constexpr size_t kLLGroupEntryBytes = sizeof(LLStepsParams);
+static_assert(kLLGroupEntryBytes % 8 == 0, "table entries stay 8-byte aligned");
+hipError_t launch_ll_group(int dt, int op, const LLStepsParams* table, int nMembers, int G, hipStream_t s);
+hipError_t ll_group_blocks_per_cu(int dt, int op, int* blocks);
+
 // The flag-wrap cleanup of one step for callers of the single-step kernel (nexrLLCleanSlot): lines
 // [firstLine, slotLines) of every slot become {0, flag, 0, flag} (reference incSend, prims_ll.h:85-93).
 struct LLCleanParams {

@@ -564,6 +564,172 @@ hipError_t launch_ll_steps(int dt, const LLStepsParams& a, int op, int grid, hip
 }
 
 // ---------------------------------------------------------------------------------------------
+// The runs of several Primitives in ONE launch (nexrReduceCopyLLStepsGroup): the step loop above for
+// nMembers parameter blocks at once. Workgroup b runs member b / G as that member's workgroup b % G, so
+// both ends of a connection between two members sit in the same grid: no second stream or hardware
+// queue, and once the host has checked that nMembers * G workgroups are resident together, every poll's
+// producer is running. The blocks (about 3.2 KiB each) do not fit the 4 KiB argument segment; they come
+// from a table in device memory that nothing writes while the launch runs, read through the constant
+// address space with a wave-uniform member index, so a step's record still arrives by scalar loads.
+// All members report into one status word: one member's timeout ends the others' polls (ll_aborted).
+// ---------------------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) LLStepsParams c_LLStepsParams;
+typedef const __attribute__((address_space(4))) nexrLLStep c_LLStep;
+
+template <int D, int OP>
+__global__ __launch_bounds__(kBlock) void reduce_copy_ll_group_kernel(const LLStepsParams* table, int nMembers, int G) {
+  constexpr uint64_t esz = 16 / Ty<D>::EPP;
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  const uint32_t m = __builtin_amdgcn_readfirstlane(blockIdx.x / (uint32_t)G);
+  const uint32_t w = blockIdx.x - m * (uint32_t)G;
+  if (m >= (uint32_t)nMembers) return;
+  c_LLStepsParams& P = ((c_LLStepsParams*)table)[m];
+  const bool lead = (threadIdx.x & 63) == 0;
+  const int nSlots = P.nSlots, nRecv = P.nRecv, nSend = P.nSend, nSteps = P.nSteps;
+  const uint64_t slotBytes = P.slotBytes, timeoutTicks = P.timeoutTicks;
+  const uint32_t flagMask = P.flagMask;
+  uint32_t* const status = P.status;
+  uint64_t rs[MP], ss[MP], headCache[MP];
+  uint32_t rSlot[MP], sSlot[MP];
+#pragma unroll
+  for (int i = 0; i < MP; i++) {
+    rs[i] = P.recvStep[i], ss[i] = P.sendStep[i], headCache[i] = 0;
+    rSlot[i] = (uint32_t)(rs[i] % (uint64_t)nSlots), sSlot[i] = (uint32_t)(ss[i] % (uint64_t)nSlots);
+  }
+  // Every earlier launch of this stream has completed: whatever ran them, the slots before recvStep are read.
+  if (lead)
+    for (int i = 0; i < nRecv; i++)
+      __hip_atomic_store(head_word(P.recvHead[i], w), rs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  LLStepArgs a;
+  a.redArg = P.redArg;
+  a.status = status;
+  a.timeoutTicks = timeoutTicks;
+  a.firstWins = P.firstWins;
+  for (int k = 0; k < nSteps; k++) {
+    c_LLStep& st = P.step[k];  // scalar loads from the table
+    const uint64_t nBytes = (uint64_t)st.nElts * esz;
+    const uint64_t nLines = (nBytes + 7) / 8;
+    const uint64_t nTiles = (nLines + kLLTileLines - 1) / kLLTileLines;
+    const bool stRecv = st.recv, stSend = st.send;
+    if (w < nTiles) {
+      if (stSend) {  // waitSend: the receiver's wave has read the step nSlots back
+#pragma unroll
+        for (int j = 0; j < MP; j++)
+          if (j < nSend && ss[j] + 1 > (uint64_t)nSlots &&
+              !wait_head(head_word(const_cast<uint64_t*>(P.sendHead[j]), w), ss[j] + 1 - nSlots, headCache[j],
+                         timeoutTicks, status))
+            return;  // no credit: status set, this wave stops
+      }
+      const int srcBuf = st.srcBuf, dstBuf = st.dstBuf;
+      a.src = srcBuf == 0 ? P.input + st.srcIx * esz : srcBuf == 1 ? P.output + st.srcIx * esz : nullptr;
+      a.dst = dstBuf == 0 ? const_cast<char*>(P.input) + st.dstIx * esz
+              : dstBuf == 1 ? P.output + st.dstIx * esz : nullptr;
+      a.nRecv = stRecv ? nRecv : 0;
+      a.nSend = stSend ? nSend : 0;
+#pragma unroll
+      for (int i = 0; i < MP; i++) {
+        a.recv[i] = P.recvFifo[i] + (uint64_t)rSlot[i] * slotBytes;
+        a.recvFlag[i] = (uint32_t)(rs[i] + 1) & flagMask;  // NCCL_LL_FLAG(step + 1) under the rule
+        a.send[i] = P.sendFifo[i] + (uint64_t)sSlot[i] * slotBytes;
+        a.sendFlag[i] = (uint32_t)(ss[i] + 1) & flagMask;
+      }
+      a.srcIsInput = srcBuf == 0 && !a.firstWins;
+      a.postOp = st.postOp && !a.firstWins;
+      bool arrived = true;
+      for (uint64_t t = w; t < nTiles; t += G) {
+        if constexpr (OP == nexrDevMinMax) {
+          if ((a.redArg & 1) == 0) arrived &= ll_tile<D, OP, true, LLStepArgs, MP>(a, t, nBytes, nLines);
+          else arrived &= ll_tile<D, OP, false, LLStepArgs, MP>(a, t, nBytes, nLines);
+        } else {
+          arrived &= ll_tile<D, OP, false, LLStepArgs, MP>(a, t, nBytes, nLines);
+        }
+      }
+      // a line never came: status set, this wave stops (its lines only; the other waves' are theirs)
+      if (__builtin_amdgcn_ballot_w64(!arrived)) return;
+    }
+    if (stRecv) {  // postRecv, relaxed as in the single-member kernel
+      if (lead)
+        for (int i = 0; i < nRecv; i++)
+          __hip_atomic_store(head_word(P.recvHead[i], w), rs[i] + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+      for (int i = 0; i < MP; i++) {
+        rs[i]++;
+        rSlot[i] = rSlot[i] + 1 == (uint32_t)nSlots ? 0 : rSlot[i] + 1;
+      }
+    }
+    if (stSend) {
+#pragma unroll
+      for (int j = 0; j < MP; j++) {
+        ss[j]++;
+        sSlot[j] = sSlot[j] + 1 == (uint32_t)nSlots ? 0 : sSlot[j] + 1;
+      }
+    }
+  }
+  // incSend's cleanup behind the member's last step, as in the single-member kernel: the host cuts every
+  // member's launch at a cleaning send step and names the connections that clean there.
+  const uint32_t cleanLast = P.cleanLast;
+  if (cleanLast) {
+    const uint64_t nLines = ((uint64_t)P.step[nSteps - 1].nElts * esz + 7) / 8;
+#pragma unroll
+    for (int j = 0; j < MP; j++) {
+      if (!(cleanLast >> j & 1)) continue;
+      const uint64_t s = P.cleanStep[j];
+      const uint32_t slot = (uint32_t)(s % (uint64_t)nSlots);
+      uint64_t head = 0;
+      if (s + 1 > (uint64_t)nSlots &&
+          !wait_head(head_word(const_cast<uint64_t*>(P.sendHead[j]), w), s + 1 - nSlots, head, timeoutTicks, status))
+        return;  // no credit: status set, this wave stops
+      ll_clean_tiles(P.sendFifo[j] + (uint64_t)slot * slotBytes, (uint32_t)(s + 1) & flagMask, nLines, slotBytes / 16,
+                     w, G);
+    }
+  }
+}
+
+template <int D>
+static const void* ll_group_fn_dt(int op) {
+  switch (op) {
+    case nexrDevSum: return (const void*)&reduce_copy_ll_group_kernel<D, nexrDevSum>;
+    case nexrDevProd: return (const void*)&reduce_copy_ll_group_kernel<D, nexrDevProd>;
+    case nexrDevMinMax: return (const void*)&reduce_copy_ll_group_kernel<D, nexrDevMinMax>;
+    case nexrDevPreMulSum: return (const void*)&reduce_copy_ll_group_kernel<D, nexrDevPreMulSum>;
+    case nexrDevSumPostDiv:
+      if constexpr (Ty<D>::kIsInt) return (const void*)&reduce_copy_ll_group_kernel<D, nexrDevSumPostDiv>;
+      break;
+  }
+  return nullptr;
+}
+
+static const void* ll_group_fn(int dt, int op) {
+  switch (dt) {
+    case nexrInt8: return ll_group_fn_dt<nexrInt8>(op);
+    case nexrUint8: return ll_group_fn_dt<nexrUint8>(op);
+    case nexrInt32: return ll_group_fn_dt<nexrInt32>(op);
+    case nexrUint32: return ll_group_fn_dt<nexrUint32>(op);
+    case nexrInt64: return ll_group_fn_dt<nexrInt64>(op);
+    case nexrUint64: return ll_group_fn_dt<nexrUint64>(op);
+    case nexrFloat16: return ll_group_fn_dt<nexrFloat16>(op);
+    case nexrFloat32: return ll_group_fn_dt<nexrFloat32>(op);
+    case nexrFloat64: return ll_group_fn_dt<nexrFloat64>(op);
+    case nexrBfloat16: return ll_group_fn_dt<nexrBfloat16>(op);
+  }
+  return nullptr;
+}
+
+hipError_t launch_ll_group(int dt, int op, const LLStepsParams* table, int nMembers, int G, hipStream_t s) {
+  const void* fn = ll_group_fn(dt, op);
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {&table, &nMembers, &G};
+  return hipLaunchKernel(fn, dim3((unsigned)(nMembers * G)), dim3(kBlock), args, 0, s);
+}
+
+// Workgroups of the group kernel one CU keeps resident (the registers decide: no LDS).
+hipError_t ll_group_blocks_per_cu(int dt, int op, int* blocks) {
+  const void* fn = ll_group_fn(dt, op);
+  if (!fn) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fn, kBlock, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
 // LL128 (reference src/device/prims_ll128.h:86-331). The reference moves a 2 KiB wire slice per
 // warp-32: lane wid holds regs[2g..2g+1] = user 16-B chunk ix(g, wid) = g*32 - 4*(g/2) + wid -
 // (g%2)*(wid/8) and sends them as wire words 64g + 2wid (+1); lanes wid%8 == 7 carry the line flag

@@ -648,9 +648,103 @@ int llTicketEvery() {
   return every;
 }
 
+// Group launches (nexrRingCommSetLLGroup): every (channel, rank) of the collective is a member of one
+// nexrReduceCopyLLStepsGroup call on one stream. Where mode 2 could run but for its stream count: LL,
+// device memory, every rank on the one GPU (the completion-word wait), the library's own LL kernels and
+// device head words on every connection; and at most NEXR_LL_GROUP_MAX_MEMBERS members.
+bool llGroupAllowed(const nexrRingComm* c, size_t nMembers) {
+  if (!c->llGroup || c->proto != nexrRingProtoLL || c->cfg.memMode != nexrRingDeviceMemory || !c->stepWaitWord ||
+      c->cfg.llFn != defaultLLFn || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || c->streams.empty() || !c->streams[0] ||
+      !c->status[0] || !c->done[0])
+    return false;
+  for (int d : c->devices)
+    if (d != c->devices[0]) return false;
+  return true;
+}
+
+// One member's record: its connections at its first step, its whole step list, and the Conn objects
+// whose host counters the calling thread publishes once the launches are complete.
+struct GroupMember {
+  nexrLLConnSet cs;
+  std::vector<nexrLLStep> steps;
+  Conn* recv = nullptr;
+  Conn* send = nullptr;
+};
+
+// The recorded members as group launches on channel 0's first stream, one wait, then the host counters
+// (head / tail) as Prims::finishRun publishes them. nexrInvalidUsage from the group call (the grid is not
+// resident at once) comes back unchanged, with nothing launched: the caller falls back.
+nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int datatype, const nexrDevRedOpFull& red) {
+  const int n = (int)members.size();
+  std::vector<nexrLLConnSet> cs;
+  std::vector<const nexrLLStep*> steps;
+  std::vector<int> nSteps;
+  size_t longest = 1;
+  for (GroupMember& m : members) {
+    cs.push_back(m.cs);
+    steps.push_back(m.steps.data());
+    nSteps.push_back((int)m.steps.size());
+    longest = std::max(longest, m.steps.size());
+  }
+  if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+  size_t perLaunch = 0;
+  nexrResult_t r = nexrLLGroupWorkspaceBytes(n, &perLaunch);
+  if (r != nexrSuccess) return r;
+  perLaunch /= NEXR_LL_GROUP_LAUNCHES;
+  hipStream_t stream = c->streams[0];
+  uint32_t* status = c->status[0];
+  uint32_t* done = c->done[0];
+  const int timeoutMs = c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000;
+  // The workspace: NEXR_LL_GROUP_LAUNCHES launches of the communicator's most members at first; a
+  // collective that needs more (the call says so before any device work) doubles it, up to one launch
+  // per step, the most a call can need. The stream is idle here: every collective waits for its launches.
+  size_t want = std::max(c->groupWsBytes, perLaunch * NEXR_LL_GROUP_LAUNCHES);
+  for (;;) {
+    if (c->groupWsBytes < want) {
+      if (c->groupWs) (void)hipFree(c->groupWs);
+      c->groupWs = nullptr;
+      c->groupWsBytes = 0;
+      if (hipMalloc(&c->groupWs, want) != hipSuccess) return nexrUnhandledCudaError;
+      c->groupWsBytes = want;
+      c->groupWsDevice = c->devices[0];
+    }
+    __atomic_store_n(status, 0u, __ATOMIC_RELEASE);
+    r = nexrReduceCopyLLStepsGroup(n, cs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
+                                   &c->llRule, status, (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
+                                   (nexrStream_t)stream);
+    // every other argument is valid by construction: nexrInvalidArgument is the workspace
+    if (r != nexrInvalidArgument || c->groupWsBytes >= perLaunch * longest) break;
+    want = std::min(c->groupWsBytes * 2, perLaunch * longest);
+  }
+  if (r == nexrInvalidUsage) return r;
+  bool ok = r == nexrSuccess, landed = false;
+  const uint32_t t = ++done[1];
+  if (hipStreamWriteValue32(stream, done, t, 0) == hipSuccess) {
+    auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; spins++) {
+      if ((int32_t)(__atomic_load_n(done, __ATOMIC_ACQUIRE) - t) >= 0) {
+        landed = true;
+        break;
+      }
+      if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeoutMs)) break;
+      if (spins >= 4096) std::this_thread::yield();
+    }
+  }
+  if (!landed && hipStreamSynchronize(stream) != hipSuccess) {
+    if (r == nexrSuccess) r = nexrUnhandledCudaError;
+    ok = false;
+  }
+  for (GroupMember& m : members) {
+    if (m.recv) m.recv->st->head.store(m.recv->recvStep, std::memory_order_release);
+    if (m.send) m.send->st->tail.store(m.send->sendStep, std::memory_order_release);
+  }
+  if (ok && __atomic_load_n(status, __ATOMIC_ACQUIRE) != 0) r = nexrInternalError;  // a step timed out
+  return r;
+}
+
 // Thread-rank collectives: the ring schedules on one thread per rank.
 nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
-                            size_t count, int datatype, int op, int root) {
+                            size_t count, int datatype, int op, int root, bool tryGroup = true) {
   if (!c || c->peer) return nexrInvalidArgument;
   size_t esz;
   nexrDevRedOpFull red;
@@ -671,13 +765,27 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
   std::vector<ChannelPart> parts = channelParts(c, (int64_t)count, esz, trafficPerByte);
   for (ChannelPart& part : parts) part.chunkCount = chunkElems(channelComm(c, part.channel), g, esz, false, 0);
   Shared sh;
-  const bool llAsync = llAsyncAllowed(c);
-  const bool llRun = llRunAllowed(c, llAsync);
-  c->lastLLMode = llRun ? 2 : llAsync ? 1 : 0;
+  const bool group = tryGroup && llGroupAllowed(c, parts.size() * (size_t)n);
+  const bool llAsync = !group && llAsyncAllowed(c);
+  const bool llRun = !group && llRunAllowed(c, llAsync);
+  c->lastLLMode = group ? 3 : llRun ? 2 : llAsync ? 1 : 0;
+  // Group launches: the rank threads only record. Should the group call find its grid not resident, the
+  // collective runs again the usual way from the counters as they were (nothing has touched the device).
+  std::vector<GroupMember> members(group ? parts.size() * (size_t)n : 0);
+  std::vector<std::pair<uint64_t, uint64_t>> steps0;  // (sendStep, recvStep) of every ring connection
+  std::vector<uint64_t> cleaned0;
+  if (group)
+    for (const ChannelPart& part : parts) {
+      nexrRingComm* ck = channelComm(c, part.channel);
+      for (int rank = 0; rank < n; rank++) steps0.emplace_back(ck->conns[rank]->sendStep, ck->conns[rank]->recvStep);
+      cleaned0.push_back(ck->cleanedSteps.load(std::memory_order_relaxed));
+    }
   std::vector<std::function<void()>> jobs;
+  size_t partIx = 0;
   for (const ChannelPart& part : parts) {
     for (int rank = 0; rank < n; rank++) {
-      jobs.emplace_back([&, rank, part] {
+      GroupMember* member = group ? &members[partIx * (size_t)n + (size_t)rank] : nullptr;
+      jobs.emplace_back([&, rank, part, member] {
         nexrRingComm* ck = channelComm(c, part.channel);
         if (ck->streams[rank]) (void)hipSetDevice(ck->devices[rank]);
         Prims p = makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, red, g,
@@ -685,6 +793,13 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
         p.recv[p.nRecv++] = ck->conns[rank];
         p.send[p.nSend++] = ck->conns[(rank + 1) % n];
         p.attach();
+        if (member) {
+          p.enableLLRecord();
+          if (!p.llRecord) {
+            sh.fail(nexrInternalError);
+            return;
+          }
+        }
         if (llRun) p.enableLLRun();
         if (llAsync && !p.llRun) p.enableLLAsync(llTicketEvery());
         switch (coll) {
@@ -694,11 +809,39 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
           case kReduce: runRingReduce(p, n, root, part); break;
           case kBroadcast: runRingBroadcast(p, n, root, part); break;
         }
+        if (member) {  // recorded, not run: the calling thread launches every member's list together
+          if (!p.run.empty()) member->cs = p.connSet();
+          member->steps.swap(p.run);
+          member->recv = p.recv[0];
+          member->send = p.send[0];
+          return;
+        }
         p.finishLL();  // queued LL steps complete before the collective returns (even after a failure)
       });
     }
+    partIx++;
   }
-  return runThreads(c, sh, jobs);
+  r = runThreads(c, sh, jobs);
+  if (!group || r != nexrSuccess) return r;
+  // a member that recorded nothing still needs valid connections for the call's checks
+  members.erase(std::remove_if(members.begin(), members.end(), [](const GroupMember& m) { return m.steps.empty(); }),
+                members.end());
+  if (members.empty()) return nexrSuccess;
+  r = runGroup(c, members, datatype, red);
+  if (r == nexrInvalidUsage) {  // the grid does not fit the GPU at once: the usual mode, from the same counters
+    size_t ix = 0, ch = 0;
+    for (const ChannelPart& part : parts) {
+      nexrRingComm* ck = channelComm(c, part.channel);
+      for (int rank = 0; rank < n; rank++, ix++) {
+        ck->conns[rank]->sendStep = steps0[ix].first;
+        ck->conns[rank]->recvStep = steps0[ix].second;
+      }
+      ck->cleanedSteps.store(cleaned0[ch++], std::memory_order_relaxed);
+    }
+    return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root, false);
+  }
+  if (r != nexrSuccess) c->broken = true;  // step counters are mid-protocol
+  return r;
 }
 
 // Process-rank collectives: this process's rank of the same ring schedules.
@@ -1032,6 +1175,13 @@ NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t c, int* queued) {
   return nexrSuccess;
 }
 
+NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t c, int on) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer || c->proto != nexrRingProtoLL || c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
+  c->llGroup = on != 0;
+  return nexrSuccess;
+}
+
 NEXR_API nexrResult_t nexrRingCommSetLLFlagRule(nexrRingComm_t c, const nexrLLFlagRule* rule) {
   if (!c) return nexrInvalidArgument;
   const nexrLLFlagRule r = rule ? *rule : kLLProductionRule;
@@ -1097,6 +1247,10 @@ NEXR_API nexrResult_t nexrRingCommDestroy(nexrRingComm_t c) {
           k->fifo = nullptr;
         }
       }
+  }
+  if (c->groupWs) {
+    (void)hipSetDevice(c->groupWsDevice);
+    (void)hipFree(c->groupWs);
   }
   for (Conn* k : c->conns) freeConn(c, k);
   for (Conn* k : c->treeUp) freeConn(c, k);

@@ -20,7 +20,8 @@ RING_LIB_PATH = os.path.join(_HERE, "libnexr_ring.so")
 EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
                     "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrTreeTopology",
-                    "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLFlagRule",
+                    "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
+                    "nexrRingCommSetLLFlagRule",
                     "nexrRingCommGetLLCleanup", "nexrRingCommDestroy", "nexrPeerRingCommCreate",
                     "nexrPeerRingAllReduce", "nexrPeerRingReduceScatter", "nexrPeerRingAllGather",
                     "nexrPeerRingReduce", "nexrPeerRingBroadcast")
@@ -70,6 +71,7 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
+    L.nexrRingCommSetLLGroup.argtypes = [vp, i32]
     L.nexrRingCommSetLLFlagRule.argtypes = [vp, ctypes.POINTER(LLFlagRule)]
     L.nexrRingCommGetLLCleanup.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.nexrPeerRingCommCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(PeerRingConfig)]
@@ -226,12 +228,19 @@ class RingComm:
         return "word" if w.value else "sync"
 
     def queued(self) -> int:
-        """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 2 runs on the device
-        with device credits, 1 queued launches, 0 host-sequenced (LL steps need every rank on one GPU
-        and device memory for 1 or 2)."""
+        """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 3 group launches on
+        one stream (set_ll_group), 2 runs on the device with device credits, 1 queued launches,
+        0 host-sequenced (LL steps need every rank on one GPU and device memory for 1, 2 or 3; 1 and 2
+        also a hardware queue per rank stream)."""
         w = ctypes.c_int()
         _check(self._L.nexrRingCommGetQueued(self._h, ctypes.byref(w)), "nexrRingCommGetQueued")
         return int(w.value)
+
+    def set_ll_group(self, on: bool) -> None:
+        """Opt in to (or out of) group launches (nexrRingCommSetLLGroup): the LL steps of every rank and
+        channel of a ring collective in the same launches on one stream, queued() == 3. Between
+        collectives; InvalidUsage unless the communicator is thread-rank, LL and device-memory."""
+        _check(self._L.nexrRingCommSetLLGroup(self._h, 1 if on else 0), "nexrRingCommSetLLGroup")
 
     def set_ll_flag_rule(self, flag_max: int, clean_mask: int) -> None:
         """The LL flag rule of every channel (nexrRingCommSetLLFlagRule): (0, 0x7ffffff8) is the production
