@@ -367,7 +367,7 @@ typedef struct {
   const uint64_t* sendHead[NEXR_LL_STEPS_MAX_PEERS]; /* the receivers' head words of the send connections */
   uint64_t sendStep[NEXR_LL_STEPS_MAX_PEERS];
   uint64_t slotBytes; /* bytes per FIFO slot, every connection (16-B multiple) */
-  uint32_t nSlots;    /* NCCL_STEPS */
+  uint32_t nSlots;    /* NCCL_STEPS: 1 .. INT_MAX (more: nexrInvalidArgument) */
   uint32_t pad;
 } nexrLLConnSet;
 NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* conns, const nexrLLStep* steps, int nSteps,

@@ -2,6 +2,7 @@
 // geometry, the host-staged variant and the op encoder. Host code only; the kernels live in
 // nexr_kernels.hip (one object per datatype).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <string.h>
 #include <stdlib.h>
 #include <unistd.h>
@@ -1495,6 +1496,7 @@ static nexrResult_t llStepsValidate(const nexrLLConnSet* cs, const nexrLLStep* s
   if (cs->nRecv < 0 || cs->nRecv > NEXR_LL_STEPS_MAX_PEERS || cs->nSend < 0 || cs->nSend > NEXR_LL_STEPS_MAX_PEERS)
     return nexrInvalidArgument;
   if (cs->slotBytes == 0 || cs->slotBytes % 16 || cs->nSlots == 0) return nexrInvalidArgument;
+  if (cs->nSlots > (uint32_t)INT_MAX) return nexrInvalidArgument;  // the kernels keep it as an int
   if (!llRuleValid(rule, cs->nSlots)) return nexrInvalidArgument;
   if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
     return nexrInvalidArgument;

@@ -141,6 +141,12 @@ def test_steps_rule_is_validated_before_the_device(nexr):
     assert call((0x80, 0x78), n_steps=0) == 0     # cleaning period == flag period
     for ok in (None, (0, 0x7FFFFFF8), TEST_RULE, (0, 0x80000000), (0, 0xFFFFFFF8)):
         assert call(ok, n_steps=0) == 0, ok
+    # nSlots above INT_MAX would turn negative in the kernels (they keep it as an int): refused, though the
+    # rule itself is valid for that many slots (0x80000000 % 0x80000000 == 0); INT_MAX slots themselves pass
+    assert call((0, 0x80000000), n_steps=0, n_slots=0x80000000) == 4
+    assert call((0, 0x80000000), n_steps=1, n_slots=0x80000000) == 4
+    assert call((0, 0xFFFFFFFF), n_steps=0, n_slots=0xFFFFFFFF) == 4
+    assert call((0, 0x7FFFFFFF), n_steps=0, n_slots=0x7FFFFFFF) == 0
     with pytest.raises(nexr.NexrError) as e:
         nexr.reduce_copy_ll_steps(0x10000, 0x20000, [(0x100000, 0x200000, 0)], [], 1 << 16, [step], 7, 0,
                                   rule=(0x30, 0x78))

@@ -21,12 +21,13 @@ Y_FIFO, Y_HEAD = 0x300000, 0x300000 + 8 * SLOT
 WS = 0x800000
 
 
-def _call(nexr, members, dt=F32, op=0, rule=None, ws=WS, ws_bytes=None, slot=SLOT, n_members=None, null=None):
+def _call(nexr, members, dt=F32, op=0, rule=None, ws=WS, ws_bytes=None, slot=SLOT, n_members=None, null=None,
+          n_slots=8):
     """members: (recv, send, steps) per member, recv / send as (fifo, head, step) lists. Returns the code."""
     L = nexr.lib()
     n = len(members) if n_members is None else n_members
     sets = [nexr.ll_conn_set(0x10000 * (m + 1), 0x20000000 + 0x10000 * m, r, s, slot[m] if isinstance(slot, list)
-                             else slot) for m, (r, s, _steps) in enumerate(members)]
+                             else slot, n_slots) for m, (r, s, _steps) in enumerate(members)]
     cs = (nexr.LLConnSet * max(1, len(sets)))(*sets)
     arrs = [(nexr.LLStep * max(1, len(st)))(*st) for _r, _s, st in members]
     ptrs = (ctypes.POINTER(nexr.LLStep) * max(1, len(arrs)))(*[ctypes.cast(a, ctypes.POINTER(nexr.LLStep))
@@ -90,6 +91,12 @@ def test_bad_arguments_fail_before_the_device(nexr):
     assert _call(nexr, bad) == 4
     assert _call(nexr, pair, ws=0) == 4                                  # no workspace
     assert _call(nexr, pair, ws=WS + 4) == 4                             # misaligned workspace
+    # nSlots above INT_MAX (the kernels keep it as an int), under a rule that is valid for that many slots
+    # (checked with empty step lists, which return 0 once the arguments have passed: the largest int does)
+    empty = [(r, s, []) for r, s, _st in pair]
+    assert _call(nexr, empty, rule=(0, 0x80000000), n_slots=0x80000000, ws=0) == 4
+    assert _call(nexr, pair, rule=(0, 0x80000000), n_slots=0x80000000, ws_bytes=8) == 4
+    assert _call(nexr, empty, rule=(0, 0x7FFFFFFF), n_slots=0x7FFFFFFF, ws=0) == 0
 
 
 def test_a_workspace_that_holds_too_few_launches(nexr):
