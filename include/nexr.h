@@ -86,7 +86,10 @@ typedef enum {
   nexrDevProd = 1,
   nexrDevMinMax = 2,     /* redOpArg bit 0: 0 = min, 1 = max (reduce_kernel.h:64) */
   nexrDevPreMulSum = 3,  /* preOp: x * scalar (scalar = raw bits of T in preOpArgs[s]) */
-  nexrDevSumPostDiv = 4, /* integer types only; redOpArg = divisor<<1 | isSigned */
+  nexrDevSumPostDiv = 4, /* integer types only; redOpArg = divisor<<1 | isSigned. isSigned alone, not the
+                          * datatype, selects the signed quotient (reduce_kernel.h:79-97), which divides by the
+                          * divisor truncated to T: a 1-byte type with isSigned set and a divisor whose low
+                          * byte is 0 is nexrInvalidArgument; with isSigned clear every divisor is valid. */
   nexrNumDevRedOps = 5
 } nexrDevRedOp_t;
 

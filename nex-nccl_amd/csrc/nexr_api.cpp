@@ -208,9 +208,10 @@ nexrResult_t validate(int nSrcs, const void* const* srcs, int nDsts, void* const
   if (op < 0 || op >= nexrNumDevRedOps) return nexrInvalidArgument;
   // SumPostDiv kernels exist for integer types only (generate.py:108 required_cuda).
   if (op == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (op == nexrDevSumPostDiv && isSignedInt(datatype)) {
-    // The signed quotient divides by the divisor truncated to T (reduce_kernel.h:94): a
-    // divisor that truncates to 0 would divide by zero.
+  if (op == nexrDevSumPostDiv && (redOpArg & 1) != 0) {
+    // The signed quotient (taken by bit 0 of redOpArg, whatever the datatype's own signedness:
+    // reduce_kernel.h:79-97) divides by the divisor truncated to T (:94): a divisor that
+    // truncates to 0 would divide by zero. Only a 1-byte T can truncate a non-zero divisor to 0.
     uint32_t divisor = (uint32_t)(redOpArg >> 1);
     if (divisor == 0) divisor = 1;
     size_t sz = typeSize(datatype);
@@ -1415,7 +1416,7 @@ NEXR_API nexrResult_t nexrReduceCopyLL(const void* src, int srcIsInput, int nRec
     return nexrInvalidArgument;
   if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
   if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && isSignedInt(datatype) && typeSize(datatype) == 1) {
+  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
     uint32_t divisor = (uint32_t)(redOpArg >> 1);
     if (divisor == 0) divisor = 1;
     if ((int8_t)divisor == 0) return nexrInvalidArgument;
@@ -1502,7 +1503,7 @@ static nexrResult_t llStepsValidate(const nexrLLConnSet* cs, const nexrLLStep* s
     return nexrInvalidArgument;
   if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
   if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && isSignedInt(datatype) && typeSize(datatype) == 1) {
+  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
     uint32_t divisor = (uint32_t)(redOpArg >> 1);
     if (divisor == 0) divisor = 1;
     if ((int8_t)divisor == 0) return nexrInvalidArgument;
@@ -1883,7 +1884,7 @@ NEXR_API nexrResult_t nexrReduceCopyLL128(const void* src, int srcIsInput, int n
     return nexrInvalidArgument;
   if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
   if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && isSignedInt(datatype) && typeSize(datatype) == 1) {
+  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
     uint32_t divisor = (uint32_t)(redOpArg >> 1);
     if (divisor == 0) divisor = 1;
     if ((int8_t)divisor == 0) return nexrInvalidArgument;

@@ -278,7 +278,7 @@ static int check(int nSrcs, int nDsts, int dt, int op, uint64_t arg, int nPreOp,
   if (dt < 0 || dt >= DT_NUM || dt == DT_F8E4M3 || dt == DT_F8E5M2) return R_INVALID;
   if (op < 0 || op >= OP_NUM) return R_INVALID;
   if (op == OP_SUMPOSTDIV && dt > DT_U64) return R_INVALID;
-  if (op == OP_SUMPOSTDIV && dt == DT_I8) {
+  if (op == OP_SUMPOSTDIV && (arg & 1) != 0 && (dt == DT_I8 || dt == DT_U8)) { /* the signed path: div_u8 */
     uint32_t d = (uint32_t)(arg >> 1);
     if (d == 0) d = 1;
     if ((int8_t)d == 0) return R_INVALID;

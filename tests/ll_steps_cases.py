@@ -205,3 +205,25 @@ def routing_case(dt, op, arg, seed) -> Case:
                MemberSpec(xs[1], xs[4], [2], [0], list(leaf)),
                MemberSpec(xs[2], xs[5], [3], [1], list(leaf))]
     return Case(dt, op, arg, 4096, None, [5, 14, 3, 9], {}, members)
+
+
+# ---- G: the arithmetic edge pairs through one member's run ------------------------------------------------
+def edge_pairs_case(dt, op, arg, peer, src, slot_bytes) -> Case:
+    """One member, one receive connection pre-filled with `peer` and one send connection: recvReduceCopySend
+    of `src` (the user input, to the output at the same offsets) in full-slot steps and a last step with
+    what is left, at most SLOTS of them (nobody frees a pre-filled slot). For tests/test_arith_edges*.py:
+    `peer` and `src` are the two operand vectors of tests/arith_edges.py's pair layout, any integer dtype of
+    the element's width."""
+    e = esz_of(dt)
+    n = int(src.size)
+    assert peer.size == n and peer.itemsize == e and src.itemsize == e
+    per = slot_bytes // 2 // e
+    steps, pieces = [], []
+    for o in range(0, n, per):
+        m = min(per, n - o)
+        steps.append(ll_steps.Step(0, o, 1, o, m, True, True, False))
+        pieces.append(peer[o:o + m])
+    assert len(steps) <= SLOTS
+    blank = np.full(n * e, FILL, dtype=np.uint8).view(src.dtype)
+    member = MemberSpec(src, blank, [0], [1], steps)
+    return Case(dt, op, arg, slot_bytes, None, [RECV_START[0], SEND_START[0]], {0: pieces}, [member])

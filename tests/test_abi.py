@@ -91,6 +91,36 @@ def test_invalid_arguments_fail_before_the_device(nexr):
     assert L.nexrReduceCopy(2, sa, 1, da, 16, 7, 0, 0, 1, None, 0, None) == 4  # preOpArgs NULL
 
 
+def test_sumpostdiv_validation_follows_the_sign_flag(nexr):
+    """The signed quotient is taken by bit 0 of redOpArg, whatever the datatype's signedness
+    (reduce_kernel.h:79-97), and divides by the divisor truncated to T: a 1-byte type with the flag set and a
+    divisor whose low byte is 0 is refused (it would divide by zero); with the flag clear the call is valid
+    (nexrInt8 by 256: every quotient is 0). Every entry point, before any device call (zero elements / steps
+    end a valid call there)."""
+    I8, U8, I32, POSTDIV = 0, 1, 2, 4
+    cases = [(U8, (256 << 1) | 1, 4), (I8, (256 << 1) | 1, 4), (U8, (0x80000000 << 1) | 1, 4),
+             (I8, (256 << 1) | 0, 0), (U8, (256 << 1) | 0, 0), (I8, (255 << 1) | 1, 0), (U8, (257 << 1) | 1, 0),
+             (I32, (256 << 1) | 1, 0), (I8, 1, 0)]  # divisor 0 means 1
+    for dt, arg, want in cases:
+        what = (dt, hex(arg))
+        assert _call(nexr, nsrcs=1, n=0, dt=dt, op=POSTDIV, arg=arg) == want, what
+
+        def rc_of(fn, *a, **kw):
+            try:
+                fn(*a, **kw)
+                return 0
+            except nexr.NexrError as e:
+                return int(e.code)
+        assert rc_of(nexr.reduce_copy_ll, 0x1000, [], [], 0x2000, [], [], 0, dt, POSTDIV, arg, True, True) == want, what
+        assert rc_of(nexr.reduce_copy_ll128, 0x1000, [], [], 0x2000, [], [], 0, dt, POSTDIV, arg, True, True) == want, \
+            what
+        assert rc_of(nexr.reduce_copy_ll_steps, 0x1000, 0x2000, [], [], 4096, [], dt, POSTDIV, arg) == want, what
+        assert rc_of(nexr.reduce_copy_ll_steps, 0x1000, 0x2000, [], [], 4096, [], dt, POSTDIV, arg,
+                     rule=(0x100, 0x78)) == want, what
+        w = nexr.make_work([0x1000], [0x2000], 0, arg, None, True)
+        assert rc_of(nexr.reduce_copy_batch, [w], dt, POSTDIV) == want, what
+
+
 def test_host_registration_validates_before_the_device(nexr):
     """nexrHostRegister / Deregister / MemAlloc / MemFree / GetHostPathStats reject bad arguments and
     accept the NULL no-ops (ncclCommDeregister and ncclMemFree take NULL, register.cc:147, allocator.cc)
