@@ -35,8 +35,9 @@ extern "C" {
 #define NEXR_API __attribute__((visibility("default")))
 
 /* 0.3.0 also covers the LL flag rule (nexrLLFlagRule, nexrReduceCopyLLStepsRule, nexrLLCleanSlot) and the
- * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup): additions only, no existing
- * entry point or struct layout changed, so the version stays. */
+ * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup, and nexrReduceCopyLL128StepsGroup
+ * for LL128 step lists): additions only, no existing entry point or struct layout changed, so the version
+ * stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
 #define NEXR_VERSION_PATCH 0
@@ -310,6 +311,15 @@ NEXR_API nexrResult_t nexrReduceCopyLL(const void* src, int srcIsInput, int nRec
  * loadRegsFinish/storeRegs :86-174) — byte-identical to the reference's warp-32 layout. Arithmetic,
  * peer-first operand order, status/timeout and pointer rules as nexrReduceCopyLL; wire buffers must
  * be 16-B aligned and hold ceil(nElts*size/1920) slices.
+ *
+ * Hand-off contract. The kernel accepts a line's data units from the same load that returned the line's
+ * flag, and the producing kernel stores a line's data units and its flag unit in one instruction. A line
+ * has ONE flag per 128 bytes and only 16-byte granules are observed untorn on gfx950 (the reference leans
+ * on NVIDIA's 128-byte warp store, :186-204, :278-285), so a consumer that polls a slot while its
+ * producer writes it could accept a line whose flag unit is new and another unit still old. The
+ * consumer's kernel must therefore not START before its producer's kernel has COMPLETED (stream order,
+ * an event, or a host wait; the ring's host sequencing does the last). Hand-off between kernels that run
+ * at the same time is what nexrReduceCopyLL128StepsGroup is for.
  */
 NEXR_API nexrResult_t nexrReduceCopyLL128(const void* src, int srcIsInput, int nRecv, const void* const* recvWire,
                                           const uint64_t* recvFlags, void* dst, int nSend, void* const* sendWire,
@@ -463,6 +473,46 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnS
                                                  int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rule,
                                                  uint32_t* status, uint32_t timeoutUs, void* workspace,
                                                  size_t workspaceBytes, nexrStream_t stream);
+
+/*
+ * nexrReduceCopyLL128StepsGroup — LL128 step lists of nMembers Primitives (1..NEXR_LL_GROUP_MAX_MEMBERS)
+ * in the same launches on ONE stream: nexrReduceCopyLLStepsGroup for the LL128 wire (reference
+ * src/device/prims_ll128.h: GenericOp :294-331, waitSend / postRecv :58-75, loadRegsBegin / recvReduceSendCopy
+ * :86-292). nexrLLConnSet and nexrLLStep are used unchanged, read for LL128:
+ *   - slotBytes is a multiple of 2048: a slot holds slotBytes / 2048 wire slices of 16 lines x 128 bytes,
+ *     1920 data bytes each, so a step's nElts may fill at most slotBytes / 2048 * 1920 bytes (more:
+ *     nexrInvalidArgument). The wire is byte-identical to nexrReduceCopyLL128's and the reference's: user
+ *     chunk map ix(g, wid), the 64-bit flag in word 15 of every line;
+ *   - the flags are recvStep + 1 / sendStep + 1 as 64-bit values, counted per connection from the
+ *     counters in conns[m]; there is no flag rule and no cleanup (the reference cleans nothing for LL128).
+ * Element arithmetic, peer-first operand order, pre/post op, the reduction semantics (nccl / fork /
+ * shipped) and the datatypes and ops accepted are those of nexrReduceCopyLL128, per step.
+ *
+ * The hand-off is ordered by construction, which is what lets a consumer poll a slot while its producer
+ * writes it (the single step nexrReduceCopyLL128 does not allow that, see there). A producing wave stores
+ * the seven data units of each of its lines for every send connection, waits until those stores have
+ * completed, and only then stores the lines' flag units (8 data bytes and the flag in one 16-byte
+ * store); a consuming wave polls the flag units and, once every flag is there, loads the lines AGAIN, so
+ * that a data unit enters the arithmetic only from a load issued after the flag had been seen. Credits
+ * are per wave on the device head words (NEXR_LL_HEAD_BYTES per connection, zeroed before the first
+ * use), as in nexrReduceCopyLLSteps: tile t (4 KiB of wire) of every step belongs to workgroup t % G,
+ * G = min(64, ceil(slotBytes / 4096)), on both ends. A line or a credit that never comes within timeoutUs
+ * sets *status = 1 and ends its wave's run; a non-zero *status ends the other polls early; the launch
+ * never hangs.
+ *
+ * Everything else is nexrReduceCopyLLStepsGroup's, by the same host code: the argument checks, equal
+ * slotBytes / nSlots across members, the launch cuts (96 steps, a member's user-range conflict, applied
+ * to all members at one step index), the dry run (nexrInvalidUsage when a launch cannot finish), the
+ * co-residency check (nexrInvalidUsage) and the workspace rules, sized by nexrLLGroupWorkspaceBytes (the
+ * table entries are the same). All of these return before any device call. A group of ONE member with
+ * one-ended connections is the "run" form: its peer's launch must then be able to run at the same time
+ * (a stream on a hardware queue of its own, grids resident together), which is the caller's business.
+ */
+NEXR_API nexrResult_t nexrReduceCopyLL128StepsGroup(int nMembers, const nexrLLConnSet* conns,
+                                                    const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                    int devRedOp, uint64_t redOpArg, uint32_t* status,
+                                                    uint32_t timeoutUs, void* workspace, size_t workspaceBytes,
+                                                    nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

@@ -136,9 +136,9 @@ NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t comm, int* word);
  * where 1 is possible and the communicator uses the library's own LL kernels; NEXR_LL_RUN=0 falls back
  * to 1). 1: queued, each step's kernel on the rank's stream with no host wait after it, the slots a
  * step read released once a completion ticket behind it lands (one per NEXR_LL_TICKET_EVERY steps,
- * default 4). 0: host-sequenced (SIMPLE, LL128, ranks on several GPUs, host memory, NEXR_LL_ASYNC=0,
- * or more rank streams on a GPU than it has hardware queues beside the default stream's). 3: group
- * launches on one stream (nexrRingCommSetLLGroup, below). */
+ * default 4). 0: host-sequenced (SIMPLE, LL128 without the group option, ranks on several GPUs, host
+ * memory, NEXR_LL_ASYNC=0, or more rank streams on a GPU than it has hardware queues beside the default
+ * stream's). 3: group launches on one stream (nexrRingCommSetLLGroup, below; LL and LL128). */
 NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
 
 /* Opt-in: run the LL steps of every rank (and channel) of a ring collective in group launches on ONE
@@ -153,8 +153,15 @@ NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
  * head words from the step counters both modes keep. A collective falls back to the mode it would have
  * run without the option when its ranks span several GPUs, the communicator has a caller's llFn, the
  * collective has more than NEXR_LL_GROUP_MAX_MEMBERS (channel, rank) members, or the group's grid is not
- * resident at once on the GPU. The tree all-reduce is not affected. nexrInvalidUsage unless the
- * communicator has thread ranks, the LL protocol and device memory. */
+ * resident at once on the GPU. The tree all-reduce is not affected.
+ *
+ * LL128 communicators take the option too: their step lists go to nexrReduceCopyLL128StepsGroup, whose
+ * hand-off is ordered by construction (include/nexr.h), the only way LL128 steps of two ranks run at the
+ * same time; with the option off (the default) an LL128 communicator stays host-sequenced, mode 0, and
+ * every fall-back above (a caller's ll128Fn in place of llFn) returns to that. There is no flag rule and
+ * no cleanup for LL128.
+ *
+ * nexrInvalidUsage unless the communicator has thread ranks, the LL or LL128 protocol and device memory. */
 NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t comm, int on);
 
 /* The LL flag rule of this communicator (nexrLLFlagRule, include/nexr.h; NULL or {0, 0x7ffffff8}: the

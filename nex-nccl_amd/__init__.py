@@ -86,7 +86,8 @@ TYPE_SIZE = {DataType.Int8: 1, DataType.Uint8: 1, DataType.Int32: 4, DataType.Ui
 ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevice", "nexrReduceCopyMultiDeviceSets",
                "nexrReduceCopyHost", "nexrHostToDevRedOp", "nexrLaunchOneRank",
                "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrReduceCopyLLStepsRule",
-               "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
+               "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrReduceCopyLL128StepsGroup",
+               "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
 
@@ -277,6 +278,9 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopyLLStepsGroup.argtypes = [i32, P(LLConnSet), P(P(LLStep)), P(i32), i32, i32, u64, P(LLFlagRule),
                                              vp, ctypes.c_uint32, vp, sz, vp]
     L.nexrReduceCopyLLStepsGroup.restype = i32
+    L.nexrReduceCopyLL128StepsGroup.argtypes = [i32, P(LLConnSet), P(P(LLStep)), P(i32), i32, i32, u64, vp,
+                                                ctypes.c_uint32, vp, sz, vp]
+    L.nexrReduceCopyLL128StepsGroup.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -571,6 +575,33 @@ def reduce_copy_ll_steps_group(members: Sequence[tuple], slot_bytes: int, dataty
                                           ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None, int(ws_bytes),
                                           ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrReduceCopyLLStepsGroup")
+    return keep
+
+
+def reduce_copy_ll128_steps_group(members: Sequence[tuple], slot_bytes: int, datatype: int, dev_red_op: int,
+                                  red_op_arg: int = 0, n_slots: int = 8, status: int = 0, timeout_us: int = 0,
+                                  stream: int = 0, workspace=None):
+    """LL128 step lists of several Primitives in the same launches on one stream, with the ordered
+    hand-off (nexrReduceCopyLL128StepsGroup). The calling shape of reduce_copy_ll_steps_group, without a
+    flag rule: slot_bytes is a multiple of 2048 and a step fills at most slot_bytes / 2048 * 1920 bytes."""
+    n = len(members)
+    cs = (LLConnSet * max(1, n))(*[ll_conn_set(m[0], m[1], m[2], m[3], slot_bytes, n_slots) for m in members])
+    arrs = [(LLStep * max(1, len(m[4])))(*m[4]) for m in members]
+    ptrs = (ctypes.POINTER(LLStep) * max(1, n))(*[ctypes.cast(a, ctypes.POINTER(LLStep)) for a in arrs])
+    counts = (ctypes.c_int * max(1, n))(*[len(m[4]) for m in members])
+    keep = None
+    if workspace is None and 1 <= n <= LL_GROUP_MAX_MEMBERS:
+        import torch
+        longest = max([len(m[4]) for m in members] + [1])
+        keep = torch.empty(ll_group_workspace_bytes(n, longest), dtype=torch.uint8, device="cuda")
+        workspace = (keep.data_ptr(), keep.numel())
+    ws_ptr, ws_bytes = workspace if workspace is not None else (0, 0)
+    rc = lib().nexrReduceCopyLL128StepsGroup(n, cs, ptrs, counts, int(datatype), int(dev_red_op),
+                                             int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                             ctypes.c_void_p(int(status)) if status else None, int(timeout_us),
+                                             ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None, int(ws_bytes),
+                                             ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrReduceCopyLL128StepsGroup")
     return keep
 
 

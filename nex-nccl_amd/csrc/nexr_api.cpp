@@ -1490,15 +1490,17 @@ NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* cs, const nexrL
 }
 
 // The argument checks of a run of LL steps of one Primitives (nexrReduceCopyLLStepsRule, and every member
-// of nexrReduceCopyLLStepsGroup): nothing here touches the device.
+// of nexrReduceCopyLLStepsGroup): nothing here touches the device. rule == nullptr: LL128 steps (every
+// member of nexrReduceCopyLL128StepsGroup), whose slots are whole 2 KiB slices of 1920 data bytes and whose
+// 64-bit flags need no rule.
 static nexrResult_t llStepsValidate(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps, int datatype,
-                                    int devRedOp, uint64_t redOpArg, const nexrLLFlagRule& rule) {
+                                    int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rule) {
   if (!cs || nSteps < 0 || (nSteps > 0 && !steps)) return nexrInvalidArgument;
   if (cs->nRecv < 0 || cs->nRecv > NEXR_LL_STEPS_MAX_PEERS || cs->nSend < 0 || cs->nSend > NEXR_LL_STEPS_MAX_PEERS)
     return nexrInvalidArgument;
-  if (cs->slotBytes == 0 || cs->slotBytes % 16 || cs->nSlots == 0) return nexrInvalidArgument;
+  if (cs->slotBytes == 0 || cs->slotBytes % (rule ? 16 : kLL128SliceBytes) || cs->nSlots == 0) return nexrInvalidArgument;
   if (cs->nSlots > (uint32_t)INT_MAX) return nexrInvalidArgument;  // the kernels keep it as an int
-  if (!llRuleValid(rule, cs->nSlots)) return nexrInvalidArgument;
+  if (rule && !llRuleValid(*rule, cs->nSlots)) return nexrInvalidArgument;
   if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
     return nexrInvalidArgument;
   if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
@@ -1515,7 +1517,8 @@ static nexrResult_t llStepsValidate(const nexrLLConnSet* cs, const nexrLLStep* s
     if (!cs->sendFifo[i] || ((uintptr_t)cs->sendFifo[i] & 15) || !cs->sendHead[i] || ((uintptr_t)cs->sendHead[i] & 7))
       return nexrInvalidArgument;
   const size_t esz = typeSize(datatype);
-  const uint64_t slotData = cs->slotBytes / 2;  // 8 data bytes per 16-byte line
+  // 8 data bytes per 16-byte line; LL128: 1920 per 2 KiB slice
+  const uint64_t slotData = rule ? cs->slotBytes / 2 : cs->slotBytes / kLL128SliceBytes * kLL128SliceData;
   for (int k = 0; k < nSteps; k++) {
     const nexrLLStep& s = steps[k];
     if (s.srcBuf < -1 || s.srcBuf > 1 || s.dstBuf < -1 || s.dstBuf > 1) return nexrInvalidArgument;
@@ -1536,7 +1539,7 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const n
                                                 const nexrLLFlagRule* rulePtr, uint32_t* status, uint32_t timeoutUs,
                                                 nexrStream_t stream) {
   const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
-  const nexrResult_t valid = llStepsValidate(cs, steps, nSteps, datatype, devRedOp, redOpArg, rule);
+  const nexrResult_t valid = llStepsValidate(cs, steps, nSteps, datatype, devRedOp, redOpArg, &rule);
   if (valid != nexrSuccess) return valid;
   if (nSteps == 0) return nexrSuccess;
   const size_t esz = typeSize(datatype);
@@ -1633,19 +1636,19 @@ namespace {
 // Test hook: NEXR_TEST_LL_GROUP_RESIDENT=k makes the next calls take k as that number, so that the
 // rejection of a grid that does not fit (and the ring's fall-back) can be tested on a GPU that fits it.
 // Read per call (tests set it between calls).
-nexrResult_t llGroupResident(int dt, int op, int64_t* resident) {
+nexrResult_t llGroupResident(bool ll128, int dt, int op, int64_t* resident) {
   if (const char* e = getenv("NEXR_TEST_LL_GROUP_RESIDENT"))
     if (*e) {
       *resident = strtoll(e, nullptr, 10);
       return nexrSuccess;
     }
   constexpr int kDevs = 16;
-  static std::atomic<int64_t> cache[kDevs][nexrNumTypes][nexrNumDevRedOps];
+  static std::atomic<int64_t> cache[2][kDevs][nexrNumTypes][nexrNumDevRedOps];  // [LL, LL128]: a kernel each
   int dev = 0;
   NEXR_HIP(hipGetDevice(&dev));
   const bool cached = dev >= 0 && dev < kDevs;
   if (cached) {
-    const int64_t v = cache[dev][dt][op].load(std::memory_order_relaxed);
+    const int64_t v = cache[ll128][dev][dt][op].load(std::memory_order_relaxed);
     if (v > 0) {
       *resident = v;
       return nexrSuccess;
@@ -1653,21 +1656,22 @@ nexrResult_t llGroupResident(int dt, int op, int64_t* resident) {
   }
   int cus = 0, blocks = 0;
   NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  NEXR_HIP(ll_group_blocks_per_cu(dt, op, &blocks));
+  NEXR_HIP(ll128 ? ll128_group_blocks_per_cu(dt, op, &blocks) : ll_group_blocks_per_cu(dt, op, &blocks));
   *resident = (int64_t)blocks * cus;
-  if (cached && *resident > 0) cache[dev][dt][op].store(*resident, std::memory_order_relaxed);
+  if (cached && *resident > 0) cache[ll128][dev][dt][op].store(*resident, std::memory_order_relaxed);
   return nexrSuccess;
 }
-}  // namespace
 
-NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnSet* conns,
-                                                 const nexrLLStep* const* steps, const int* nSteps, int datatype,
-                                                 int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rulePtr,
-                                                 uint32_t* status, uint32_t timeoutUs, void* workspace,
-                                                 size_t workspaceBytes, nexrStream_t stream) {
+// The host side of both group calls: the argument checks, the launch cuts, the dry run, the workspace and
+// residency checks, the one copy of the tables and the launches. rule == nullptr: LL128 steps
+// (nexrReduceCopyLL128StepsGroup), which have no cleaning steps (so no cut behind one), slots counted in
+// 2 KiB slices and a kernel (and so an occupancy) of their own; everything else is the same code.
+nexrResult_t llStepsGroup(int nMembers, const nexrLLConnSet* conns, const nexrLLStep* const* steps, const int* nSteps,
+                          int datatype, int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rule, uint32_t* status,
+                          uint32_t timeoutUs, void* workspace, size_t workspaceBytes, nexrStream_t stream) {
   constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  const bool ll128 = rule == nullptr;
   if (nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || !conns || !steps || !nSteps) return nexrInvalidArgument;
-  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
   int maxSteps = 0;
   for (int m = 0; m < nMembers; m++) {
     const nexrResult_t valid = llStepsValidate(&conns[m], steps[m], nSteps[m], datatype, devRedOp, redOpArg, rule);
@@ -1711,7 +1715,7 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnS
     P.nSend = cs.nSend;
     P.nSlots = (int)cs.nSlots;
     P.firstWins = firstWins;
-    P.flagMask = rule.flagMax ? rule.flagMax - 1 : 0xffffffffu;
+    P.flagMask = rule && rule->flagMax ? rule->flagMax - 1 : 0xffffffffu;
   }
   std::vector<std::vector<UserRange>> seen((size_t)nMembers);
   auto cut = [&]() {  // the launch is complete: its blocks go into the table, the next one starts at the counters
@@ -1760,10 +1764,10 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnS
       P.step[P.nSteps++] = s;
       if (rd[(size_t)m].end) seen[(size_t)m].push_back(rd[(size_t)m]);
       if (wr[(size_t)m].end) seen[(size_t)m].push_back(wr[(size_t)m]);
-      if (s.send)
+      if (s.send && rule)
         for (int j = 0; j < conns[m].nSend; j++) {
           const uint64_t ss = P.sendStep[j] + sent;
-          if (((uint32_t)ss & rule.cleanMask) == rule.cleanMask) {
+          if (((uint32_t)ss & rule->cleanMask) == rule->cleanMask) {
             P.cleanLast |= 1u << j;
             P.cleanStep[j] = ss;
             cleans = true;
@@ -1834,20 +1838,44 @@ NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnS
   if (workspaceBytes / kLLGroupEntryBytes / (size_t)nMembers < nLaunches) return nexrInvalidArgument;
 
   // Co-residency: all nMembers * G workgroups at once, or a poll could wait for a workgroup that has no CU.
-  const uint64_t slotTiles = (conns[0].slotBytes / 16 + kLLTileLines - 1) / kLLTileLines;
+  // (a workgroup per tile of a slot: kLLTileLines 16-byte lines, or kLL128TileUnits 16-byte wire units)
+  const uint64_t tileUnits = ll128 ? kLL128TileUnits : kLLTileLines;
+  const uint64_t slotTiles = (conns[0].slotBytes / 16 + tileUnits - 1) / tileUnits;
   const int G = (int)(slotTiles < 1 ? 1 : slotTiles > (uint64_t)kLLStepsMaxGrid ? kLLStepsMaxGrid : slotTiles);
   int64_t resident = 0;
-  const nexrResult_t occ = llGroupResident(datatype, devRedOp, &resident);
+  const nexrResult_t occ = llGroupResident(ll128, datatype, devRedOp, &resident);
   if (occ != nexrSuccess) return occ;
   if ((int64_t)nMembers * G > resident) return nexrInvalidUsage;
 
   // Pageable source: the runtime has staged it when the call returns, so `table` may go out of scope.
   NEXR_HIP(hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(LLStepsParams), hipMemcpyHostToDevice,
                           (hipStream_t)stream));
-  for (size_t l = 0; l < nLaunches; l++)
-    NEXR_HIP(launch_ll_group(datatype, devRedOp, (const LLStepsParams*)workspace + l * (size_t)nMembers, nMembers, G,
-                             (hipStream_t)stream));
+  for (size_t l = 0; l < nLaunches; l++) {
+    const LLStepsParams* entries = (const LLStepsParams*)workspace + l * (size_t)nMembers;
+    NEXR_HIP(ll128 ? launch_ll128_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream)
+                   : launch_ll_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream));
+  }
   return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnSet* conns,
+                                                 const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                 int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rulePtr,
+                                                 uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                 size_t workspaceBytes, nexrStream_t stream) {
+  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
+  return llStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, &rule, status, timeoutUs,
+                      workspace, workspaceBytes, stream);
+}
+
+NEXR_API nexrResult_t nexrReduceCopyLL128StepsGroup(int nMembers, const nexrLLConnSet* conns,
+                                                    const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                    int devRedOp, uint64_t redOpArg, uint32_t* status,
+                                                    uint32_t timeoutUs, void* workspace, size_t workspaceBytes,
+                                                    nexrStream_t stream) {
+  return llStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, nullptr, status, timeoutUs,
+                      workspace, workspaceBytes, stream);
 }
 
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,

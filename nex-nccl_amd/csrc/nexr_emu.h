@@ -187,7 +187,7 @@ struct nexrRingComm {
   bool stepWaitWord = true;
   // How the last thread-rank ring collective ran its LL steps (diagnostics, nexrRingCommGetQueued):
   // 0 host-sequenced, 1 queued launches (Prims::enableLLAsync), 2 runs with device credits (enableLLRun).
-  // 3: group launches on one stream (nexrRingCommSetLLGroup).
+  // 3: group launches on one stream (nexrRingCommSetLLGroup; LL and LL128).
   int lastLLMode = 0;
   // nexrRingCommSetLLGroup: the option, and the device workspace of the group launches' tables (made by
   // the first group collective on the ranks' GPU, grown when a collective needs more launches).
@@ -460,8 +460,10 @@ struct Prims {
   // and the host hand-offs of the queued mode are gone. Conditions (llRunAllowed, nexr_ring.cpp): those
   // of the queued mode (every rank's kernels can run at once on the one GPU), the library's own LL
   // kernels, and device head words on every connection.
-  void enableLLRun() {
-    if (proto != nexrRingProtoLL || !device || !done || !status || !c->stepWaitWord) return;
+  void enableLLRun(bool ll128Too = false) {
+    if (!(proto == nexrRingProtoLL || (ll128Too && proto == nexrRingProtoLL128)) || !device || !done || !status ||
+        !c->stepWaitWord)
+      return;
     if (nRecv > NEXR_LL_STEPS_MAX_PEERS || nSend > NEXR_LL_STEPS_MAX_PEERS) return;
     for (int i = 0; i < nRecv; i++)
       if (!recv[i]->devHead || slot(recv[i]) != c->stepBytes) return;
@@ -473,9 +475,11 @@ struct Prims {
   }
   // Group launches (nexrRingCommSetLLGroup): the run mode's recording with no flush. The rank thread only
   // collects its whole step list; the calling thread launches every member's at once (ringCollective).
+  // LL128 too: its lists go to nexrReduceCopyLL128StepsGroup, the only LL128 kernel whose consumers may
+  // poll while their producers write (never to flushRun's LL call: a recording never flushes).
   bool llRecord = false;
   void enableLLRecord() {
-    enableLLRun();
+    enableLLRun(true);
     llRecord = llRun;
   }
   // The connections of this Primitives as the LL steps calls take them, at the run's first step.
@@ -679,7 +683,8 @@ struct Prims {
       run.push_back(s);
       for (int i = 0; i < nr; i++) recv[i]->recvStep += 1;
       for (int i = 0; i < ns; i++) {  // the run's kernel cleans the slot on such a step (flushRun passes the rule)
-        if (llCleans(c->llRule, send[i]->sendStep)) c->cleanedSteps.fetch_add(1, std::memory_order_relaxed);
+        if (proto == nexrRingProtoLL && llCleans(c->llRule, send[i]->sendStep))
+          c->cleanedSteps.fetch_add(1, std::memory_order_relaxed);
         send[i]->sendStep += 1;
       }
       return llRecord || run.size() < kLLRunFlush || flushRun();

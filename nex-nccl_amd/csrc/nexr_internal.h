@@ -136,6 +136,13 @@ struct LL128Params {
 };
 hipError_t launch_ll128(int dt, const LL128Params& a, int op, int grid, hipStream_t s);
 
+// LL128 step lists of nMembers Primitives in one launch (nexrReduceCopyLL128StepsGroup; nexr_ll.hip). The
+// table entry is the LL group's LLStepsParams (flagMask, cleanLast and cleanStep unused: 64-bit flags, no
+// cleanup), so nexrLLGroupWorkspaceBytes sizes both calls' workspaces. Tile t (kLL128TileUnits wire units)
+// of a step belongs to workgroup t % G, G from slotBytes alone, at most kLLStepsMaxGrid.
+hipError_t launch_ll128_group(int dt, int op, const LLStepsParams* table, int nMembers, int G, hipStream_t s);
+hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -900,4 +900,293 @@ hipError_t launch_ll128(int dt, const LL128Params& a, int op, int grid, hipStrea
   return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------------------------
+// LL128 step lists of several Primitives in ONE launch (nexrReduceCopyLL128StepsGroup): the group
+// kernel's walk (workgroup b runs member b / G as its workgroup b % G; credits per wave on the device
+// head words, waitSend / postRecv, prims_ll128.h:58-75) over LL128 steps whose hand-off is ordered by
+// construction. The single step above accepts a line's data units from the very load that returned its
+// flag, which is only right when the producer's kernel has completed: a line has ONE flag per 128 bytes
+// and only 16-byte granules are observed untorn here, where the reference leans on NVIDIA's 128-byte
+// warp store (prims_ll128.h:186-204, :278-285). Here instead:
+//   producer, per wave: the seven data units of each of its lines (sc0 sc1), for every send connection;
+//     then ONE s_waitcnt vmcnt(0); then the flag units (8 data bytes and the 64-bit flag, one 16-byte
+//     store). The wave that stores a line's data stores its flag too, so no workgroup barrier.
+//   consumer, per wave: polls its eight lines' flag units until all carry the step's flag, then loads
+//     every unit AGAIN: a data unit enters the arithmetic only from a load issued after a load that
+//     returned its line's flag had completed. The flag lane's own 8 data bytes share the flag's 16-byte
+//     granule (the same observed 16-byte atomicity the LL lines rest on).
+// Lane t owns unit t of a 256-unit sub-tile, so wave v owns units [64v, 64v + 64), eight whole lines: a
+// line never spans waves, and the credit is per wave exactly as in the LL runs. No flag rule and no
+// cleanup: the flags are 64-bit and the reference cleans nothing for LL128.
+// ---------------------------------------------------------------------------------------------
+struct LL128StepArgs {  // one step of a member's list, built in registers
+  const char* src;
+  char* dst;
+  const char* recv[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t recvFlag[NEXR_LL_STEPS_MAX_PEERS];
+  char* send[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t sendFlag[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t redArg;
+  uint32_t* status;
+  uint64_t timeoutTicks;
+  int nRecv, nSend, srcIsInput, postOp, firstWins;
+};
+
+// Returns false when one of this wave's lines never arrived (status set or seen set; the wave's outputs
+// of the tile stay unwritten). Every condition of the polls is wave-uniform: a tile holds whole slices
+// (128 units), so a wave's 64 units are all inside it or all outside.
+template <int D, int OP, bool IsMin>
+__device__ __forceinline__ bool ll128_step_tile(const LL128StepArgs& a, uint64_t tile, uint64_t nBytes,
+                                                uint64_t nUnits) {
+  using T = Ty<D>;
+  using V = typename T::V;
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  const uint64_t u0 = tile * kLL128TileUnits;
+  const uint32_t tileUnits = (uint32_t)(nUnits - u0 < (uint64_t)kLL128TileUnits ? nUnits - u0 : kLL128TileUnits);
+  const int q = (int)(threadIdx.x & 127);
+  const int g = q >> 5, wid = q & 31;
+  const bool flagLane = (wid & 7) == 7;
+  uint64_t off, len;  // the lane's user bytes in its slice: ix(g, wid), as ll128_tile
+  if (!flagLane) {
+    off = (uint64_t)(g * 32 - 4 * (g / 2) + wid - (g % 2) * (wid / 8)) * 16;
+    len = 16;
+  } else {
+    const int ge = g & ~1;
+    off = (uint64_t)(ge * 32 - 4 * (ge / 2) + wid) * 16 + (g & 1) * 8;
+    len = 8;
+  }
+  const int flagSrc = (int)((threadIdx.x & 63) | 7);
+  u32x4 d[kLL128U];
+  uint64_t valid[kLL128U], dOff[kLL128U];
+  bool ok[kLL128U];
+#pragma unroll
+  for (int u = 0; u < kLL128U; u++) {
+    const uint32_t m = u * kBlock + threadIdx.x;
+    ok[u] = m < tileUnits;
+    const uint64_t dBase = ((u0 + m) >> 7) * kLL128SliceData;
+    const uint64_t eltBytes = !ok[u] ? 0 : nBytes - dBase < kLL128SliceData ? nBytes - dBase : kLL128SliceData;
+    valid[u] = off < eltBytes ? (eltBytes - off < len ? eltBytes - off : len) : 0;
+    dOff[u] = dBase + off;
+    d[u] = (u32x4)0u;
+    if (a.src) {
+      if (valid[u] == 16) d[u] = *(const g_cu32x4_a1*)(a.src + dOff[u]);
+      else if (valid[u]) d[u] = ld_partial(a.src + dOff[u], valid[u]);
+      if constexpr (OP == nexrDevPreMulSum) {
+        if (a.srcIsInput) d[u] = bc<u32x4>(T::mul(bc<V>(d[u]), T::splat(a.redArg)));
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MP; i++) {
+    if (i >= a.nRecv) break;
+    const auto r = wire_rsrc(a.recv[i] + u0 * 16, (uint64_t)tileUnits * 16);
+    const uint64_t f = a.recvFlag[i];
+#pragma unroll
+    for (int u = 0; u < kLL128U; u++) {
+      if (!__builtin_amdgcn_ballot_w64(ok[u])) continue;  // none of this wave's units in the tile
+      const uint32_t o = (u * kBlock + threadIdx.x) * 16;
+      // The poll (readLL128's flag vote, prims_ll128.h:100-121): relaxed, bounded, and what it returns
+      // beside the flags is thrown away.
+      uint64_t t0 = 0;
+      for (uint32_t tries = 1;; tries++) {
+        const u32x4 p = wire_ld(r, o);  // past the end: zeros
+        const uint32_t fl = __shfl(p.z, flagSrc), fh = __shfl(p.w, flagSrc);
+        if (__all(!ok[u] || (((uint64_t)fh << 32) | fl) == f)) break;
+        if (tries % kLLAbortEvery == 0 && ll_aborted(a.status)) return false;  // checkAbort (primitives.h:142-156)
+        if (tries % kLLClockEvery == 0) {
+          const uint64_t now = __builtin_amdgcn_s_memrealtime();
+          if (!t0) t0 = now;
+          else if (now - t0 > a.timeoutTicks) {
+            if (a.status) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            return false;
+          }
+        }
+        __builtin_amdgcn_s_sleep(1);
+      }
+      // Every line's flag came back in a load that has completed (its value was branched on): the loads
+      // from here on are issued behind it. The wait keeps them there whatever the compiler would do.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const u32x4 x = wire_ld(r, o);
+      if ((i == 0 && !a.src) || a.firstWins) d[u] = x;
+      else d[u] = bc<u32x4>(reduce_step<D, OP, IsMin>(bc<V>(x), bc<V>(d[u])));
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kLL128U; u++) {
+    if constexpr (OP == nexrDevSumPostDiv) {
+      if (a.postOp) d[u] = bc<u32x4>(T::divide(bc<V>(d[u]), a.redArg));
+    }
+    if constexpr (T::kCanon) {
+      const bool arith = !a.firstWins && ((a.nRecv >= 1 && a.src) || a.nRecv >= 2 ||
+                                          (OP == nexrDevPreMulSum && a.src && a.srcIsInput));
+      if (arith) d[u] = bc<u32x4>(T::canon(bc<V>(d[u])));
+    }
+  }
+  if (a.nSend > 0) {
+    // data units, one drain for every send connection of the step, then the flag units
+#pragma unroll
+    for (int i = 0; i < MP; i++) {
+      if (i >= a.nSend) break;
+      const auto r = wire_rsrc(a.send[i] + u0 * 16, (uint64_t)tileUnits * 16);
+#pragma unroll
+      for (int u = 0; u < kLL128U; u++)
+        if (ok[u] && !flagLane) wire_st(r, (u * kBlock + threadIdx.x) * 16, d[u]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < MP; i++) {
+      if (i >= a.nSend) break;
+      const auto r = wire_rsrc(a.send[i] + u0 * 16, (uint64_t)tileUnits * 16);
+      const uint64_t f = a.sendFlag[i];
+#pragma unroll
+      for (int u = 0; u < kLL128U; u++)
+        if (ok[u] && flagLane)
+          wire_st(r, (u * kBlock + threadIdx.x) * 16, (u32x4){d[u].x, d[u].y, (uint32_t)f, (uint32_t)(f >> 32)});
+    }
+  }
+  if (a.dst) {
+#pragma unroll
+    for (int u = 0; u < kLL128U; u++) {
+      if (!ok[u] || !valid[u]) continue;
+      if (valid[u] == 16) *(g_u32x4_a1*)(a.dst + dOff[u]) = d[u];
+      else st_partial(a.dst + dOff[u], valid[u], d[u]);
+    }
+  }
+  return true;
+}
+
+template <int D, int OP>
+__global__ __launch_bounds__(kBlock) void reduce_copy_ll128_group_kernel(const LLStepsParams* table, int nMembers,
+                                                                         int G) {
+  constexpr uint64_t esz = 16 / Ty<D>::EPP;
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  const uint32_t m = __builtin_amdgcn_readfirstlane(blockIdx.x / (uint32_t)G);
+  const uint32_t w = blockIdx.x - m * (uint32_t)G;
+  if (m >= (uint32_t)nMembers) return;
+  c_LLStepsParams& P = ((c_LLStepsParams*)table)[m];
+  const bool lead = (threadIdx.x & 63) == 0;
+  const int nSlots = P.nSlots, nRecv = P.nRecv, nSend = P.nSend, nSteps = P.nSteps;
+  const uint64_t slotBytes = P.slotBytes, timeoutTicks = P.timeoutTicks;
+  uint32_t* const status = P.status;
+  uint64_t rs[MP], ss[MP], headCache[MP];
+  uint32_t rSlot[MP], sSlot[MP];
+#pragma unroll
+  for (int i = 0; i < MP; i++) {
+    rs[i] = P.recvStep[i], ss[i] = P.sendStep[i], headCache[i] = 0;
+    rSlot[i] = (uint32_t)(rs[i] % (uint64_t)nSlots), sSlot[i] = (uint32_t)(ss[i] % (uint64_t)nSlots);
+  }
+  // Every earlier launch of this stream has completed: whatever ran them, the slots before recvStep are read.
+  if (lead)
+    for (int i = 0; i < nRecv; i++)
+      __hip_atomic_store(head_word(P.recvHead[i], w), rs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  LL128StepArgs a;
+  a.redArg = P.redArg;
+  a.status = status;
+  a.timeoutTicks = timeoutTicks;
+  a.firstWins = P.firstWins;
+  for (int k = 0; k < nSteps; k++) {
+    c_LLStep& st = P.step[k];  // scalar loads from the table
+    const uint64_t nBytes = (uint64_t)st.nElts * esz;
+    const uint64_t nUnits = (nBytes + kLL128SliceData - 1) / kLL128SliceData * 128;
+    const uint64_t nTiles = (nUnits + kLL128TileUnits - 1) / kLL128TileUnits;
+    const bool stRecv = st.recv, stSend = st.send;
+    if (w < nTiles) {
+      if (stSend) {  // waitSend: the receiver's wave has read the step nSlots back
+#pragma unroll
+        for (int j = 0; j < MP; j++)
+          if (j < nSend && ss[j] + 1 > (uint64_t)nSlots &&
+              !wait_head(head_word(const_cast<uint64_t*>(P.sendHead[j]), w), ss[j] + 1 - nSlots, headCache[j],
+                         timeoutTicks, status))
+            return;  // no credit: status set, this wave stops
+      }
+      const int srcBuf = st.srcBuf, dstBuf = st.dstBuf;
+      a.src = srcBuf == 0 ? P.input + st.srcIx * esz : srcBuf == 1 ? P.output + st.srcIx * esz : nullptr;
+      a.dst = dstBuf == 0 ? const_cast<char*>(P.input) + st.dstIx * esz
+              : dstBuf == 1 ? P.output + st.dstIx * esz : nullptr;
+      a.nRecv = stRecv ? nRecv : 0;
+      a.nSend = stSend ? nSend : 0;
+#pragma unroll
+      for (int i = 0; i < MP; i++) {
+        a.recv[i] = P.recvFifo[i] + (uint64_t)rSlot[i] * slotBytes;
+        a.recvFlag[i] = rs[i] + 1;  // the 64-bit flag: step + 1
+        a.send[i] = P.sendFifo[i] + (uint64_t)sSlot[i] * slotBytes;
+        a.sendFlag[i] = ss[i] + 1;
+      }
+      a.srcIsInput = srcBuf == 0 && !a.firstWins;
+      a.postOp = st.postOp && !a.firstWins;
+      for (uint64_t t = w; t < nTiles; t += G) {
+        bool arrived;
+        if constexpr (OP == nexrDevMinMax) {
+          if ((a.redArg & 1) == 0) arrived = ll128_step_tile<D, OP, true>(a, t, nBytes, nUnits);
+          else arrived = ll128_step_tile<D, OP, false>(a, t, nBytes, nUnits);
+        } else {
+          arrived = ll128_step_tile<D, OP, false>(a, t, nBytes, nUnits);
+        }
+        // a line never came: status set, this wave stops (its lines only; the other waves' are theirs)
+        if (!arrived) return;
+      }
+    }
+    if (stRecv) {  // postRecv, relaxed as in the LL runs: what the wave read is in its outputs
+      if (lead)
+        for (int i = 0; i < nRecv; i++)
+          __hip_atomic_store(head_word(P.recvHead[i], w), rs[i] + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+      for (int i = 0; i < MP; i++) {
+        rs[i]++;
+        rSlot[i] = rSlot[i] + 1 == (uint32_t)nSlots ? 0 : rSlot[i] + 1;
+      }
+    }
+    if (stSend) {
+#pragma unroll
+      for (int j = 0; j < MP; j++) {
+        ss[j]++;
+        sSlot[j] = sSlot[j] + 1 == (uint32_t)nSlots ? 0 : sSlot[j] + 1;
+      }
+    }
+  }
+}
+
+template <int D>
+static const void* ll128_group_fn_dt(int op) {
+  switch (op) {
+    case nexrDevSum: return (const void*)&reduce_copy_ll128_group_kernel<D, nexrDevSum>;
+    case nexrDevProd: return (const void*)&reduce_copy_ll128_group_kernel<D, nexrDevProd>;
+    case nexrDevMinMax: return (const void*)&reduce_copy_ll128_group_kernel<D, nexrDevMinMax>;
+    case nexrDevPreMulSum: return (const void*)&reduce_copy_ll128_group_kernel<D, nexrDevPreMulSum>;
+    case nexrDevSumPostDiv:
+      if constexpr (Ty<D>::kIsInt) return (const void*)&reduce_copy_ll128_group_kernel<D, nexrDevSumPostDiv>;
+      break;
+  }
+  return nullptr;
+}
+
+static const void* ll128_group_fn(int dt, int op) {
+  switch (dt) {
+    case nexrInt8: return ll128_group_fn_dt<nexrInt8>(op);
+    case nexrUint8: return ll128_group_fn_dt<nexrUint8>(op);
+    case nexrInt32: return ll128_group_fn_dt<nexrInt32>(op);
+    case nexrUint32: return ll128_group_fn_dt<nexrUint32>(op);
+    case nexrInt64: return ll128_group_fn_dt<nexrInt64>(op);
+    case nexrUint64: return ll128_group_fn_dt<nexrUint64>(op);
+    case nexrFloat16: return ll128_group_fn_dt<nexrFloat16>(op);
+    case nexrFloat32: return ll128_group_fn_dt<nexrFloat32>(op);
+    case nexrFloat64: return ll128_group_fn_dt<nexrFloat64>(op);
+    case nexrBfloat16: return ll128_group_fn_dt<nexrBfloat16>(op);
+  }
+  return nullptr;
+}
+
+hipError_t launch_ll128_group(int dt, int op, const LLStepsParams* table, int nMembers, int G, hipStream_t s) {
+  const void* fn = ll128_group_fn(dt, op);
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {&table, &nMembers, &G};
+  return hipLaunchKernel(fn, dim3((unsigned)(nMembers * G)), dim3(kBlock), args, 0, s);
+}
+
+hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
+  const void* fn = ll128_group_fn(dt, op);
+  if (!fn) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fn, kBlock, 0);
+}
+
 }  // namespace nexr

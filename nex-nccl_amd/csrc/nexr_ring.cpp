@@ -589,7 +589,8 @@ bool validConfigBuff(const nexrRingComm* c) {
 // a queued LL128 ring failed the oracle this way), while LL's flag per 8-byte granule has no such
 // window; ordering queued LL128 consumers behind producer events instead ran slower than host
 // sequencing (0.26-0.28 against 0.22 ms for C1, profiles/r06g_ll_queue_probe.json), so LL128 stays
-// host-sequenced. The kernels' progress does not depend on the hardware queues (Prims comment), but
+// host-sequenced in this mode and in the runs (its ordered hand-off lives in the group launches only,
+// llGroupAllowed below). The kernels' progress does not depend on the hardware queues (Prims comment), but
 // as a margin the rank streams of the device (all channels, the tree's second streams included) must
 // fit in its hardware queues beside the default stream's: at most GPU_MAX_HW_QUEUES - 1 of them (HIP's
 // default is 4 per device). Every rank on one GPU and FIFOs in device memory, as enableLLAsync
@@ -649,13 +650,17 @@ int llTicketEvery() {
 }
 
 // Group launches (nexrRingCommSetLLGroup): every (channel, rank) of the collective is a member of one
-// nexrReduceCopyLLStepsGroup call on one stream. Where mode 2 could run but for its stream count: LL,
-// device memory, every rank on the one GPU (the completion-word wait), the library's own LL kernels and
-// device head words on every connection; and at most NEXR_LL_GROUP_MAX_MEMBERS members.
+// nexrReduceCopyLLStepsGroup call on one stream (LL128: nexrReduceCopyLL128StepsGroup, whose ordered
+// hand-off is what lets LL128 consumers poll inside a launch at all). Where mode 2 could run but for its
+// stream count: LL or LL128, device memory, every rank on the one GPU (the completion-word wait), the
+// library's own kernels (not a caller's llFn / ll128Fn) and device head words on every connection; and at
+// most NEXR_LL_GROUP_MAX_MEMBERS members.
 bool llGroupAllowed(const nexrRingComm* c, size_t nMembers) {
-  if (!c->llGroup || c->proto != nexrRingProtoLL || c->cfg.memMode != nexrRingDeviceMemory || !c->stepWaitWord ||
-      c->cfg.llFn != defaultLLFn || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || c->streams.empty() || !c->streams[0] ||
-      !c->status[0] || !c->done[0])
+  const bool ownFn = c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
+                     : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
+                                                      : false;
+  if (!c->llGroup || !ownFn || c->cfg.memMode != nexrRingDeviceMemory || !c->stepWaitWord ||
+      nMembers > NEXR_LL_GROUP_MAX_MEMBERS || c->streams.empty() || !c->streams[0] || !c->status[0] || !c->done[0])
     return false;
   for (int d : c->devices)
     if (d != c->devices[0]) return false;
@@ -709,9 +714,13 @@ nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int da
       c->groupWsDevice = c->devices[0];
     }
     __atomic_store_n(status, 0u, __ATOMIC_RELEASE);
-    r = nexrReduceCopyLLStepsGroup(n, cs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
-                                   &c->llRule, status, (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
-                                   (nexrStream_t)stream);
+    r = c->proto == nexrRingProtoLL128
+            ? nexrReduceCopyLL128StepsGroup(n, cs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
+                                            status, (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
+                                            (nexrStream_t)stream)
+            : nexrReduceCopyLLStepsGroup(n, cs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
+                                         &c->llRule, status, (uint32_t)timeoutMs * 1000u, c->groupWs,
+                                         c->groupWsBytes, (nexrStream_t)stream);
     // every other argument is valid by construction: nexrInvalidArgument is the workspace
     if (r != nexrInvalidArgument || c->groupWsBytes >= perLaunch * longest) break;
     want = std::min(c->groupWsBytes * 2, perLaunch * longest);
@@ -1177,7 +1186,9 @@ NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t c, int* queued) {
 
 NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t c, int on) {
   if (!c) return nexrInvalidArgument;
-  if (c->peer || c->proto != nexrRingProtoLL || c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
+  if (c->peer || (c->proto != nexrRingProtoLL && c->proto != nexrRingProtoLL128) ||
+      c->cfg.memMode != nexrRingDeviceMemory)
+    return nexrInvalidUsage;
   c->llGroup = on != 0;
   return nexrSuccess;
 }

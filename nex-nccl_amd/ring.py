@@ -238,8 +238,10 @@ class RingComm:
 
     def set_ll_group(self, on: bool) -> None:
         """Opt in to (or out of) group launches (nexrRingCommSetLLGroup): the LL steps of every rank and
-        channel of a ring collective in the same launches on one stream, queued() == 3. Between
-        collectives; InvalidUsage unless the communicator is thread-rank, LL and device-memory."""
+        channel of a ring collective in the same launches on one stream, queued() == 3. LL128
+        communicators too (nexrReduceCopyLL128StepsGroup, the ordered hand-off); without the option they
+        stay host-sequenced. Between collectives; InvalidUsage unless the communicator is thread-rank, LL
+        or LL128, and device-memory."""
         _check(self._L.nexrRingCommSetLLGroup(self._h, 1 if on else 0), "nexrRingCommSetLLGroup")
 
     def set_ll_flag_rule(self, flag_max: int, clean_mask: int) -> None:
