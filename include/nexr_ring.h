@@ -129,7 +129,9 @@ NEXR_API nexrResult_t nexrTreeTopology(nexrRingComm_t comm, int rank, int* up, i
  * synchronisation. NEXR_STEP_WAIT=word / sync, read once per process, forces either. */
 NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t comm, int* word);
 
-/* How the last thread-rank ring collective on this communicator ran its LL steps. *queued = 2: runs
+/* How the last thread-rank ring collective on this communicator ran its LL steps (and, while the group
+ * option below is on, the last nexrTreeAllReduce: 3 as group launches, 0 when it fell back to host
+ * sequencing; with the option off a tree call leaves the report untouched). *queued = 2: runs
  * on the device (nexrReduceCopyLLSteps), up to 96 steps per launch, the peers' data found by the
  * kernel's flag poll (prims_ll.h:38-93) and the slot credits by its poll of the receivers' head words in
  * device memory (waitSend / postRecv, :55-83), no host wait until the collective's end (the default
@@ -153,7 +155,17 @@ NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
  * head words from the step counters both modes keep. A collective falls back to the mode it would have
  * run without the option when its ranks span several GPUs, the communicator has a caller's llFn, the
  * collective has more than NEXR_LL_GROUP_MAX_MEMBERS (channel, rank) members, or the group's grid is not
- * resident at once on the GPU. The tree all-reduce is not affected.
+ * resident at once on the GPU.
+ *
+ * nexrTreeAllReduce takes the option too. Every Primitives of the call is a member: the root with its
+ * receive and send connections to every child, and every other rank's reduce-up and broadcast-down halves,
+ * 2n - 1 members per channel (up to 3 + 3 connections each). The rank threads record, the calling thread
+ * queues the group launches, and the call reports 3. It runs host-sequenced instead, as without the option
+ * and from the step counters as they were, and reports 0, when the ranks span several GPUs, the
+ * communicator has a caller's llFn / ll128Fn or waits by hipStreamSynchronize, the call has more than
+ * NEXR_LL_GROUP_MAX_MEMBERS members over its channels, or the grid is not resident at once. Under LL a
+ * member with several send connections cleans every one of them on its cleaning steps. Ring and tree calls
+ * may be mixed and the option toggled between them: they use disjoint connections.
  *
  * LL128 communicators take the option too: their step lists go to nexrReduceCopyLL128StepsGroup, whose
  * hand-off is ordered by construction (include/nexr.h), the only way LL128 steps of two ranks run at the

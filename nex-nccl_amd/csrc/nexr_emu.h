@@ -187,7 +187,8 @@ struct nexrRingComm {
   bool stepWaitWord = true;
   // How the last thread-rank ring collective ran its LL steps (diagnostics, nexrRingCommGetQueued):
   // 0 host-sequenced, 1 queued launches (Prims::enableLLAsync), 2 runs with device credits (enableLLRun).
-  // 3: group launches on one stream (nexrRingCommSetLLGroup; LL and LL128).
+  // 3: group launches on one stream (nexrRingCommSetLLGroup; LL and LL128). The tree all-reduce reports
+  // here only while that option is on (3, or 0 when it fell back).
   int lastLLMode = 0;
   // nexrRingCommSetLLGroup: the option, and the device workspace of the group launches' tables (made by
   // the first group collective on the ranks' GPU, grown when a collective needs more launches).
@@ -474,7 +475,8 @@ struct Prims {
     __atomic_store_n(status, 0u, __ATOMIC_RELEASE);
   }
   // Group launches (nexrRingCommSetLLGroup): the run mode's recording with no flush. The rank thread only
-  // collects its whole step list; the calling thread launches every member's at once (ringCollective).
+  // collects its whole step list; the calling thread launches every member's at once (ringCollective,
+  // treeAllReduce).
   // LL128 too: its lists go to nexrReduceCopyLL128StepsGroup, the only LL128 kernel whose consumers may
   // poll while their producers write (never to flushRun's LL call: a recording never flushes).
   bool llRecord = false;

@@ -649,7 +649,8 @@ int llTicketEvery() {
   return every;
 }
 
-// Group launches (nexrRingCommSetLLGroup): every (channel, rank) of the collective is a member of one
+// Group launches (nexrRingCommSetLLGroup): every Primitives of the collective, a ring's (channel, rank) or
+// a tree's root and reduce-up / broadcast-down halves (2n - 1 per channel), is a member of one
 // nexrReduceCopyLLStepsGroup call on one stream (LL128: nexrReduceCopyLL128StepsGroup, whose ordered
 // hand-off is what lets LL128 consumers poll inside a launch at all). Where mode 2 could run but for its
 // stream count: LL or LL128, device memory, every rank on the one GPU (the completion-word wait), the
@@ -667,13 +668,25 @@ bool llGroupAllowed(const nexrRingComm* c, size_t nMembers) {
   return true;
 }
 
-// One member's record: its connections at its first step, its whole step list, and the Conn objects
-// whose host counters the calling thread publishes once the launches are complete.
+// One member's record: its connections at its first step, its whole step list, and the Conn objects (up
+// to kMaxArity each way: the tree's fans) whose host counters the calling thread publishes once the
+// launches are complete.
 struct GroupMember {
   nexrLLConnSet cs;
   std::vector<nexrLLStep> steps;
-  Conn* recv = nullptr;
-  Conn* send = nullptr;
+  Conn* recv[kMaxArity] = {};
+  int nRecv = 0;
+  Conn* send[kMaxArity] = {};
+  int nSend = 0;
+  // Takes what a recording Primitives collected (Prims::enableLLRecord), every connection of it.
+  void take(Prims& p) {
+    if (!p.run.empty()) cs = p.connSet();
+    steps.swap(p.run);
+    nRecv = p.nRecv;
+    nSend = p.nSend;
+    for (int i = 0; i < p.nRecv; i++) recv[i] = p.recv[i];
+    for (int i = 0; i < p.nSend; i++) send[i] = p.send[i];
+  }
 };
 
 // The recorded members as group launches on channel 0's first stream, one wait, then the host counters
@@ -744,8 +757,8 @@ nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int da
     ok = false;
   }
   for (GroupMember& m : members) {
-    if (m.recv) m.recv->st->head.store(m.recv->recvStep, std::memory_order_release);
-    if (m.send) m.send->st->tail.store(m.send->sendStep, std::memory_order_release);
+    for (int i = 0; i < m.nRecv; i++) m.recv[i]->st->head.store(m.recv[i]->recvStep, std::memory_order_release);
+    for (int i = 0; i < m.nSend; i++) m.send[i]->st->tail.store(m.send[i]->sendStep, std::memory_order_release);
   }
   if (ok && __atomic_load_n(status, __ATOMIC_ACQUIRE) != 0) r = nexrInternalError;  // a step timed out
   return r;
@@ -819,10 +832,7 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
           case kBroadcast: runRingBroadcast(p, n, root, part); break;
         }
         if (member) {  // recorded, not run: the calling thread launches every member's list together
-          if (!p.run.empty()) member->cs = p.connSet();
-          member->steps.swap(p.run);
-          member->recv = p.recv[0];
-          member->send = p.send[0];
+          member->take(p);
           return;
         }
         p.finishLL();  // queued LL steps complete before the collective returns (even after a failure)
@@ -957,6 +967,128 @@ nexrResult_t peerFinish(nexrRingComm* c, Shared& sh) {
     return (nexrResult_t)sh.firstError.load();
   }
   return nexrSuccess;
+}
+
+// The tree all-reduce on thread ranks. Group launches (nexrRingCommSetLLGroup) as in ringCollective: every
+// Primitives of the call is a member, the root once and every other rank's two halves, 2n - 1 per channel.
+nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                           int datatype, int op, bool tryGroup = true) {
+  if (!c || c->peer) return nexrInvalidArgument;
+  size_t esz;
+  nexrDevRedOpFull red;
+  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  if (r != nexrSuccess) return r;
+  const int n = c->cfg.nRanks;
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (count == 0) return nexrSuccess;
+  for (int i = 0; i < n; i++)
+    if (!sendbuffs[i] || !recvbuffs[i]) return nexrInvalidArgument;
+  if (n == 1) return oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, esz);
+  std::vector<ChannelPart> parts = channelParts(c, (int64_t)count, esz, /*ncclFuncAllReduce*/ 2);
+  for (ChannelPart& part : parts) {
+    nexrRingComm* ck = channelComm(c, part.channel);
+    r = ensureTree(ck);
+    if (r != nexrSuccess) {
+      c->broken = true;
+      return r;
+    }
+    // calcCollChunking for the part: nBytes = its count x esz (enqueue.cc:664-679)
+    part.chunkCount = chunkElems(ck, kGeomPipe, esz, true, (size_t)part.count * esz);
+  }
+  const size_t perChannel = 2 * (size_t)n - 1;
+  const bool group = tryGroup && llGroupAllowed(c, parts.size() * perChannel);
+  if (c->llGroup) c->lastLLMode = group ? 3 : 0;  // option off: the report stays the last ring collective's
+  // Group launches: the Primitives only record (the unchanged runTree). Should the group call find its grid
+  // not resident, the call runs again host-sequenced from the counters as they were.
+  std::vector<GroupMember> members(group ? parts.size() * perChannel : 0);
+  std::vector<std::pair<uint64_t, uint64_t>> steps0;  // (sendStep, recvStep) of every treeUp, then treeDown
+  std::vector<uint64_t> cleaned0;
+  if (group)
+    for (const ChannelPart& part : parts) {
+      nexrRingComm* ck = channelComm(c, part.channel);
+      for (const auto* v : {&ck->treeUp, &ck->treeDown})
+        for (const Conn* q : *v)
+          if (q) steps0.emplace_back(q->sendStep, q->recvStep);
+      cleaned0.push_back(ck->cleanedSteps.load(std::memory_order_relaxed));
+    }
+  Shared sh;
+  std::vector<std::function<void()>> jobs;
+  // One Primitives: its connections, then the role's steps, run or (member != nullptr) recorded.
+  auto role = [&](Prims& p, TreeRole which, bool leaf, const ChannelPart& part, GroupMember* member) {
+    p.attach();
+    if (member) {
+      p.enableLLRecord();
+      if (!p.llRecord) {
+        sh.fail(nexrInternalError);
+        return;
+      }
+    }
+    runTree(p, which, leaf, part);
+    if (member) member->take(p);
+  };
+  for (const ChannelPart& part : parts) {
+    nexrRingComm* ck = channelComm(c, part.channel);
+    for (int rank = 0; rank < n; rank++) {
+      const TreeLinks& t = ck->tree[rank];
+      const bool leaf = t.down[0] == -1;
+      auto make = [&, rank, ck](hipStream_t s, uint32_t* st) {
+        return makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, red, kGeomPipe, s, st);
+      };
+      GroupMember* member = group ? &members[jobs.size()] : nullptr;  // one job, one member, in this order
+      if (t.up == -1) {  // root: recv from and send to every child
+        jobs.emplace_back([&, rank, make, ck, part, member] {
+          if (ck->streams[rank]) (void)hipSetDevice(ck->devices[rank]);
+          Prims p = make(ck->streams[rank], ck->status[rank]);
+          const TreeLinks& tl = ck->tree[rank];
+          for (int i = 0; i < tl.nDown(); i++) {
+            p.recv[p.nRecv++] = ck->treeUp[tl.down[i]];
+            p.send[p.nSend++] = ck->treeDown[tl.down[i]];
+          }
+          role(p, kTreeRoot, false, part, member);
+        });
+        continue;
+      }
+      jobs.emplace_back([&, rank, leaf, make, ck, part, member] {  // reduce up: recv from children, send to the parent
+        if (ck->streams[rank]) (void)hipSetDevice(ck->devices[rank]);
+        Prims p = make(ck->streams[rank], ck->status[rank]);
+        const TreeLinks& tl = ck->tree[rank];
+        for (int i = 0; i < tl.nDown(); i++) p.recv[p.nRecv++] = ck->treeUp[tl.down[i]];
+        p.send[p.nSend++] = ck->treeUp[rank];
+        role(p, kTreeReduceUp, leaf, part, member);
+      });
+      member = group ? &members[jobs.size()] : nullptr;
+      jobs.emplace_back([&, rank, leaf, make, ck, part, member] {  // broadcast down: recv from the parent, send to children
+        if (ck->streams2[rank]) (void)hipSetDevice(ck->devices[rank]);
+        Prims p = make(ck->streams2[rank], ck->status2[rank]);
+        const TreeLinks& tl = ck->tree[rank];
+        p.recv[p.nRecv++] = ck->treeDown[rank];
+        for (int i = 0; i < tl.nDown(); i++) p.send[p.nSend++] = ck->treeDown[tl.down[i]];
+        role(p, kTreeBcastDown, leaf, part, member);
+      });
+    }
+  }
+  r = runThreads(c, sh, jobs);
+  if (!group || r != nexrSuccess) return r;
+  members.erase(std::remove_if(members.begin(), members.end(), [](const GroupMember& m) { return m.steps.empty(); }),
+                members.end());
+  if (members.empty()) return nexrSuccess;
+  r = runGroup(c, members, datatype, red);
+  if (r == nexrInvalidUsage) {  // the grid does not fit the GPU at once: host-sequenced, from the same counters
+    size_t ix = 0, ch = 0;
+    for (const ChannelPart& part : parts) {
+      nexrRingComm* ck = channelComm(c, part.channel);
+      for (auto* v : {&ck->treeUp, &ck->treeDown})
+        for (Conn* q : *v)
+          if (q) {
+            q->sendStep = steps0[ix].first;
+            q->recvStep = steps0[ix++].second;
+          }
+      ck->cleanedSteps.store(cleaned0[ch++], std::memory_order_relaxed);
+    }
+    return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, false);
+  }
+  if (r != nexrSuccess) c->broken = true;  // step counters are mid-protocol
+  return r;
 }
 
 // A communicator touches HIP when its FIFOs live in device memory or when any of its steps runs the
@@ -1103,73 +1235,7 @@ NEXR_API nexrResult_t nexrRingBroadcast(nexrRingComm_t c, const void* const* sen
 NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op) {
   DeviceGuard dg(c && c->needHip);
-  if (!c || c->peer) return nexrInvalidArgument;
-  size_t esz;
-  nexrDevRedOpFull red;
-  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
-  if (r != nexrSuccess) return r;
-  const int n = c->cfg.nRanks;
-  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
-  if (count == 0) return nexrSuccess;
-  for (int i = 0; i < n; i++)
-    if (!sendbuffs[i] || !recvbuffs[i]) return nexrInvalidArgument;
-  if (n == 1) return oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, esz);
-  std::vector<ChannelPart> parts = channelParts(c, (int64_t)count, esz, /*ncclFuncAllReduce*/ 2);
-  for (ChannelPart& part : parts) {
-    nexrRingComm* ck = channelComm(c, part.channel);
-    r = ensureTree(ck);
-    if (r != nexrSuccess) {
-      c->broken = true;
-      return r;
-    }
-    // calcCollChunking for the part: nBytes = its count x esz (enqueue.cc:664-679)
-    part.chunkCount = chunkElems(ck, kGeomPipe, esz, true, (size_t)part.count * esz);
-  }
-  Shared sh;
-  std::vector<std::function<void()>> jobs;
-  for (const ChannelPart& part : parts) {
-    nexrRingComm* ck = channelComm(c, part.channel);
-    for (int rank = 0; rank < n; rank++) {
-      const TreeLinks& t = ck->tree[rank];
-      const bool leaf = t.down[0] == -1;
-      auto make = [&, rank, ck](hipStream_t s, uint32_t* st) {
-        return makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, red, kGeomPipe, s, st);
-      };
-      if (t.up == -1) {  // root: recv from and send to every child
-        jobs.emplace_back([&, rank, make, ck, part] {
-          if (ck->streams[rank]) (void)hipSetDevice(ck->devices[rank]);
-          Prims p = make(ck->streams[rank], ck->status[rank]);
-          const TreeLinks& tl = ck->tree[rank];
-          for (int i = 0; i < tl.nDown(); i++) {
-            p.recv[p.nRecv++] = ck->treeUp[tl.down[i]];
-            p.send[p.nSend++] = ck->treeDown[tl.down[i]];
-          }
-          p.attach();
-          runTree(p, kTreeRoot, false, part);
-        });
-        continue;
-      }
-      jobs.emplace_back([&, rank, leaf, make, ck, part] {  // reduce up: recv from children, send to the parent
-        if (ck->streams[rank]) (void)hipSetDevice(ck->devices[rank]);
-        Prims p = make(ck->streams[rank], ck->status[rank]);
-        const TreeLinks& tl = ck->tree[rank];
-        for (int i = 0; i < tl.nDown(); i++) p.recv[p.nRecv++] = ck->treeUp[tl.down[i]];
-        p.send[p.nSend++] = ck->treeUp[rank];
-        p.attach();
-        runTree(p, kTreeReduceUp, leaf, part);
-      });
-      jobs.emplace_back([&, rank, leaf, make, ck, part] {  // broadcast down: recv from the parent, send to children
-        if (ck->streams2[rank]) (void)hipSetDevice(ck->devices[rank]);
-        Prims p = make(ck->streams2[rank], ck->status2[rank]);
-        const TreeLinks& tl = ck->tree[rank];
-        p.recv[p.nRecv++] = ck->treeDown[rank];
-        for (int i = 0; i < tl.nDown(); i++) p.send[p.nSend++] = ck->treeDown[tl.down[i]];
-        p.attach();
-        runTree(p, kTreeBcastDown, leaf, part);
-      });
-    }
-  }
-  return runThreads(c, sh, jobs);
+  return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
 }
 
 NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t c, int* word) {

@@ -231,7 +231,8 @@ class RingComm:
         """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 3 group launches on
         one stream (set_ll_group), 2 runs on the device with device credits, 1 queued launches,
         0 host-sequenced (LL steps need every rank on one GPU and device memory for 1, 2 or 3; 1 and 2
-        also a hardware queue per rank stream)."""
+        also a hardware queue per rank stream). While set_ll_group is on, a tree_all_reduce reports here
+        too: 3 when it ran as group launches, 0 when it fell back."""
         w = ctypes.c_int()
         _check(self._L.nexrRingCommGetQueued(self._h, ctypes.byref(w)), "nexrRingCommGetQueued")
         return int(w.value)
@@ -241,7 +242,13 @@ class RingComm:
         channel of a ring collective in the same launches on one stream, queued() == 3. LL128
         communicators too (nexrReduceCopyLL128StepsGroup, the ordered hand-off); without the option they
         stay host-sequenced. Between collectives; InvalidUsage unless the communicator is thread-rank, LL
-        or LL128, and device-memory."""
+        or LL128, and device-memory.
+
+        tree_all_reduce takes the option too: the root and every other rank's reduce-up and broadcast-down
+        halves are the members, 2n - 1 per channel, and queued() is 3 after it. It falls back to
+        host-sequenced steps (queued() == 0) when the ranks span GPUs, with a caller's ll_fn / ll128_fn,
+        above 32 members over all channels, or when the grid is not resident at once. With the option off
+        a tree call leaves queued() as it was."""
         _check(self._L.nexrRingCommSetLLGroup(self._h, 1 if on else 0), "nexrRingCommSetLLGroup")
 
     def set_ll_flag_rule(self, flag_max: int, clean_mask: int) -> None:
