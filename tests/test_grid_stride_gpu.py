@@ -1,7 +1,9 @@
 """The kernel's grid-stride loop: a one-shot grid covers every call up to 2^24 workgroups (256 GiB
 per buffer), so the stride path only runs beyond that. Forcing a small grid with NEXR_GRID (read
 once per process, hence a child process per setting) makes every workgroup stride over many trips;
-results must be identical to the oracle under every cache policy."""
+results must be identical to the oracle under every cache policy. The five cases here are aligned and
+mostly in the default shape; tests/test_policy_matrix_gpu.py's strided item runs two workgroups over
+misaligned trips (a head and a tail) of every workgroup shape under both nt policies."""
 import os
 import subprocess
 import sys
