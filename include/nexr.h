@@ -35,8 +35,9 @@ extern "C" {
 #define NEXR_API __attribute__((visibility("default")))
 
 /* 0.3.0 also covers the LL flag rule (nexrLLFlagRule, nexrReduceCopyLLStepsRule, nexrLLCleanSlot) and the
- * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup, and nexrReduceCopyLL128StepsGroup
- * for LL128 step lists): additions only, no existing entry point or struct layout changed, so the version
+ * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup, nexrReduceCopyLL128StepsGroup
+ * for LL128 step lists, and nexrSimpleGroupWorkspaceBytes / nexrReduceCopySimpleStepsGroup with
+ * nexrSimpleConnSet for SIMPLE ones): additions only, no existing entry point or struct layout changed, so the version
  * stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
@@ -513,6 +514,72 @@ NEXR_API nexrResult_t nexrReduceCopyLL128StepsGroup(int nMembers, const nexrLLCo
                                                     int devRedOp, uint64_t redOpArg, uint32_t* status,
                                                     uint32_t timeoutUs, void* workspace, size_t workspaceBytes,
                                                     nexrStream_t stream);
+
+/*
+ * nexrReduceCopySimpleStepsGroup — SIMPLE step lists of nMembers Primitives (1..NEXR_LL_GROUP_MAX_MEMBERS)
+ * in the same launches on ONE stream: the group call for the protocol whose data carries no flags
+ * (reference src/device/prims_simple.h: genericOp :190-330, waitPeer / postPeer :111-188). nexrLLStep is
+ * used unchanged; one record is ONE SLICE of genericOp:
+ *   - srcs = [user src if srcBuf != -1, then the slot of every receive connection when recv], dsts = [user
+ *     dst if dstBuf != -1, then the slot of every send connection when send]; acc = srcs[0], the USER source
+ *     first (nexrReduceCopy's order, not the LL calls' peer-first one); the PreMulSum pre-op applies to
+ *     source 0 only when srcBuf == 0 (the user input), postOp as in the record. Element arithmetic, the
+ *     reduction semantics (nccl / fork / shipped) and the datatypes and ops accepted are nexrReduceCopy's
+ *     (fp8 is refused, as in the LL calls);
+ *   - a connection's slot is fifo + (step % nSlots) * slotBytes; a slice may fill stepPerSlice consecutive
+ *     slots (nElts * size <= slotBytes * stepPerSlice, else nexrInvalidArgument), and a recv or send record
+ *     advances the counters by stepPerSlice. A record with nElts == 0 only advances and posts;
+ *   - stepPerSlice >= 1, nSlots % stepPerSlice == 0, and every recvStep / sendStep is a multiple of
+ *     stepPerSlice (a slice never wraps the FIFO), else nexrInvalidArgument; slotBytes (a 16-B multiple),
+ *     nSlots and stepPerSlice are equal across members; FIFOs are 16-B aligned, user buffers at any
+ *     alignment; workgroupsPerMember is 0..NEXR_SIMPLE_GROUP_MAX_GRID.
+ *
+ * Credits are per WORKGROUP, in device memory: a connection has a tail block and a head block of
+ * NEXR_SIMPLE_CREDIT_BYTES each (8-byte aligned, zeroed before the first use), one 8-byte word per workgroup
+ * at a 16-B stride. Tile t of every slice, bytes [t * 4096, t * 4096 + 4096) from the slice's start, belongs
+ * to workgroup t % G on both ends of a connection; G is workgroupsPerMember, or for 0
+ * min(256, ceil(slotBytes * stepPerSlice / 4096)). Word w of the tail block says how far the sender's
+ * workgroup w has published, word w of the head block how far the receiver's workgroup w has released: a
+ * sender's workgroup writes a slot only when head[w] + nSlots >= sendStep + stepPerSlice, a receiver's reads
+ * only when tail[w] >= recvStep + stepPerSlice. A workgroup that owns no tile of a slice neither waits nor
+ * is waited for on it; it still advances and posts. At the start of a launch a member stores recvStep into
+ * its head words and sendStep into its tail words, so a connection may come from host-sequenced steps that
+ * have completed. The tail is published behind a release fence and read in front of an acquire fence, both
+ * at system scope. A tail or a head that never comes within timeoutUs (0: one second) sets
+ * *status = 1 and ends its workgroup's run; a non-zero *status ends the other polls early; the launch never
+ * hangs.
+ *
+ * The host side is nexrReduceCopyLLStepsGroup's, by the same code: the launch cuts (96 records, a member's
+ * user-range conflict, applied to all members at one index), the dry run (nexrInvalidUsage when a launch
+ * cannot finish; the credit test is sendStep + stepPerSlice - nSlots <= head), the co-residency check
+ * (nMembers * G workgroups resident at once, else nexrInvalidUsage) and the workspace rules, sized by
+ * nexrSimpleGroupWorkspaceBytes for NEXR_LL_GROUP_LAUNCHES launches (too small: nexrInvalidArgument). All of
+ * these return before any device call. A group of ONE member with one-ended connections is the "run" form.
+ */
+#define NEXR_SIMPLE_CREDIT_BYTES 4096   /* per connection and direction: one 8-byte word per workgroup at a 16-B stride */
+#define NEXR_SIMPLE_GROUP_MAX_GRID 256  /* workgroups per member at most: NEXR_SIMPLE_CREDIT_BYTES / 16 */
+typedef struct {
+  const void* input;
+  void* output;
+  int nRecv, nSend;
+  const void* recvFifo[NEXR_LL_STEPS_MAX_PEERS];
+  const uint64_t* recvTail[NEXR_LL_STEPS_MAX_PEERS]; /* written by the sender */
+  uint64_t* recvHead[NEXR_LL_STEPS_MAX_PEERS];       /* written by this member */
+  uint64_t recvStep[NEXR_LL_STEPS_MAX_PEERS];
+  void* sendFifo[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t* sendTail[NEXR_LL_STEPS_MAX_PEERS];       /* written by this member */
+  const uint64_t* sendHead[NEXR_LL_STEPS_MAX_PEERS]; /* written by the receiver */
+  uint64_t sendStep[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t slotBytes;    /* stepSize: bytes per FIFO step, a 16-B multiple */
+  uint32_t nSlots;       /* NCCL_STEPS */
+  uint32_t stepPerSlice; /* StepPerSlice of the collective's ProtoSimple: every step record is one slice */
+} nexrSimpleConnSet;
+NEXR_API nexrResult_t nexrSimpleGroupWorkspaceBytes(int nMembers, size_t* bytes);
+NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns,
+                                                     const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                     int devRedOp, uint64_t redOpArg, int workgroupsPerMember,
+                                                     uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                     size_t workspaceBytes, nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

@@ -138,9 +138,10 @@ NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t comm, int* word);
  * where 1 is possible and the communicator uses the library's own LL kernels; NEXR_LL_RUN=0 falls back
  * to 1). 1: queued, each step's kernel on the rank's stream with no host wait after it, the slots a
  * step read released once a completion ticket behind it lands (one per NEXR_LL_TICKET_EVERY steps,
- * default 4). 0: host-sequenced (SIMPLE, LL128 without the group option, ranks on several GPUs, host
+ * default 4). 0: host-sequenced (SIMPLE and LL128 without their group options, ranks on several GPUs, host
  * memory, NEXR_LL_ASYNC=0, or more rank streams on a GPU than it has hardware queues beside the default
- * stream's). 3: group launches on one stream (nexrRingCommSetLLGroup, below; LL and LL128). */
+ * stream's). 3: group launches on one stream (nexrRingCommSetLLGroup, below; LL and LL128;
+ * nexrRingCommSetSimpleGroup for SIMPLE). */
 NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
 
 /* Opt-in: run the LL steps of every rank (and channel) of a ring collective in group launches on ONE
@@ -175,6 +176,29 @@ NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
  *
  * nexrInvalidUsage unless the communicator has thread ranks, the LL or LL128 protocol and device memory. */
 NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t comm, int on);
+
+/* SIMPLE step lists in group launches (nexrReduceCopySimpleStepsGroup, include/nexr.h): nexrRingCommSetLLGroup
+ * for the SIMPLE protocol, whose steps otherwise cost one launch, one completion wait and the host's
+ * head / tail stores each. With on != 0 the five ring collectives record each (channel, rank)'s slices on
+ * the rank threads (Prims::genericOp makes no waits and no launches; zero-size slices are recorded too),
+ * the calling thread queues the group launches on one stream, waits once and publishes the host head /
+ * tail, and nexrRingCommGetQueued reports 3. The first switch-on allocates and zeroes a tail block and a
+ * head block of NEXR_SIMPLE_CREDIT_BYTES per ring connection; communicators that never switch it on are
+ * unchanged. The grid starts at the call's default (a workgroup per 4 KiB tile of a slice, 256 at most per
+ * member) and is halved down to one workgroup per member while the call answers that it is not resident at
+ * once. A collective is host-sequenced as without the option, from the counters as they were, and reports
+ * 0, when its ranks span several GPUs, the communicator has a caller's fn or waits for its steps by
+ * hipStreamSynchronize, the collective has more than NEXR_LL_GROUP_MAX_MEMBERS (channel, rank) members, or
+ * the grid is not resident even at one workgroup per member. The option may be toggled between collectives,
+ * and collectives with 1-step slices (Reduce, Broadcast) and 2-step slices may alternate: every launch
+ * re-stores its head and tail words from the step counters both modes keep. nexrTreeAllReduce does not
+ * take it. Opt-in, and not always a gain: a 4 MiB fp32 all-reduce on one MI355X took 0.181-0.210 ms with
+ * the option against 0.167-0.197 ms host-sequenced at 2 ranks (SLOWER), 0.375-0.407 against 0.384-0.425 at
+ * 4 ranks, 0.831-0.850 against 1.047-1.076 at 8 ranks and 0.501-0.524 against 0.570-0.601 at 4 ranks x 2
+ * channels (profiles/r10a_simple_group_probe.json).
+ *
+ * nexrInvalidUsage unless the communicator has thread ranks, the SIMPLE protocol and device memory. */
+NEXR_API nexrResult_t nexrRingCommSetSimpleGroup(nexrRingComm_t comm, int on);
 
 /* The LL flag rule of this communicator (nexrLLFlagRule, include/nexr.h; NULL or {0, 0x7ffffff8}: the
  * production rule, the default; {0x100, 0x78}: the reference's TEST_LL_CLEANUP), for every channel. Its LL

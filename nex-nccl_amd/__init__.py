@@ -87,6 +87,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrReduceCopyHost", "nexrHostToDevRedOp", "nexrLaunchOneRank",
                "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrReduceCopyLLStepsRule",
                "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrReduceCopyLL128StepsGroup",
+               "nexrSimpleGroupWorkspaceBytes", "nexrReduceCopySimpleStepsGroup",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -153,6 +154,21 @@ class LLConnSet(ctypes.Structure):
                 ("recvStep", ctypes.c_uint64 * 3), ("sendFifo", ctypes.c_void_p * 3),
                 ("sendHead", ctypes.c_void_p * 3), ("sendStep", ctypes.c_uint64 * 3),
                 ("slotBytes", ctypes.c_uint64), ("nSlots", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+SIMPLE_CREDIT_BYTES = 4096   # NEXR_SIMPLE_CREDIT_BYTES: a connection's tail block, and its head block
+SIMPLE_GROUP_MAX_GRID = 256  # NEXR_SIMPLE_GROUP_MAX_GRID
+SIMPLE_TILE_BYTES = 4096     # tile t of a slice belongs to workgroup t % G
+
+
+class SimpleConnSet(ctypes.Structure):
+    """Mirror of nexrSimpleConnSet (include/nexr.h): the connections a SIMPLE step list uses."""
+    _fields_ = [("input", ctypes.c_void_p), ("output", ctypes.c_void_p), ("nRecv", ctypes.c_int),
+                ("nSend", ctypes.c_int), ("recvFifo", ctypes.c_void_p * 3), ("recvTail", ctypes.c_void_p * 3),
+                ("recvHead", ctypes.c_void_p * 3), ("recvStep", ctypes.c_uint64 * 3),
+                ("sendFifo", ctypes.c_void_p * 3), ("sendTail", ctypes.c_void_p * 3),
+                ("sendHead", ctypes.c_void_p * 3), ("sendStep", ctypes.c_uint64 * 3),
+                ("slotBytes", ctypes.c_uint64), ("nSlots", ctypes.c_uint32), ("stepPerSlice", ctypes.c_uint32)]
 
 
 class LLFlagRule(ctypes.Structure):
@@ -281,6 +297,11 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopyLL128StepsGroup.argtypes = [i32, P(LLConnSet), P(P(LLStep)), P(i32), i32, i32, u64, vp,
                                                 ctypes.c_uint32, vp, sz, vp]
     L.nexrReduceCopyLL128StepsGroup.restype = i32
+    L.nexrSimpleGroupWorkspaceBytes.argtypes = [i32, P(sz)]
+    L.nexrSimpleGroupWorkspaceBytes.restype = i32
+    L.nexrReduceCopySimpleStepsGroup.argtypes = [i32, P(SimpleConnSet), P(P(LLStep)), P(i32), i32, i32, u64, i32, vp,
+                                                 ctypes.c_uint32, vp, sz, vp]
+    L.nexrReduceCopySimpleStepsGroup.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -602,6 +623,61 @@ def reduce_copy_ll128_steps_group(members: Sequence[tuple], slot_bytes: int, dat
                                              ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None, int(ws_bytes),
                                              ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrReduceCopyLL128StepsGroup")
+    return keep
+
+
+def simple_conn_set(input_ptr: int, output_ptr: int, recv: Sequence[tuple], send: Sequence[tuple], slot_bytes: int,
+                    n_slots: int = 8, step_per_slice: int = 1) -> SimpleConnSet:
+    """A SimpleConnSet from (fifo pointer, tail-block pointer, head-block pointer, step counter) per
+    connection."""
+    cs = SimpleConnSet()
+    cs.input, cs.output = int(input_ptr) or None, int(output_ptr) or None
+    cs.nRecv, cs.nSend = len(recv), len(send)
+    for i, (fifo, tail, head, step) in enumerate(recv):
+        cs.recvFifo[i], cs.recvTail[i], cs.recvHead[i], cs.recvStep[i] = int(fifo), int(tail), int(head), int(step)
+    for i, (fifo, tail, head, step) in enumerate(send):
+        cs.sendFifo[i], cs.sendTail[i], cs.sendHead[i], cs.sendStep[i] = int(fifo), int(tail), int(head), int(step)
+    cs.slotBytes, cs.nSlots, cs.stepPerSlice = int(slot_bytes), int(n_slots), int(step_per_slice)
+    return cs
+
+
+def simple_group_workspace_bytes(n_members: int, n_launches: int = LL_GROUP_LAUNCHES) -> int:
+    """Bytes of workspace for `n_launches` launches of a SIMPLE group of `n_members`
+    (nexrSimpleGroupWorkspaceBytes sizes for LL_GROUP_LAUNCHES; a region per launch is that / LL_GROUP_LAUNCHES)."""
+    b = ctypes.c_size_t(0)
+    _check(lib().nexrSimpleGroupWorkspaceBytes(int(n_members), ctypes.byref(b)), "nexrSimpleGroupWorkspaceBytes")
+    return b.value // LL_GROUP_LAUNCHES * max(1, int(n_launches))
+
+
+def reduce_copy_simple_steps_group(members: Sequence[tuple], slot_bytes: int, datatype: int, dev_red_op: int,
+                                   red_op_arg: int = 0, n_slots: int = 8, step_per_slice: int = 1,
+                                   workgroups_per_member: int = 0, status: int = 0, timeout_us: int = 0,
+                                   stream: int = 0, workspace=None):
+    """SIMPLE step lists of several Primitives in the same launches on one stream, tails and heads in device
+    memory (nexrReduceCopySimpleStepsGroup). members: (input_ptr, output_ptr, recv, send, steps) per member,
+    recv / send as in simple_conn_set, steps a list of LLStep (one slice each). workspace: (device pointer,
+    bytes), or None to allocate one (a torch uint8 tensor sized for one launch per step of the longest list,
+    the most a call can need). Returns the workspace tensor it allocated (None when one was given): keep it
+    alive until the stream has passed the call."""
+    n = len(members)
+    cs = (SimpleConnSet * max(1, n))(*[simple_conn_set(m[0], m[1], m[2], m[3], slot_bytes, n_slots, step_per_slice)
+                                       for m in members])
+    arrs = [(LLStep * max(1, len(m[4])))(*m[4]) for m in members]
+    ptrs = (ctypes.POINTER(LLStep) * max(1, n))(*[ctypes.cast(a, ctypes.POINTER(LLStep)) for a in arrs])
+    counts = (ctypes.c_int * max(1, n))(*[len(m[4]) for m in members])
+    keep = None
+    if workspace is None and 1 <= n <= LL_GROUP_MAX_MEMBERS:
+        import torch
+        longest = max([len(m[4]) for m in members] + [1])
+        keep = torch.empty(simple_group_workspace_bytes(n, longest), dtype=torch.uint8, device="cuda")
+        workspace = (keep.data_ptr(), keep.numel())
+    ws_ptr, ws_bytes = workspace if workspace is not None else (0, 0)
+    rc = lib().nexrReduceCopySimpleStepsGroup(n, cs, ptrs, counts, int(datatype), int(dev_red_op),
+                                              int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, int(workgroups_per_member),
+                                              ctypes.c_void_p(int(status)) if status else None, int(timeout_us),
+                                              ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None, int(ws_bytes),
+                                              ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrReduceCopySimpleStepsGroup")
     return keep
 
 

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "nexr_internal.h"
@@ -1662,6 +1663,157 @@ nexrResult_t llGroupResident(bool ll128, int dt, int op, int64_t* resident) {
   return nexrSuccess;
 }
 
+// The planner of the group calls (LL, LL128 and SIMPLE step lists), from the members' parameter blocks `cur`
+// as they stand at the call's counters with no steps yet: the launch cuts, the dry run, the workspace and
+// residency checks, the one copy of the tables and the launches. A recv / send step advances a
+// connection's counters by `adv` (1, or SIMPLE's stepPerSlice) and a slot is free again nSlots steps later.
+// rule: the LL flag rule, whose cleaning steps end a launch (nullptr: none).
+extern "C++" {
+template <typename Params, typename ResidentFn, typename LaunchFn>
+nexrResult_t stepsGroupPlan(int nMembers, std::vector<Params>& cur, const nexrLLStep* const* steps, const int* nSteps,
+                            int maxSteps, size_t esz, uint64_t adv, uint64_t nSlots, const nexrLLFlagRule* rule, int G,
+                            ResidentFn residentFn, LaunchFn launchFn, void* workspace, size_t workspaceBytes,
+                            nexrStream_t stream) {
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  std::vector<Params> table;
+  std::vector<std::vector<UserRange>> seen((size_t)nMembers);
+  auto cut = [&]() {  // the launch is complete: its blocks go into the table, the next one starts at the counters
+    for (int m = 0; m < nMembers; m++) {
+      Params& P = cur[(size_t)m];
+      table.push_back(P);
+      for (int k = 0; k < P.nSteps; k++) {
+        const nexrLLStep& s = P.step[k];
+        for (int i = 0; i < MP; i++) P.recvStep[i] += s.recv ? adv : 0, P.sendStep[i] += s.send ? adv : 0;
+      }
+      P.nSteps = 0;
+      if constexpr (std::is_same<Params, LLStepsParams>::value) P.cleanLast = 0;
+      seen[(size_t)m].clear();
+    }
+  };
+  int inLaunch = 0;  // step indices in the current launch
+  for (int k = 0; k < maxSteps; k++) {
+    bool before = inLaunch == kLLStepsMax, cleans = false;
+    std::vector<UserRange> rd((size_t)nMembers, UserRange{0, 0, false}), wr((size_t)nMembers, UserRange{0, 0, true});
+    for (int m = 0; m < nMembers; m++) {
+      if (k >= nSteps[m]) continue;
+      const nexrLLStep& s = steps[m][k];
+      const Params& cs = cur[(size_t)m];
+      if (s.nElts && s.srcBuf >= 0) {
+        rd[(size_t)m].beg = (uintptr_t)(s.srcBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.srcIx * esz;
+        rd[(size_t)m].end = rd[(size_t)m].beg + (uintptr_t)s.nElts * esz;
+      }
+      if (s.nElts && s.dstBuf >= 0) {
+        wr[(size_t)m].beg = (uintptr_t)(s.dstBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.dstIx * esz;
+        wr[(size_t)m].end = wr[(size_t)m].beg + (uintptr_t)s.nElts * esz;
+      }
+      before = before || (rd[(size_t)m].end && rangesConflict(seen[(size_t)m], rd[(size_t)m])) ||
+               (wr[(size_t)m].end && rangesConflict(seen[(size_t)m], wr[(size_t)m]));
+    }
+    if (before && inLaunch) {
+      cut();
+      inLaunch = 0;
+    }
+    for (int m = 0; m < nMembers; m++) {
+      if (k >= nSteps[m]) continue;
+      const nexrLLStep& s = steps[m][k];
+      Params& P = cur[(size_t)m];
+      // the member's send counters at this step: those of the launch's start plus its send steps so far
+      uint64_t sent = 0;
+      for (int q = 0; q < P.nSteps; q++) sent += P.step[q].send ? 1 : 0;
+      P.step[P.nSteps++] = s;
+      if (rd[(size_t)m].end) seen[(size_t)m].push_back(rd[(size_t)m]);
+      if (wr[(size_t)m].end) seen[(size_t)m].push_back(wr[(size_t)m]);
+      if constexpr (std::is_same<Params, LLStepsParams>::value) {
+        if (s.send && rule)
+          for (int j = 0; j < P.nSend; j++) {
+            const uint64_t ss = P.sendStep[j] + sent;
+            if (((uint32_t)ss & rule->cleanMask) == rule->cleanMask) {
+              P.cleanLast |= 1u << j;
+              P.cleanStep[j] = ss;
+              cleans = true;
+            }
+          }
+      }
+    }
+    inLaunch++;
+    if (cleans) {
+      cut();
+      inLaunch = 0;
+    }
+  }
+  if (inLaunch) cut();
+  const size_t nLaunches = table.size() / (size_t)nMembers;
+
+  // The dry run: every launch must finish with what it and the launches before it produce, because the
+  // next one starts only behind it on the stream. Connections whose FIFO is some member's send FIFO and
+  // another's receive FIFO are internal: their data and credit counters are walked here; the others are
+  // taken as always ready (their peer runs elsewhere).
+  struct Link {
+    uint64_t sent, read;
+  };
+  std::vector<Link> links;
+  std::vector<int> sendLink((size_t)nMembers * MP, -1), recvLink((size_t)nMembers * MP, -1);
+  const Params* first = table.data();  // the first launch's blocks: the connections at the call's counters
+  for (int m = 0; m < nMembers; m++)
+    for (int j = 0; j < first[m].nSend; j++)
+      for (int r = 0; r < nMembers && sendLink[(size_t)m * MP + j] < 0; r++)
+        for (int i = 0; i < first[r].nRecv; i++)
+          if ((const void*)first[r].recvFifo[i] == (const void*)first[m].sendFifo[j] &&
+              recvLink[(size_t)r * MP + i] < 0) {
+            if (first[m].sendStep[j] < first[r].recvStep[i]) return nexrInvalidUsage;  // more read than sent
+            sendLink[(size_t)m * MP + j] = recvLink[(size_t)r * MP + i] = (int)links.size();
+            links.push_back(Link{first[m].sendStep[j], first[r].recvStep[i]});
+            break;
+          }
+  std::vector<int> pos((size_t)nMembers);
+  for (size_t l = 0; l < nLaunches; l++) {
+    const Params* L = &table[l * (size_t)nMembers];
+    std::fill(pos.begin(), pos.end(), 0);
+    for (bool progress = true; progress;) {
+      progress = false;
+      for (int m = 0; m < nMembers; m++) {
+        while (pos[(size_t)m] < L[m].nSteps) {
+          const nexrLLStep& s = L[m].step[pos[(size_t)m]];
+          bool ready = true;
+          for (int i = 0; s.recv && i < L[m].nRecv; i++) {  // the line flags: the sender has written the step
+            const int id = recvLink[(size_t)m * MP + i];
+            if (id >= 0 && links[(size_t)id].sent < links[(size_t)id].read + adv) ready = false;
+          }
+          for (int j = 0; s.send && j < L[m].nSend; j++) {  // waitSend: the step nSlots back has been read
+            const int id = sendLink[(size_t)m * MP + j];
+            if (id >= 0 && links[(size_t)id].sent + adv > links[(size_t)id].read + nSlots) ready = false;
+          }
+          if (!ready) break;
+          for (int i = 0; s.recv && i < L[m].nRecv; i++)
+            if (recvLink[(size_t)m * MP + i] >= 0) links[(size_t)recvLink[(size_t)m * MP + i]].read += adv;
+          for (int j = 0; s.send && j < L[m].nSend; j++)
+            if (sendLink[(size_t)m * MP + j] >= 0) links[(size_t)sendLink[(size_t)m * MP + j]].sent += adv;
+          pos[(size_t)m]++;
+          progress = true;
+        }
+      }
+    }
+    for (int m = 0; m < nMembers; m++)
+      if (pos[(size_t)m] < L[m].nSteps) return nexrInvalidUsage;  // this launch would wait for a later one
+  }
+
+  // One region of the workspace per launch: a table is never written while a queued launch may read it.
+  if (workspaceBytes / sizeof(Params) / (size_t)nMembers < nLaunches) return nexrInvalidArgument;
+
+  // Co-residency: all nMembers * G workgroups at once, or a poll could wait for a workgroup that has no CU.
+  int64_t resident = 0;
+  const nexrResult_t occ = residentFn(&resident);
+  if (occ != nexrSuccess) return occ;
+  if ((int64_t)nMembers * G > resident) return nexrInvalidUsage;
+
+  // Pageable source: the runtime has staged it when the call returns, so `table` may go out of scope.
+  NEXR_HIP(hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(Params), hipMemcpyHostToDevice,
+                          (hipStream_t)stream));
+  for (size_t l = 0; l < nLaunches; l++) NEXR_HIP(launchFn((const Params*)workspace + l * (size_t)nMembers));
+  return nexrSuccess;
+}
+}  // extern "C++"
+
 // The host side of both group calls: the argument checks, the launch cuts, the dry run, the workspace and
 // residency checks, the one copy of the tables and the launches. rule == nullptr: LL128 steps
 // (nexrReduceCopyLL128StepsGroup), which have no cleaning steps (so no cut behind one), slots counted in
@@ -1691,7 +1843,6 @@ nexrResult_t llStepsGroup(int nMembers, const nexrLLConnSet* conns, const nexrLL
   // member's 97th of the launch or that conflicts with user bytes the member touched earlier in it
   // (rangesConflict), and behind a step that cleans on any member (the kernel cleans behind a member's
   // last step). Entry (launch l, member m) of the table is that member's parameter block of launch l.
-  std::vector<LLStepsParams> table;
   std::vector<LLStepsParams> cur((size_t)nMembers);
   for (int m = 0; m < nMembers; m++) {
     const nexrLLConnSet& cs = conns[m];
@@ -1717,145 +1868,18 @@ nexrResult_t llStepsGroup(int nMembers, const nexrLLConnSet* conns, const nexrLL
     P.firstWins = firstWins;
     P.flagMask = rule && rule->flagMax ? rule->flagMax - 1 : 0xffffffffu;
   }
-  std::vector<std::vector<UserRange>> seen((size_t)nMembers);
-  auto cut = [&]() {  // the launch is complete: its blocks go into the table, the next one starts at the counters
-    for (int m = 0; m < nMembers; m++) {
-      LLStepsParams& P = cur[(size_t)m];
-      table.push_back(P);
-      for (int k = 0; k < P.nSteps; k++) {
-        const nexrLLStep& s = P.step[k];
-        for (int i = 0; i < MP; i++) P.recvStep[i] += s.recv ? 1 : 0, P.sendStep[i] += s.send ? 1 : 0;
-      }
-      P.nSteps = 0;
-      P.cleanLast = 0;
-      seen[(size_t)m].clear();
-    }
-  };
-  int inLaunch = 0;  // step indices in the current launch
-  for (int k = 0; k < maxSteps; k++) {
-    bool before = inLaunch == kLLStepsMax, cleans = false;
-    std::vector<UserRange> rd((size_t)nMembers, UserRange{0, 0, false}), wr((size_t)nMembers, UserRange{0, 0, true});
-    for (int m = 0; m < nMembers; m++) {
-      if (k >= nSteps[m]) continue;
-      const nexrLLStep& s = steps[m][k];
-      const nexrLLConnSet& cs = conns[m];
-      if (s.nElts && s.srcBuf >= 0) {
-        rd[(size_t)m].beg = (uintptr_t)(s.srcBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.srcIx * esz;
-        rd[(size_t)m].end = rd[(size_t)m].beg + (uintptr_t)s.nElts * esz;
-      }
-      if (s.nElts && s.dstBuf >= 0) {
-        wr[(size_t)m].beg = (uintptr_t)(s.dstBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.dstIx * esz;
-        wr[(size_t)m].end = wr[(size_t)m].beg + (uintptr_t)s.nElts * esz;
-      }
-      before = before || (rd[(size_t)m].end && rangesConflict(seen[(size_t)m], rd[(size_t)m])) ||
-               (wr[(size_t)m].end && rangesConflict(seen[(size_t)m], wr[(size_t)m]));
-    }
-    if (before && inLaunch) {
-      cut();
-      inLaunch = 0;
-    }
-    for (int m = 0; m < nMembers; m++) {
-      if (k >= nSteps[m]) continue;
-      const nexrLLStep& s = steps[m][k];
-      LLStepsParams& P = cur[(size_t)m];
-      // the member's send counters at this step: those of the launch's start plus its send steps so far
-      uint64_t sent = 0;
-      for (int q = 0; q < P.nSteps; q++) sent += P.step[q].send ? 1 : 0;
-      P.step[P.nSteps++] = s;
-      if (rd[(size_t)m].end) seen[(size_t)m].push_back(rd[(size_t)m]);
-      if (wr[(size_t)m].end) seen[(size_t)m].push_back(wr[(size_t)m]);
-      if (s.send && rule)
-        for (int j = 0; j < conns[m].nSend; j++) {
-          const uint64_t ss = P.sendStep[j] + sent;
-          if (((uint32_t)ss & rule->cleanMask) == rule->cleanMask) {
-            P.cleanLast |= 1u << j;
-            P.cleanStep[j] = ss;
-            cleans = true;
-          }
-        }
-    }
-    inLaunch++;
-    if (cleans) {
-      cut();
-      inLaunch = 0;
-    }
-  }
-  if (inLaunch) cut();
-  const size_t nLaunches = table.size() / (size_t)nMembers;
-
-  // The dry run: every launch must finish with what it and the launches before it produce, because the
-  // next one starts only behind it on the stream. Connections whose FIFO is some member's send FIFO and
-  // another's receive FIFO are internal: their data and credit counters are walked here; the others are
-  // taken as always ready (their peer runs elsewhere).
-  struct Link {
-    uint64_t sent, read;
-  };
-  std::vector<Link> links;
-  std::vector<int> sendLink((size_t)nMembers * MP, -1), recvLink((size_t)nMembers * MP, -1);
-  for (int m = 0; m < nMembers; m++)
-    for (int j = 0; j < conns[m].nSend; j++)
-      for (int r = 0; r < nMembers && sendLink[(size_t)m * MP + j] < 0; r++)
-        for (int i = 0; i < conns[r].nRecv; i++)
-          if (conns[r].recvFifo[i] == conns[m].sendFifo[j] && recvLink[(size_t)r * MP + i] < 0) {
-            if (conns[m].sendStep[j] < conns[r].recvStep[i]) return nexrInvalidUsage;  // more read than sent
-            sendLink[(size_t)m * MP + j] = recvLink[(size_t)r * MP + i] = (int)links.size();
-            links.push_back(Link{conns[m].sendStep[j], conns[r].recvStep[i]});
-            break;
-          }
-  std::vector<int> pos((size_t)nMembers);
-  for (size_t l = 0; l < nLaunches; l++) {
-    const LLStepsParams* L = &table[l * (size_t)nMembers];
-    std::fill(pos.begin(), pos.end(), 0);
-    for (bool progress = true; progress;) {
-      progress = false;
-      for (int m = 0; m < nMembers; m++) {
-        while (pos[(size_t)m] < L[m].nSteps) {
-          const nexrLLStep& s = L[m].step[pos[(size_t)m]];
-          bool ready = true;
-          for (int i = 0; s.recv && i < L[m].nRecv; i++) {  // the line flags: the sender has written the step
-            const int id = recvLink[(size_t)m * MP + i];
-            if (id >= 0 && links[(size_t)id].sent < links[(size_t)id].read + 1) ready = false;
-          }
-          for (int j = 0; s.send && j < L[m].nSend; j++) {  // waitSend: the step nSlots back has been read
-            const int id = sendLink[(size_t)m * MP + j];
-            if (id >= 0 && links[(size_t)id].sent + 1 > links[(size_t)id].read + nSlots) ready = false;
-          }
-          if (!ready) break;
-          for (int i = 0; s.recv && i < L[m].nRecv; i++)
-            if (recvLink[(size_t)m * MP + i] >= 0) links[(size_t)recvLink[(size_t)m * MP + i]].read++;
-          for (int j = 0; s.send && j < L[m].nSend; j++)
-            if (sendLink[(size_t)m * MP + j] >= 0) links[(size_t)sendLink[(size_t)m * MP + j]].sent++;
-          pos[(size_t)m]++;
-          progress = true;
-        }
-      }
-    }
-    for (int m = 0; m < nMembers; m++)
-      if (pos[(size_t)m] < L[m].nSteps) return nexrInvalidUsage;  // this launch would wait for a later one
-  }
-
-  // One region of the workspace per launch: a table is never written while a queued launch may read it.
-  if (workspaceBytes / kLLGroupEntryBytes / (size_t)nMembers < nLaunches) return nexrInvalidArgument;
-
-  // Co-residency: all nMembers * G workgroups at once, or a poll could wait for a workgroup that has no CU.
   // (a workgroup per tile of a slot: kLLTileLines 16-byte lines, or kLL128TileUnits 16-byte wire units)
   const uint64_t tileUnits = ll128 ? kLL128TileUnits : kLLTileLines;
   const uint64_t slotTiles = (conns[0].slotBytes / 16 + tileUnits - 1) / tileUnits;
   const int G = (int)(slotTiles < 1 ? 1 : slotTiles > (uint64_t)kLLStepsMaxGrid ? kLLStepsMaxGrid : slotTiles);
-  int64_t resident = 0;
-  const nexrResult_t occ = llGroupResident(ll128, datatype, devRedOp, &resident);
-  if (occ != nexrSuccess) return occ;
-  if ((int64_t)nMembers * G > resident) return nexrInvalidUsage;
-
-  // Pageable source: the runtime has staged it when the call returns, so `table` may go out of scope.
-  NEXR_HIP(hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(LLStepsParams), hipMemcpyHostToDevice,
-                          (hipStream_t)stream));
-  for (size_t l = 0; l < nLaunches; l++) {
-    const LLStepsParams* entries = (const LLStepsParams*)workspace + l * (size_t)nMembers;
-    NEXR_HIP(ll128 ? launch_ll128_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream)
-                   : launch_ll_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream));
-  }
-  return nexrSuccess;
+  return stepsGroupPlan(
+      nMembers, cur, steps, nSteps, maxSteps, esz, 1, nSlots, rule, G,
+      [&](int64_t* resident) { return llGroupResident(ll128, datatype, devRedOp, resident); },
+      [&](const LLStepsParams* entries) {
+        return ll128 ? launch_ll128_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream)
+                     : launch_ll_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
+      },
+      workspace, workspaceBytes, stream);
 }
 }  // namespace
 
@@ -1876,6 +1900,146 @@ NEXR_API nexrResult_t nexrReduceCopyLL128StepsGroup(int nMembers, const nexrLLCo
                                                     nexrStream_t stream) {
   return llStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, nullptr, status, timeoutUs,
                       workspace, workspaceBytes, stream);
+}
+
+// ---- nexrReduceCopySimpleStepsGroup: SIMPLE step lists of several Primitives in one launch ------------
+NEXR_API nexrResult_t nexrSimpleGroupWorkspaceBytes(int nMembers, size_t* bytes) {
+  if (!bytes || nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS) return nexrInvalidArgument;
+  *bytes = (size_t)nMembers * sizeof(SimpleStepsParams) * NEXR_LL_GROUP_LAUNCHES;
+  return nexrSuccess;
+}
+
+namespace {
+// Workgroups of the SIMPLE group kernel the current device keeps resident, as llGroupResident. The
+// hardware admits 256-thread workgroups by their scalar registers too, and for kernels that use more than
+// 80 of them one fewer per CU than the occupancy query says; a surplus workgroup would queue until a
+// resident one exits, which a poll may be waiting for. So one is taken off the query's answer.
+// Test hook: NEXR_TEST_SIMPLE_GROUP_RESIDENT=k makes the next calls take k as that number (read per call).
+nexrResult_t simpleGroupResident(int dt, int op, int64_t* resident) {
+  if (const char* e = getenv("NEXR_TEST_SIMPLE_GROUP_RESIDENT"))
+    if (*e) {
+      *resident = strtoll(e, nullptr, 10);
+      return nexrSuccess;
+    }
+  constexpr int kDevs = 16;
+  static std::atomic<int64_t> cache[kDevs][nexrNumTypes][nexrNumDevRedOps];
+  int dev = 0;
+  NEXR_HIP(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < kDevs;
+  if (cached) {
+    const int64_t v = cache[dev][dt][op].load(std::memory_order_relaxed);
+    if (v > 0) {
+      *resident = v;
+      return nexrSuccess;
+    }
+  }
+  int cus = 0, blocks = 0;
+  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  NEXR_HIP(simple_group_blocks_per_cu(dt, op, &blocks));
+  if (blocks > 8) blocks = 8;
+  if (blocks > 1) blocks--;
+  *resident = (int64_t)blocks * cus;
+  if (cached && *resident > 0) cache[dev][dt][op].store(*resident, std::memory_order_relaxed);
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns,
+                                                     const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                     int devRedOp, uint64_t redOpArg, int workgroupsPerMember,
+                                                     uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                     size_t workspaceBytes, nexrStream_t stream) {
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  if (nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || !conns || !steps || !nSteps) return nexrInvalidArgument;
+  if (workgroupsPerMember < 0 || workgroupsPerMember > NEXR_SIMPLE_GROUP_MAX_GRID) return nexrInvalidArgument;
+  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
+    return nexrInvalidArgument;
+  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
+  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
+  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
+    uint32_t divisor = (uint32_t)(redOpArg >> 1);
+    if (divisor == 0) divisor = 1;
+    if ((int8_t)divisor == 0) return nexrInvalidArgument;
+  }
+  const size_t esz = typeSize(datatype);
+  int maxSteps = 0;
+  for (int m = 0; m < nMembers; m++) {
+    const nexrSimpleConnSet& cs = conns[m];
+    if (nSteps[m] < 0 || (nSteps[m] > 0 && !steps[m])) return nexrInvalidArgument;
+    if (cs.nRecv < 0 || cs.nRecv > MP || cs.nSend < 0 || cs.nSend > MP) return nexrInvalidArgument;
+    if (cs.slotBytes == 0 || cs.slotBytes % 16 || cs.nSlots == 0 || cs.nSlots > (uint32_t)INT_MAX)
+      return nexrInvalidArgument;
+    if (cs.stepPerSlice < 1 || cs.nSlots % cs.stepPerSlice) return nexrInvalidArgument;
+    // one G, one credit window and one slice size serve the launch
+    if (cs.slotBytes != conns[0].slotBytes || cs.nSlots != conns[0].nSlots || cs.stepPerSlice != conns[0].stepPerSlice)
+      return nexrInvalidArgument;
+    for (int i = 0; i < cs.nRecv; i++)
+      if (!cs.recvFifo[i] || ((uintptr_t)cs.recvFifo[i] & 15) || !cs.recvTail[i] || ((uintptr_t)cs.recvTail[i] & 7) ||
+          !cs.recvHead[i] || ((uintptr_t)cs.recvHead[i] & 7) || cs.recvStep[i] % cs.stepPerSlice)
+        return nexrInvalidArgument;
+    for (int i = 0; i < cs.nSend; i++)
+      if (!cs.sendFifo[i] || ((uintptr_t)cs.sendFifo[i] & 15) || !cs.sendTail[i] || ((uintptr_t)cs.sendTail[i] & 7) ||
+          !cs.sendHead[i] || ((uintptr_t)cs.sendHead[i] & 7) || cs.sendStep[i] % cs.stepPerSlice)
+        return nexrInvalidArgument;
+    const uint64_t sliceBytes = cs.slotBytes * cs.stepPerSlice;
+    for (int k = 0; k < nSteps[m]; k++) {
+      const nexrLLStep& s = steps[m][k];
+      if (s.srcBuf < -1 || s.srcBuf > 1 || s.dstBuf < -1 || s.dstBuf > 1) return nexrInvalidArgument;
+      if ((s.recv && cs.nRecv == 0) || (s.send && cs.nSend == 0)) return nexrInvalidArgument;
+      if ((s.srcBuf == 0 && !cs.input) || (s.srcBuf == 1 && !cs.output) || (s.dstBuf == 0 && !cs.input) ||
+          (s.dstBuf == 1 && !cs.output))
+        return nexrInvalidArgument;
+      if (s.srcIx < 0 || s.dstIx < 0) return nexrInvalidArgument;
+      if (s.nElts == 0) continue;
+      if ((s.srcBuf < 0 && !s.recv) || (s.dstBuf < 0 && !s.send)) return nexrInvalidArgument;
+      if ((uint64_t)s.nElts * esz > sliceBytes) return nexrInvalidArgument;
+    }
+    maxSteps = std::max(maxSteps, nSteps[m]);
+  }
+  if (maxSteps == 0) return nexrSuccess;
+  if (!workspace || ((uintptr_t)workspace & 7)) return nexrInvalidArgument;
+  const uint64_t sps = conns[0].stepPerSlice;
+  int srcIsInput = 1, postOp = 1, firstWins = 0;
+  llSemantics(&datatype, &devRedOp, &srcIsInput, &postOp, &firstWins);  // fork: the dispatch type; shipped: source 0
+
+  std::vector<SimpleStepsParams> cur((size_t)nMembers);
+  for (int m = 0; m < nMembers; m++) {
+    const nexrSimpleConnSet& cs = conns[m];
+    SimpleStepsParams& P = cur[(size_t)m];
+    memset(&P, 0, sizeof(P));
+    P.input = (const char*)cs.input;
+    P.output = (char*)cs.output;
+    for (int i = 0; i < MP; i++) {
+      P.recvFifo[i] = (const char*)cs.recvFifo[i];
+      P.recvTail[i] = cs.recvTail[i];
+      P.recvHead[i] = cs.recvHead[i];
+      P.sendFifo[i] = (char*)cs.sendFifo[i];
+      P.sendTail[i] = cs.sendTail[i];
+      P.sendHead[i] = cs.sendHead[i];
+      P.recvStep[i] = cs.recvStep[i];
+      P.sendStep[i] = cs.sendStep[i];
+    }
+    P.slotBytes = cs.slotBytes;
+    P.redArg = redOpArg;
+    P.status = status;
+    P.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;
+    P.nRecv = cs.nRecv;
+    P.nSend = cs.nSend;
+    P.nSlots = (int)cs.nSlots;
+    P.firstWins = firstWins;
+    P.stepPerSlice = (int)cs.stepPerSlice;
+  }
+  // A workgroup per 4 KiB tile of a full slice unless the caller says how many.
+  const uint64_t sliceTiles = (conns[0].slotBytes * sps + kSimpleTileBytes - 1) / kSimpleTileBytes;
+  const int G = workgroupsPerMember ? workgroupsPerMember
+                                    : (int)(sliceTiles > (uint64_t)kSimpleMaxGrid ? kSimpleMaxGrid : sliceTiles);
+  return stepsGroupPlan(
+      nMembers, cur, steps, nSteps, maxSteps, esz, sps, conns[0].nSlots, nullptr, G,
+      [&](int64_t* resident) { return simpleGroupResident(datatype, devRedOp, resident); },
+      [&](const SimpleStepsParams* entries) {
+        return launch_simple_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
+      },
+      workspace, workspaceBytes, stream);
 }
 
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,

@@ -70,6 +70,11 @@ struct Conn {
   // Thread ranks, FIFO in device memory: the receiver's head words for runs of LL steps on the device
   // (nexrReduceCopyLLSteps), NEXR_LL_HEAD_BYTES right behind the FIFO in the same zeroed allocation.
   uint64_t* devHead = nullptr;
+  // SIMPLE group launches (nexrRingCommSetSimpleGroup): the connection's tail block (written by the sender's
+  // workgroups) and head block (by the receiver's), NEXR_SIMPLE_CREDIT_BYTES each in one zeroed device
+  // allocation, made when the option is first switched on.
+  uint64_t* simpleTail = nullptr;
+  uint64_t* simpleHead = nullptr;
   ConnState own;
   ConnState* st = &own;  // the counters: `own` for thread ranks, a shared-memory slot for process ranks
   // Each endpoint's step (the conn->step a Primitives loads and saves, prims_simple.h:528-560): only
@@ -187,12 +192,14 @@ struct nexrRingComm {
   bool stepWaitWord = true;
   // How the last thread-rank ring collective ran its LL steps (diagnostics, nexrRingCommGetQueued):
   // 0 host-sequenced, 1 queued launches (Prims::enableLLAsync), 2 runs with device credits (enableLLRun).
-  // 3: group launches on one stream (nexrRingCommSetLLGroup; LL and LL128). The tree all-reduce reports
+  // 3: group launches on one stream (nexrRingCommSetLLGroup; LL and LL128; nexrRingCommSetSimpleGroup for the
+  // SIMPLE ring collectives). The tree all-reduce reports
   // here only while that option is on (3, or 0 when it fell back).
   int lastLLMode = 0;
   // nexrRingCommSetLLGroup: the option, and the device workspace of the group launches' tables (made by
   // the first group collective on the ranks' GPU, grown when a collective needs more launches).
   bool llGroup = false;
+  bool simpleGroup = false;  // nexrRingCommSetSimpleGroup (SIMPLE communicators; the same workspace)
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;
@@ -484,6 +491,43 @@ struct Prims {
     enableLLRun(true);
     llRecord = llRun;
   }
+  // SIMPLE group launches (nexrRingCommSetSimpleGroup): genericOp records its slices instead of running
+  // them (no waits, no launches, the counters advance); the calling thread launches every member's list.
+  bool simpleRecord = false;
+  void enableSimpleRecord() {
+    if (proto != nexrRingProtoSimple || !device || !c->stepWaitWord) return;
+    if (nRecv > NEXR_LL_STEPS_MAX_PEERS || nSend > NEXR_LL_STEPS_MAX_PEERS) return;
+    for (int i = 0; i < nRecv; i++)
+      if (!recv[i]->simpleHead || slot(recv[i]) != c->stepBytes) return;
+    for (int i = 0; i < nSend; i++)
+      if (!send[i]->simpleHead || slot(send[i]) != c->stepBytes) return;
+    simpleRecord = true;
+    run.clear();
+  }
+  nexrSimpleConnSet simpleConnSet() const {
+    nexrSimpleConnSet cs;
+    memset(&cs, 0, sizeof(cs));
+    cs.input = userInput;
+    cs.output = userOutput;
+    cs.nRecv = nRecv;
+    cs.nSend = nSend;
+    for (int i = 0; i < nRecv; i++) {
+      cs.recvFifo[i] = recv[i]->fifo;
+      cs.recvTail[i] = recv[i]->simpleTail;
+      cs.recvHead[i] = recv[i]->simpleHead;
+      cs.recvStep[i] = runRecv0[i];
+    }
+    for (int i = 0; i < nSend; i++) {
+      cs.sendFifo[i] = send[i]->fifo;
+      cs.sendTail[i] = send[i]->simpleTail;
+      cs.sendHead[i] = send[i]->simpleHead;
+      cs.sendStep[i] = runSend0[i];
+    }
+    cs.slotBytes = c->stepBytes;
+    cs.nSlots = kSteps;
+    cs.stepPerSlice = (uint32_t)stepPerSlice;
+    return cs;
+  }
   // The connections of this Primitives as the LL steps calls take them, at the run's first step.
   nexrLLConnSet connSet() const {
     nexrLLConnSet cs;
@@ -610,6 +654,31 @@ struct Prims {
     for (int slice = 0; slice < slicePerChunk; slice++) {
       sliceSize = std::min(sliceSize, nelem - offset);
       if (sliceSize < 0) sliceSize = 0;
+      if (simpleRecord) {  // no wait and no launch: the group launches' kernel waits and posts on the device
+        if (sh->aborted()) {
+          sh->fail(nexrRemoteError);
+          return false;
+        }
+        if (run.empty()) {
+          for (int i = 0; i < nRecv; i++) runRecv0[i] = recv[i]->recvStep;
+          for (int i = 0; i < nSend; i++) runSend0[i] = send[i]->sendStep;
+        }
+        nexrLLStep s;
+        memset(&s, 0, sizeof(s));
+        s.srcBuf = (int8_t)(srcBuf == kNone ? -1 : srcBuf);
+        s.dstBuf = (int8_t)(dstBuf == kNone ? -1 : dstBuf);
+        s.srcIx = srcBuf == kNone ? 0 : srcIx + offset;
+        s.dstIx = dstBuf == kNone ? 0 : dstIx + offset;
+        s.nElts = (uint32_t)sliceSize;  // zero-size slices are recorded too: they advance and post
+        s.recv = nr > 0;
+        s.send = ns > 0;
+        s.postOp = postOp ? 1 : 0;
+        run.push_back(s);
+        for (int i = 0; i < nr; i++) recv[i]->recvStep += stepPerSlice;
+        for (int i = 0; i < ns; i++) send[i]->sendStep += stepPerSlice;
+        offset += sliceSize;
+        continue;
+      }
       const void* srcs[1 + kMaxArity];
       void* dsts[1 + kMaxArity];
       int k = 0, m = 0;

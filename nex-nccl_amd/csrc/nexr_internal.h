@@ -143,6 +143,39 @@ hipError_t launch_ll128(int dt, const LL128Params& a, int op, int grid, hipStrea
 hipError_t launch_ll128_group(int dt, int op, const LLStepsParams* table, int nMembers, int G, hipStream_t s);
 hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks);
 
+// SIMPLE step lists of nMembers Primitives in one launch (nexrReduceCopySimpleStepsGroup; nexr_simple.hip).
+// A record is one slice of genericOp; tile t (kSimpleTileBytes from the slice's start) belongs to workgroup
+// t % G on both ends of a connection, and the credit is per workgroup: word w (kSimpleCreditStride apart)
+// of a connection's tail block says how far the sender's workgroup w has published, word w of its head
+// block how far the receiver's workgroup w has released.
+constexpr int kSimpleTileBytes = 4096;
+constexpr int kSimpleCreditStride = 16;
+constexpr int kSimpleMaxGrid = NEXR_SIMPLE_CREDIT_BYTES / kSimpleCreditStride;
+static_assert(kSimpleMaxGrid == NEXR_SIMPLE_GROUP_MAX_GRID, "public grid limit must match the credit block");
+struct SimpleStepsParams {
+  const char* input;
+  char* output;
+  const char* recvFifo[NEXR_LL_STEPS_MAX_PEERS];
+  const uint64_t* recvTail[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t* recvHead[NEXR_LL_STEPS_MAX_PEERS];
+  char* sendFifo[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t* sendTail[NEXR_LL_STEPS_MAX_PEERS];
+  const uint64_t* sendHead[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t recvStep[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t sendStep[NEXR_LL_STEPS_MAX_PEERS];
+  uint64_t slotBytes;
+  uint64_t redArg;
+  uint32_t* status;
+  uint64_t timeoutTicks;
+  int nRecv, nSend, nSlots, nSteps;
+  int firstWins;     // nexrSemanticsShipped: every reduce returns source 0
+  int stepPerSlice;  // counter steps (and slots) per record
+  nexrLLStep step[kLLStepsMax];
+};
+static_assert(sizeof(SimpleStepsParams) % 8 == 0, "table entries stay 8-byte aligned");
+hipError_t launch_simple_group(int dt, int op, const SimpleStepsParams* table, int nMembers, int G, hipStream_t s);
+hipError_t simple_group_blocks_per_cu(int dt, int op, int* blocks);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -1190,3 +1190,6 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 }
 
 }  // namespace nexr
+
+// SIMPLE step lists in group launches: the same code object (tests/test_code_objects.py counts them).
+#include "nexr_simple.hip"

@@ -569,6 +569,7 @@ void freeConn(nexrRingComm* c, Conn* k) {
     if (c->cfg.memMode == nexrRingDeviceMemory) {
       (void)hipSetDevice(k->device);
       (void)hipFree(k->fifo);
+      if (k->simpleTail) (void)hipFree(k->simpleTail);
     } else if (k->pinned) {
       (void)nexrHostMemFree(k->fifo);
     } else {
@@ -668,11 +669,26 @@ bool llGroupAllowed(const nexrRingComm* c, size_t nMembers) {
   return true;
 }
 
+// SIMPLE group launches (nexrRingCommSetSimpleGroup): every (channel, rank) Primitives of a ring collective
+// is a member of one nexrReduceCopySimpleStepsGroup call on one stream. Device memory, every rank on the one
+// GPU with the completion-word step wait, the library's own reduce-copy (not a caller's fn), and at most
+// NEXR_LL_GROUP_MAX_MEMBERS members; otherwise the collective is host-sequenced as without the option.
+bool simpleGroupAllowed(const nexrRingComm* c, size_t nMembers) {
+  if (!c->simpleGroup || c->proto != nexrRingProtoSimple || c->cfg.fn != defaultDeviceFn ||
+      c->cfg.memMode != nexrRingDeviceMemory || !c->stepWaitWord || nMembers > NEXR_LL_GROUP_MAX_MEMBERS ||
+      c->streams.empty() || !c->streams[0] || !c->status[0] || !c->done[0])
+    return false;
+  for (int d : c->devices)
+    if (d != c->devices[0]) return false;
+  return true;
+}
+
 // One member's record: its connections at its first step, its whole step list, and the Conn objects (up
 // to kMaxArity each way: the tree's fans) whose host counters the calling thread publishes once the
 // launches are complete.
 struct GroupMember {
-  nexrLLConnSet cs;
+  nexrLLConnSet cs = {};
+  nexrSimpleConnSet scs = {};  // SIMPLE members (Prims::enableSimpleRecord)
   std::vector<nexrLLStep> steps;
   Conn* recv[kMaxArity] = {};
   int nRecv = 0;
@@ -680,7 +696,10 @@ struct GroupMember {
   int nSend = 0;
   // Takes what a recording Primitives collected (Prims::enableLLRecord), every connection of it.
   void take(Prims& p) {
-    if (!p.run.empty()) cs = p.connSet();
+    if (!p.run.empty()) {
+      if (p.simpleRecord) scs = p.simpleConnSet();
+      else cs = p.connSet();
+    }
     steps.swap(p.run);
     nRecv = p.nRecv;
     nSend = p.nSend;
@@ -694,19 +713,22 @@ struct GroupMember {
 // resident at once) comes back unchanged, with nothing launched: the caller falls back.
 nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int datatype, const nexrDevRedOpFull& red) {
   const int n = (int)members.size();
+  const bool simple = c->proto == nexrRingProtoSimple;
+  std::vector<nexrSimpleConnSet> scs;
   std::vector<nexrLLConnSet> cs;
   std::vector<const nexrLLStep*> steps;
   std::vector<int> nSteps;
   size_t longest = 1;
   for (GroupMember& m : members) {
     cs.push_back(m.cs);
+    scs.push_back(m.scs);
     steps.push_back(m.steps.data());
     nSteps.push_back((int)m.steps.size());
     longest = std::max(longest, m.steps.size());
   }
   if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
   size_t perLaunch = 0;
-  nexrResult_t r = nexrLLGroupWorkspaceBytes(n, &perLaunch);
+  nexrResult_t r = simple ? nexrSimpleGroupWorkspaceBytes(n, &perLaunch) : nexrLLGroupWorkspaceBytes(n, &perLaunch);
   if (r != nexrSuccess) return r;
   perLaunch /= NEXR_LL_GROUP_LAUNCHES;
   hipStream_t stream = c->streams[0];
@@ -727,6 +749,22 @@ nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int da
       c->groupWsDevice = c->devices[0];
     }
     __atomic_store_n(status, 0u, __ATOMIC_RELEASE);
+    if (simple) {
+      // The default grid first (a workgroup per 4 KiB tile of a slice); a grid that is not resident at once
+      // is halved down to one workgroup per member before the collective gives the group up.
+      int G = 0;
+      for (;;) {
+        r = nexrReduceCopySimpleStepsGroup(n, scs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
+                                           G, status, (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
+                                           (nexrStream_t)stream);
+        if (r != nexrInvalidUsage || G == 1) break;
+        if (G == 0) {
+          const uint64_t tiles = (c->stepBytes * scs[0].stepPerSlice + 4095) / 4096;
+          G = (int)std::min<uint64_t>(tiles, NEXR_SIMPLE_GROUP_MAX_GRID);
+        }
+        G = std::max(1, G / 2);
+      }
+    } else
     r = c->proto == nexrRingProtoLL128
             ? nexrReduceCopyLL128StepsGroup(n, cs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
                                             status, (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
@@ -787,7 +825,8 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
   std::vector<ChannelPart> parts = channelParts(c, (int64_t)count, esz, trafficPerByte);
   for (ChannelPart& part : parts) part.chunkCount = chunkElems(channelComm(c, part.channel), g, esz, false, 0);
   Shared sh;
-  const bool group = tryGroup && llGroupAllowed(c, parts.size() * (size_t)n);
+  const bool simpleGroup = tryGroup && simpleGroupAllowed(c, parts.size() * (size_t)n);
+  const bool group = simpleGroup || (tryGroup && llGroupAllowed(c, parts.size() * (size_t)n));
   const bool llAsync = !group && llAsyncAllowed(c);
   const bool llRun = !group && llRunAllowed(c, llAsync);
   c->lastLLMode = group ? 3 : llRun ? 2 : llAsync ? 1 : 0;
@@ -816,8 +855,9 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
         p.send[p.nSend++] = ck->conns[(rank + 1) % n];
         p.attach();
         if (member) {
-          p.enableLLRecord();
-          if (!p.llRecord) {
+          if (simpleGroup) p.enableSimpleRecord();
+          else p.enableLLRecord();
+          if (!p.llRecord && !p.simpleRecord) {
             sh.fail(nexrInternalError);
             return;
           }
@@ -1256,6 +1296,36 @@ NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t c, int on) {
       c->cfg.memMode != nexrRingDeviceMemory)
     return nexrInvalidUsage;
   c->llGroup = on != 0;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrRingCommSetSimpleGroup(nexrRingComm_t c, int on) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer || c->proto != nexrRingProtoSimple || c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
+  if (on) {  // the first switch-on makes every ring connection's tail and head blocks, zeroed, and the
+             // status word the group launches report a timeout in (SIMPLE communicators have none otherwise)
+    DeviceGuard dg(c->needHip);
+    if (!c->status.empty() && !c->status[0]) {
+      if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+      const nexrResult_t res = allocStatus(c, &c->status[0]);
+      if (res != nexrSuccess) return res;
+    }
+    const int nCh = 1 + (int)c->channels.size();
+    for (int k = 0; k < nCh; k++)
+      for (Conn* q : channelComm(c, k)->conns) {
+        if (!q || q->simpleTail) continue;
+        void* p = nullptr;
+        if (hipSetDevice(q->device) != hipSuccess || hipMalloc(&p, 2 * NEXR_SIMPLE_CREDIT_BYTES) != hipSuccess)
+          return nexrUnhandledCudaError;
+        if (hipMemset(p, 0, 2 * NEXR_SIMPLE_CREDIT_BYTES) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+          (void)hipFree(p);
+          return nexrUnhandledCudaError;
+        }
+        q->simpleTail = (uint64_t*)p;
+        q->simpleHead = (uint64_t*)((char*)p + NEXR_SIMPLE_CREDIT_BYTES);
+      }
+  }
+  c->simpleGroup = on != 0;
   return nexrSuccess;
 }
 

@@ -21,6 +21,7 @@ EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
                     "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
+                    "nexrRingCommSetSimpleGroup",
                     "nexrRingCommSetLLFlagRule",
                     "nexrRingCommGetLLCleanup", "nexrRingCommDestroy", "nexrPeerRingCommCreate",
                     "nexrPeerRingAllReduce", "nexrPeerRingReduceScatter", "nexrPeerRingAllGather",
@@ -72,6 +73,7 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommSetLLGroup.argtypes = [vp, i32]
+    L.nexrRingCommSetSimpleGroup.argtypes = [vp, i32]
     L.nexrRingCommSetLLFlagRule.argtypes = [vp, ctypes.POINTER(LLFlagRule)]
     L.nexrRingCommGetLLCleanup.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.nexrPeerRingCommCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(PeerRingConfig)]
@@ -229,7 +231,7 @@ class RingComm:
 
     def queued(self) -> int:
         """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 3 group launches on
-        one stream (set_ll_group), 2 runs on the device with device credits, 1 queued launches,
+        one stream (set_ll_group; set_simple_group for SIMPLE), 2 runs on the device with device credits, 1 queued launches,
         0 host-sequenced (LL steps need every rank on one GPU and device memory for 1, 2 or 3; 1 and 2
         also a hardware queue per rank stream). While set_ll_group is on, a tree_all_reduce reports here
         too: 3 when it ran as group launches, 0 when it fell back."""
@@ -250,6 +252,16 @@ class RingComm:
         above 32 members over all channels, or when the grid is not resident at once. With the option off
         a tree call leaves queued() as it was."""
         _check(self._L.nexrRingCommSetLLGroup(self._h, 1 if on else 0), "nexrRingCommSetLLGroup")
+
+    def set_simple_group(self, on: bool) -> None:
+        """Opt in to (or out of) SIMPLE group launches (nexrRingCommSetSimpleGroup): the slices of every rank
+        and channel of a ring collective as step lists in the same launches on one stream
+        (nexrReduceCopySimpleStepsGroup), tails and heads in device memory, queued() == 3. Between
+        collectives; InvalidUsage unless the communicator is thread-rank, SIMPLE and device-memory. A
+        collective falls back to host-sequenced steps (queued() == 0) when the ranks span GPUs, with a
+        caller's fn, the hipStreamSynchronize step wait, more than 32 members, or a grid that is not resident
+        at once even at one workgroup per member. tree_all_reduce does not take it."""
+        _check(self._L.nexrRingCommSetSimpleGroup(self._h, 1 if on else 0), "nexrRingCommSetSimpleGroup")
 
     def set_ll_flag_rule(self, flag_max: int, clean_mask: int) -> None:
         """The LL flag rule of every channel (nexrRingCommSetLLFlagRule): (0, 0x7ffffff8) is the production
