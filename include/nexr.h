@@ -37,7 +37,8 @@ extern "C" {
 /* 0.3.0 also covers the LL flag rule (nexrLLFlagRule, nexrReduceCopyLLStepsRule, nexrLLCleanSlot) and the
  * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup, nexrReduceCopyLL128StepsGroup
  * for LL128 step lists, and nexrSimpleGroupWorkspaceBytes / nexrReduceCopySimpleStepsGroup with
- * nexrSimpleConnSet for SIMPLE ones): additions only, no existing entry point or struct layout changed, so the version
+ * nexrSimpleConnSet for SIMPLE ones, nexrSimpleGroupDirectWorkspaceBytes / nexrReduceCopySimpleStepsGroupDirect
+ * with nexrSimpleDirectSet for their DirectWrite form): additions only, no existing entry point or struct layout changed, so the version
  * stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
@@ -580,6 +581,53 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSim
                                                      int devRedOp, uint64_t redOpArg, int workgroupsPerMember,
                                                      uint32_t* status, uint32_t timeoutUs, void* workspace,
                                                      size_t workspaceBytes, nexrStream_t stream);
+
+/*
+ * nexrReduceCopySimpleStepsGroupDirect — nexrReduceCopySimpleStepsGroup with DirectWrite connections
+ * (reference src/device/prims_simple.h:148-164, :258-269): a sender writes into the RECEIVING member's output
+ * buffer at the record's dstIx instead of a FIFO slot, and the receiver reads its own output there. `direct`
+ * is one nexrSimpleDirectSet per member, or NULL; with NULL the call IS nexrReduceCopySimpleStepsGroup (the
+ * same kernels, tables and workspace size).
+ *
+ * A record permits direct ends in nexrLLStep.pad[0] (every other call ignores the pad bytes):
+ * NEXR_SIMPLE_DIRECT_RECV is DirectRecv1, NEXR_SIMPLE_DIRECT_SEND DirectSend1 of the reference's genericOp.
+ * An end is direct only when the record's bit AND the connection's entry say so. Per record, on a member
+ * with output O and element size `size`:
+ *   - send connection j with sendDirect[j] != NULL: the destination is sendDirect[j] + dstIx * size, at any
+ *     alignment, instead of the slot (dstIx is read also when dstBuf == -1);
+ *   - the receive connection with recvDirect[0] != 0: the source is O + dstIx * size instead of the slot. Only
+ *     one receive may be direct: a member with any recvDirect set needs nRecv == 1 and a non-NULL output
+ *     (else nexrInvalidArgument);
+ *   - a direct receive with srcBuf == -1 and dstBuf == 1 has its source and its user destination at the same
+ *     bytes: nothing is stored to O. If the record sends, that one source is copied to the send destinations
+ *     bit for bit (no pre-op, no post-op); if not, the record moves no data: it waits, advances and posts;
+ *   - everything else is nexrReduceCopySimpleStepsGroup's: the operand order [user src, receive...], the
+ *     pre-op, the post-op, the reduction semantics. The bytes every member ends with equal the FIFO path's.
+ * Tiles, credits, the timeout and the status word are unchanged (tile t of a slice counts from the slice's
+ * start address, which both ends compute alike); the tail and head words after a direct run equal those of
+ * the same lists through FIFOs, and a direct slice writes no FIFO byte.
+ *
+ * Host side, before any device call: the checks of nexrReduceCopySimpleStepsGroup; a connection between two
+ * members (one's sendFifo is the other's recvFifo) must be direct on both ends or on neither, with
+ * sendDirect equal to the receiver's output (else nexrInvalidArgument); one-ended connections are trusted,
+ * as is the room behind sendDirect. For the launch cuts a direct source is a read of the member's output at
+ * dstIx; a direct destination belongs to no member (the connection's credits order it). The workspace is
+ * sized by nexrSimpleGroupDirectWorkspaceBytes when direct != NULL.
+ */
+#define NEXR_SIMPLE_DIRECT_RECV 1u
+#define NEXR_SIMPLE_DIRECT_SEND 2u
+typedef struct {
+  void*   sendDirect[NEXR_LL_STEPS_MAX_PEERS]; /* element 0 of the RECEIVING member's output buffer; NULL: this connection uses its FIFO */
+  uint8_t recvDirect[NEXR_LL_STEPS_MAX_PEERS]; /* 1: the sender of receive connection i writes into THIS member's output */
+  uint8_t pad[5];
+} nexrSimpleDirectSet;
+NEXR_API nexrResult_t nexrSimpleGroupDirectWorkspaceBytes(int nMembers, size_t* bytes);
+NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const nexrSimpleConnSet* conns,
+                                                           const nexrLLStep* const* steps, const int* nSteps,
+                                                           int datatype, int devRedOp, uint64_t redOpArg,
+                                                           int workgroupsPerMember, const nexrSimpleDirectSet* direct,
+                                                           uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                           size_t workspaceBytes, nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

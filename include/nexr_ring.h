@@ -200,6 +200,37 @@ NEXR_API nexrResult_t nexrRingCommSetLLGroup(nexrRingComm_t comm, int on);
  * nexrInvalidUsage unless the communicator has thread ranks, the SIMPLE protocol and device memory. */
 NEXR_API nexrResult_t nexrRingCommSetSimpleGroup(nexrRingComm_t comm, int on);
 
+/* DirectWrite for the SIMPLE ring collectives (reference src/device/prims_simple.h:148-164, :258-269). With
+ * on != 0 the caller states that the user buffers it will pass are registered (the reference's regUsed): a
+ * sender then writes each slice into the NEXT rank's recvbuff at the slice's output offset instead of a FIFO
+ * slot, the receiver reads it from its own recvbuff, a copy whose source is its destination is skipped, and
+ * the last step of every chunk (directRecv) moves no data: it only waits and posts. Thread ranks know every
+ * buffer when the call starts, so nothing is exchanged. Host or device memory both qualify. A collective runs
+ * direct where the reference registers (src/register/coll_reg.cc:177-178): AllGather and Broadcast always,
+ * in place or not; AllReduce only when every rank is out of place (its reduce-scatter half uses the
+ * recvbuffs as scratch); ReduceScatter and Reduce never. Device-memory ranks on several GPUs fall back to
+ * FIFOs too, and nexrTreeAllReduce ignores the option. A call that is not eligible runs exactly as without
+ * the option; the results are bit-identical either way. Direct and FIFO slices share the step counters, so
+ * the option may be toggled between collectives, and it combines with nexrRingCommSetSimpleGroup (the
+ * records then carry the direct bits and the group call is nexrReduceCopySimpleStepsGroupDirect,
+ * include/nexr.h). Host-sequenced, a skipped copy is one fn call with one source and the send destinations,
+ * and a directRecv slice makes no fn call. Derived: 5n - 4 against 6n - 4 memory accesses per chunk element
+ * of an n-rank all-reduce, 2n - 1 against 3n - 1 for an out-of-place all-gather. Measured on one MI355X, 4 MiB
+ * of fp32 per rank, medians of 30 calls, two runs each (profiles/r11a_simple_direct_probe.json, DESIGN §8.3;
+ * a setting's two runs differ by up to 15-25 %): host-sequenced, direct against FIFOs, all-reduce at 2 / 4 / 8
+ * ranks 0.13-0.16 / 0.34-0.37 / 1.02-1.03 ms against 0.15-0.18 / 0.38-0.40 / 1.06-1.08, all-gather at 2 / 8
+ * ranks 0.12-0.13 / 0.63-0.66 against 0.14-0.15 / 0.67-0.68, broadcast 0.15-0.17 / 0.39 against 0.19 /
+ * 0.38-0.40; in group launches direct is level with FIFOs within that spread and SLOWER for the broadcast at
+ * 2 ranks (0.15-0.16 against 0.13-0.14) and the all-reduce at 4 and 8 ranks (0.36-0.38 against 0.35, 0.83-0.88
+ * against 0.77-0.85). Opt-in.
+ *
+ * nexrInvalidUsage unless the communicator has thread ranks and the SIMPLE protocol. */
+NEXR_API nexrResult_t nexrRingCommSetDirect(nexrRingComm_t comm, int on);
+
+/* The last thread-rank ring collective's send slices of either kind over all ranks and channels (zero-size
+ * slices included): *directSlices went into a peer's recvbuff, *fifoSlices into a FIFO slot. */
+NEXR_API nexrResult_t nexrRingCommGetDirect(nexrRingComm_t comm, uint64_t* directSlices, uint64_t* fifoSlices);
+
 /* The LL flag rule of this communicator (nexrLLFlagRule, include/nexr.h; NULL or {0, 0x7ffffff8}: the
  * production rule, the default; {0x100, 0x78}: the reference's TEST_LL_CLEANUP), for every channel. Its LL
  * steps take their flags from it, and on a cleaning send step rewrite the rest of the step's slot as

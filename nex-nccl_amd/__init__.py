@@ -88,6 +88,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrReduceCopyLLStepsRule",
                "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrReduceCopyLL128StepsGroup",
                "nexrSimpleGroupWorkspaceBytes", "nexrReduceCopySimpleStepsGroup",
+               "nexrSimpleGroupDirectWorkspaceBytes", "nexrReduceCopySimpleStepsGroupDirect",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -169,6 +170,15 @@ class SimpleConnSet(ctypes.Structure):
                 ("sendFifo", ctypes.c_void_p * 3), ("sendTail", ctypes.c_void_p * 3),
                 ("sendHead", ctypes.c_void_p * 3), ("sendStep", ctypes.c_uint64 * 3),
                 ("slotBytes", ctypes.c_uint64), ("nSlots", ctypes.c_uint32), ("stepPerSlice", ctypes.c_uint32)]
+
+
+SIMPLE_DIRECT_RECV = 1  # NEXR_SIMPLE_DIRECT_RECV: LLStep.pad[0] bit, DirectRecv1 of genericOp
+SIMPLE_DIRECT_SEND = 2  # NEXR_SIMPLE_DIRECT_SEND: DirectSend1
+
+
+class SimpleDirectSet(ctypes.Structure):
+    """Mirror of nexrSimpleDirectSet (include/nexr.h): a member's direct ends (32 bytes)."""
+    _fields_ = [("sendDirect", ctypes.c_void_p * 3), ("recvDirect", ctypes.c_uint8 * 3), ("pad", ctypes.c_uint8 * 5)]
 
 
 class LLFlagRule(ctypes.Structure):
@@ -302,6 +312,11 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopySimpleStepsGroup.argtypes = [i32, P(SimpleConnSet), P(P(LLStep)), P(i32), i32, i32, u64, i32, vp,
                                                  ctypes.c_uint32, vp, sz, vp]
     L.nexrReduceCopySimpleStepsGroup.restype = i32
+    L.nexrSimpleGroupDirectWorkspaceBytes.argtypes = [i32, P(sz)]
+    L.nexrSimpleGroupDirectWorkspaceBytes.restype = i32
+    L.nexrReduceCopySimpleStepsGroupDirect.argtypes = [i32, P(SimpleConnSet), P(P(LLStep)), P(i32), i32, i32, u64, i32,
+                                                       P(SimpleDirectSet), vp, ctypes.c_uint32, vp, sz, vp]
+    L.nexrReduceCopySimpleStepsGroupDirect.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -537,9 +552,11 @@ def reduce_copy_ll128(src: int, recv_wire: Sequence[int], recv_flags: Sequence[i
 
 
 def ll_step(src_buf: int = -1, src_ix: int = 0, dst_buf: int = -1, dst_ix: int = 0, n_elts: int = 0,
-            recv: bool = False, send: bool = False, post_op: bool = False) -> LLStep:
-    """One step of a run (buffers: 0 input, 1 output, -1 none)."""
+            recv: bool = False, send: bool = False, post_op: bool = False, direct: int = 0) -> LLStep:
+    """One step of a run (buffers: 0 input, 1 output, -1 none). direct: SIMPLE_DIRECT_RECV | SIMPLE_DIRECT_SEND,
+    the ends a SIMPLE record permits to be direct (pad[0]; read by reduce_copy_simple_steps_group_direct only)."""
     s = LLStep()
+    s.pad[0] = int(direct)
     s.srcIx, s.dstIx, s.nElts = int(src_ix), int(dst_ix), int(n_elts)
     s.recv, s.send, s.srcBuf, s.dstBuf, s.postOp = int(bool(recv)), int(bool(send)), int(src_buf), int(dst_buf), \
         int(bool(post_op))
@@ -678,6 +695,60 @@ def reduce_copy_simple_steps_group(members: Sequence[tuple], slot_bytes: int, da
                                               ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None, int(ws_bytes),
                                               ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrReduceCopySimpleStepsGroup")
+    return keep
+
+
+def simple_direct_set(send_direct: Sequence[int] = (), recv_direct: Sequence[int] = ()) -> SimpleDirectSet:
+    """A SimpleDirectSet: per send connection the receiving member's output pointer (0: FIFO), per receive
+    connection whether its sender writes into this member's output."""
+    d = SimpleDirectSet()
+    for j, ptr in enumerate(send_direct):
+        d.sendDirect[j] = int(ptr) or None
+    for i, on in enumerate(recv_direct):
+        d.recvDirect[i] = 1 if on else 0
+    return d
+
+
+def simple_group_direct_workspace_bytes(n_members: int, n_launches: int = LL_GROUP_LAUNCHES) -> int:
+    """simple_group_workspace_bytes for reduce_copy_simple_steps_group_direct with direct sets (its table
+    entries are larger; nexrSimpleGroupDirectWorkspaceBytes)."""
+    b = ctypes.c_size_t(0)
+    _check(lib().nexrSimpleGroupDirectWorkspaceBytes(int(n_members), ctypes.byref(b)),
+           "nexrSimpleGroupDirectWorkspaceBytes")
+    return b.value // LL_GROUP_LAUNCHES * max(1, int(n_launches))
+
+
+def reduce_copy_simple_steps_group_direct(members: Sequence[tuple], direct, slot_bytes: int, datatype: int,
+                                          dev_red_op: int, red_op_arg: int = 0, n_slots: int = 8,
+                                          step_per_slice: int = 1, workgroups_per_member: int = 0, status: int = 0,
+                                          timeout_us: int = 0, stream: int = 0, workspace=None):
+    """reduce_copy_simple_steps_group with DirectWrite connections (nexrReduceCopySimpleStepsGroupDirect).
+    direct: None (the call is then the FIFO one), or per member a SimpleDirectSet or a (send_direct,
+    recv_direct) pair as simple_direct_set takes them. The records' direct bits come from ll_step(direct=...)."""
+    n = len(members)
+    cs = (SimpleConnSet * max(1, n))(*[simple_conn_set(m[0], m[1], m[2], m[3], slot_bytes, n_slots, step_per_slice)
+                                       for m in members])
+    arrs = [(LLStep * max(1, len(m[4])))(*m[4]) for m in members]
+    ptrs = (ctypes.POINTER(LLStep) * max(1, n))(*[ctypes.cast(a, ctypes.POINTER(LLStep)) for a in arrs])
+    counts = (ctypes.c_int * max(1, n))(*[len(m[4]) for m in members])
+    ds = None
+    if direct is not None:
+        ds = (SimpleDirectSet * max(1, n))(*[d if isinstance(d, SimpleDirectSet) else simple_direct_set(*d)
+                                             for d in direct])
+    keep = None
+    if workspace is None and 1 <= n <= LL_GROUP_MAX_MEMBERS and any(len(m[4]) for m in members):
+        import torch
+        longest = max([len(m[4]) for m in members] + [1])
+        size = simple_group_direct_workspace_bytes if direct is not None else simple_group_workspace_bytes
+        keep = torch.empty(size(n, longest), dtype=torch.uint8, device="cuda")
+        workspace = (keep.data_ptr(), keep.numel())
+    ws_ptr, ws_bytes = workspace if workspace is not None else (0, 0)
+    rc = lib().nexrReduceCopySimpleStepsGroupDirect(n, cs, ptrs, counts, int(datatype), int(dev_red_op),
+                                                    int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, int(workgroups_per_member),
+                                                    ds, ctypes.c_void_p(int(status)) if status else None,
+                                                    int(timeout_us), ctypes.c_void_p(int(ws_ptr)) if ws_ptr else None,
+                                                    int(ws_bytes), ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrReduceCopySimpleStepsGroupDirect")
     return keep
 
 

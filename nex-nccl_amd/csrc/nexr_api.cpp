@@ -1669,11 +1669,13 @@ nexrResult_t llGroupResident(bool ll128, int dt, int op, int64_t* resident) {
 // connection's counters by `adv` (1, or SIMPLE's stepPerSlice) and a slot is free again nSlots steps later.
 // rule: the LL flag rule, whose cleaning steps end a launch (nullptr: none).
 extern "C++" {
-template <typename Params, typename ResidentFn, typename LaunchFn>
+// directRd(member, record): a further user range the record reads (a SIMPLE direct receive reads the member's
+// output at dstIx), end == 0 for none.
+template <typename Params, typename ResidentFn, typename LaunchFn, typename DirectRdFn>
 nexrResult_t stepsGroupPlan(int nMembers, std::vector<Params>& cur, const nexrLLStep* const* steps, const int* nSteps,
                             int maxSteps, size_t esz, uint64_t adv, uint64_t nSlots, const nexrLLFlagRule* rule, int G,
-                            ResidentFn residentFn, LaunchFn launchFn, void* workspace, size_t workspaceBytes,
-                            nexrStream_t stream) {
+                            ResidentFn residentFn, LaunchFn launchFn, DirectRdFn directRd, void* workspace,
+                            size_t workspaceBytes, nexrStream_t stream) {
   constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
   std::vector<Params> table;
   std::vector<std::vector<UserRange>> seen((size_t)nMembers);
@@ -1694,10 +1696,12 @@ nexrResult_t stepsGroupPlan(int nMembers, std::vector<Params>& cur, const nexrLL
   for (int k = 0; k < maxSteps; k++) {
     bool before = inLaunch == kLLStepsMax, cleans = false;
     std::vector<UserRange> rd((size_t)nMembers, UserRange{0, 0, false}), wr((size_t)nMembers, UserRange{0, 0, true});
+    std::vector<UserRange> rd2((size_t)nMembers, UserRange{0, 0, false});
     for (int m = 0; m < nMembers; m++) {
       if (k >= nSteps[m]) continue;
       const nexrLLStep& s = steps[m][k];
       const Params& cs = cur[(size_t)m];
+      rd2[(size_t)m] = directRd(m, s);
       if (s.nElts && s.srcBuf >= 0) {
         rd[(size_t)m].beg = (uintptr_t)(s.srcBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.srcIx * esz;
         rd[(size_t)m].end = rd[(size_t)m].beg + (uintptr_t)s.nElts * esz;
@@ -1707,6 +1711,7 @@ nexrResult_t stepsGroupPlan(int nMembers, std::vector<Params>& cur, const nexrLL
         wr[(size_t)m].end = wr[(size_t)m].beg + (uintptr_t)s.nElts * esz;
       }
       before = before || (rd[(size_t)m].end && rangesConflict(seen[(size_t)m], rd[(size_t)m])) ||
+               (rd2[(size_t)m].end && rangesConflict(seen[(size_t)m], rd2[(size_t)m])) ||
                (wr[(size_t)m].end && rangesConflict(seen[(size_t)m], wr[(size_t)m]));
     }
     if (before && inLaunch) {
@@ -1722,6 +1727,7 @@ nexrResult_t stepsGroupPlan(int nMembers, std::vector<Params>& cur, const nexrLL
       for (int q = 0; q < P.nSteps; q++) sent += P.step[q].send ? 1 : 0;
       P.step[P.nSteps++] = s;
       if (rd[(size_t)m].end) seen[(size_t)m].push_back(rd[(size_t)m]);
+      if (rd2[(size_t)m].end) seen[(size_t)m].push_back(rd2[(size_t)m]);
       if (wr[(size_t)m].end) seen[(size_t)m].push_back(wr[(size_t)m]);
       if constexpr (std::is_same<Params, LLStepsParams>::value) {
         if (s.send && rule)
@@ -1879,7 +1885,7 @@ nexrResult_t llStepsGroup(int nMembers, const nexrLLConnSet* conns, const nexrLL
         return ll128 ? launch_ll128_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream)
                      : launch_ll_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
       },
-      workspace, workspaceBytes, stream);
+      [](int, const nexrLLStep&) { return UserRange{0, 0, false}; }, workspace, workspaceBytes, stream);
 }
 }  // namespace
 
@@ -1915,19 +1921,20 @@ namespace {
 // 80 of them one fewer per CU than the occupancy query says; a surplus workgroup would queue until a
 // resident one exits, which a poll may be waiting for. So one is taken off the query's answer.
 // Test hook: NEXR_TEST_SIMPLE_GROUP_RESIDENT=k makes the next calls take k as that number (read per call).
-nexrResult_t simpleGroupResident(int dt, int op, int64_t* resident) {
+// direct: the kernel variant of nexrReduceCopySimpleStepsGroupDirect (the one that is launched is queried).
+nexrResult_t simpleGroupResident(bool direct, int dt, int op, int64_t* resident) {
   if (const char* e = getenv("NEXR_TEST_SIMPLE_GROUP_RESIDENT"))
     if (*e) {
       *resident = strtoll(e, nullptr, 10);
       return nexrSuccess;
     }
   constexpr int kDevs = 16;
-  static std::atomic<int64_t> cache[kDevs][nexrNumTypes][nexrNumDevRedOps];
+  static std::atomic<int64_t> cache[2][kDevs][nexrNumTypes][nexrNumDevRedOps];  // [FIFO-only, direct]
   int dev = 0;
   NEXR_HIP(hipGetDevice(&dev));
   const bool cached = dev >= 0 && dev < kDevs;
   if (cached) {
-    const int64_t v = cache[dev][dt][op].load(std::memory_order_relaxed);
+    const int64_t v = cache[direct][dev][dt][op].load(std::memory_order_relaxed);
     if (v > 0) {
       *resident = v;
       return nexrSuccess;
@@ -1935,20 +1942,20 @@ nexrResult_t simpleGroupResident(int dt, int op, int64_t* resident) {
   }
   int cus = 0, blocks = 0;
   NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  NEXR_HIP(simple_group_blocks_per_cu(dt, op, &blocks));
+  NEXR_HIP(direct ? simple_group_direct_blocks_per_cu(dt, op, &blocks) : simple_group_blocks_per_cu(dt, op, &blocks));
   if (blocks > 8) blocks = 8;
   if (blocks > 1) blocks--;
   *resident = (int64_t)blocks * cus;
-  if (cached && *resident > 0) cache[dev][dt][op].store(*resident, std::memory_order_relaxed);
+  if (cached && *resident > 0) cache[direct][dev][dt][op].store(*resident, std::memory_order_relaxed);
   return nexrSuccess;
 }
-}  // namespace
 
-NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns,
-                                                     const nexrLLStep* const* steps, const int* nSteps, int datatype,
-                                                     int devRedOp, uint64_t redOpArg, int workgroupsPerMember,
-                                                     uint32_t* status, uint32_t timeoutUs, void* workspace,
-                                                     size_t workspaceBytes, nexrStream_t stream) {
+// The host side of both SIMPLE group calls. direct == nullptr: nexrReduceCopySimpleStepsGroup, the FIFO-only
+// kernels and their table entry; else one nexrSimpleDirectSet per member, the direct kernels and theirs.
+nexrResult_t simpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns, const nexrLLStep* const* steps,
+                              const int* nSteps, int datatype, int devRedOp, uint64_t redOpArg,
+                              int workgroupsPerMember, const nexrSimpleDirectSet* direct, uint32_t* status,
+                              uint32_t timeoutUs, void* workspace, size_t workspaceBytes, nexrStream_t stream) {
   constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
   if (nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || !conns || !steps || !nSteps) return nexrInvalidArgument;
   if (workgroupsPerMember < 0 || workgroupsPerMember > NEXR_SIMPLE_GROUP_MAX_GRID) return nexrInvalidArgument;
@@ -1996,17 +2003,34 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSim
     }
     maxSteps = std::max(maxSteps, nSteps[m]);
   }
+  if (direct) {
+    // Only one receive may be direct (prims_simple.h:262), and its source is the member's output.
+    for (int m = 0; m < nMembers; m++) {
+      bool any = false;
+      for (int i = 0; i < MP; i++) any = any || direct[m].recvDirect[i] != 0;
+      if (any && (conns[m].nRecv != 1 || !direct[m].recvDirect[0] || !conns[m].output)) return nexrInvalidArgument;
+    }
+    // A connection between two members is direct on both ends or on neither, into the receiver's output.
+    for (int m = 0; m < nMembers; m++)
+      for (int j = 0; j < conns[m].nSend; j++)
+        for (int r = 0; r < nMembers; r++)
+          for (int i = 0; i < conns[r].nRecv; i++) {
+            if (conns[r].recvFifo[i] != conns[m].sendFifo[j]) continue;
+            const void* sd = direct[m].sendDirect[j];
+            if ((sd != nullptr) != (direct[r].recvDirect[i] != 0)) return nexrInvalidArgument;
+            if (sd && sd != conns[r].output) return nexrInvalidArgument;
+          }
+  }
   if (maxSteps == 0) return nexrSuccess;
   if (!workspace || ((uintptr_t)workspace & 7)) return nexrInvalidArgument;
   const uint64_t sps = conns[0].stepPerSlice;
   int srcIsInput = 1, postOp = 1, firstWins = 0;
   llSemantics(&datatype, &devRedOp, &srcIsInput, &postOp, &firstWins);  // fork: the dispatch type; shipped: source 0
-
-  std::vector<SimpleStepsParams> cur((size_t)nMembers);
-  for (int m = 0; m < nMembers; m++) {
-    const nexrSimpleConnSet& cs = conns[m];
-    SimpleStepsParams& P = cur[(size_t)m];
-    memset(&P, 0, sizeof(P));
+  // A workgroup per 4 KiB tile of a full slice unless the caller says how many.
+  const uint64_t sliceTiles = (conns[0].slotBytes * sps + kSimpleTileBytes - 1) / kSimpleTileBytes;
+  const int G = workgroupsPerMember ? workgroupsPerMember
+                                    : (int)(sliceTiles > (uint64_t)kSimpleMaxGrid ? kSimpleMaxGrid : sliceTiles);
+  auto fill = [&](SimpleStepsParams& P, const nexrSimpleConnSet& cs) {
     P.input = (const char*)cs.input;
     P.output = (char*)cs.output;
     for (int i = 0; i < MP; i++) {
@@ -2028,18 +2052,70 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSim
     P.nSlots = (int)cs.nSlots;
     P.firstWins = firstWins;
     P.stepPerSlice = (int)cs.stepPerSlice;
+  };
+  if (direct) {
+    std::vector<SimpleDirectParams> cur((size_t)nMembers);
+    for (int m = 0; m < nMembers; m++) {
+      SimpleDirectParams& P = cur[(size_t)m];
+      memset((void*)&P, 0, sizeof(P));
+      fill(P, conns[m]);
+      for (int j = 0; j < conns[m].nSend; j++) P.sendDirect[j] = (char*)direct[m].sendDirect[j];
+      P.recvDirect = direct[m].recvDirect[0] ? 1 : 0;
+    }
+    return stepsGroupPlan(
+        nMembers, cur, steps, nSteps, maxSteps, esz, sps, conns[0].nSlots, nullptr, G,
+        [&](int64_t* resident) { return simpleGroupResident(true, datatype, devRedOp, resident); },
+        [&](const SimpleDirectParams* entries) {
+          return launch_simple_group_direct(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
+        },
+        [&](int m, const nexrLLStep& st) {  // a direct source: the member's output at dstIx
+          UserRange rd{0, 0, false};
+          if (st.nElts && st.recv && (st.pad[0] & NEXR_SIMPLE_DIRECT_RECV) && direct[m].recvDirect[0]) {
+            rd.beg = (uintptr_t)conns[m].output + (uintptr_t)st.dstIx * esz;
+            rd.end = rd.beg + (uintptr_t)st.nElts * esz;
+          }
+          return rd;
+        },
+        workspace, workspaceBytes, stream);
   }
-  // A workgroup per 4 KiB tile of a full slice unless the caller says how many.
-  const uint64_t sliceTiles = (conns[0].slotBytes * sps + kSimpleTileBytes - 1) / kSimpleTileBytes;
-  const int G = workgroupsPerMember ? workgroupsPerMember
-                                    : (int)(sliceTiles > (uint64_t)kSimpleMaxGrid ? kSimpleMaxGrid : sliceTiles);
+  std::vector<SimpleStepsParams> cur((size_t)nMembers);
+  for (int m = 0; m < nMembers; m++) {
+    memset(&cur[(size_t)m], 0, sizeof(SimpleStepsParams));
+    fill(cur[(size_t)m], conns[m]);
+  }
   return stepsGroupPlan(
       nMembers, cur, steps, nSteps, maxSteps, esz, sps, conns[0].nSlots, nullptr, G,
-      [&](int64_t* resident) { return simpleGroupResident(datatype, devRedOp, resident); },
+      [&](int64_t* resident) { return simpleGroupResident(false, datatype, devRedOp, resident); },
       [&](const SimpleStepsParams* entries) {
         return launch_simple_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
       },
-      workspace, workspaceBytes, stream);
+      [](int, const nexrLLStep&) { return UserRange{0, 0, false}; }, workspace, workspaceBytes, stream);
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns,
+                                                     const nexrLLStep* const* steps, const int* nSteps, int datatype,
+                                                     int devRedOp, uint64_t redOpArg, int workgroupsPerMember,
+                                                     uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                     size_t workspaceBytes, nexrStream_t stream) {
+  return simpleStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, workgroupsPerMember, nullptr,
+                          status, timeoutUs, workspace, workspaceBytes, stream);
+}
+
+NEXR_API nexrResult_t nexrSimpleGroupDirectWorkspaceBytes(int nMembers, size_t* bytes) {
+  if (!bytes || nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS) return nexrInvalidArgument;
+  *bytes = (size_t)nMembers * sizeof(SimpleDirectParams) * NEXR_LL_GROUP_LAUNCHES;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const nexrSimpleConnSet* conns,
+                                                           const nexrLLStep* const* steps, const int* nSteps,
+                                                           int datatype, int devRedOp, uint64_t redOpArg,
+                                                           int workgroupsPerMember, const nexrSimpleDirectSet* direct,
+                                                           uint32_t* status, uint32_t timeoutUs, void* workspace,
+                                                           size_t workspaceBytes, nexrStream_t stream) {
+  return simpleStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, workgroupsPerMember, direct,
+                          status, timeoutUs, workspace, workspaceBytes, stream);
 }
 
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,

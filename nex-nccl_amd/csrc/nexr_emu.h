@@ -200,6 +200,11 @@ struct nexrRingComm {
   // the first group collective on the ranks' GPU, grown when a collective needs more launches).
   bool llGroup = false;
   bool simpleGroup = false;  // nexrRingCommSetSimpleGroup (SIMPLE communicators; the same workspace)
+  // nexrRingCommSetDirect: the caller's statement that the user buffers it passes are registered (the
+  // reference's regUsed), and the last ring collective's send slices of either kind over all ranks and
+  // channels (nexrRingCommGetDirect; counted on the top-level communicator).
+  bool direct = false;
+  std::atomic<uint64_t> directSlices{0}, fifoSlices{0};
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;
@@ -494,6 +499,23 @@ struct Prims {
   // SIMPLE group launches (nexrRingCommSetSimpleGroup): genericOp records its slices instead of running
   // them (no waits, no launches, the counters advance); the calling thread launches every member's list.
   bool simpleRecord = false;
+  // DirectWrite (nexrRingCommSetDirect; prims_simple.h:148-164): this collective's user buffers are
+  // registered, so a send whose record permits it (DirectSend1) goes into the peer's output at dstIx,
+  // sendDirect[i] being element 0 of the output of send peer i, and the one receive connection's source (with
+  // DirectRecv1) is this rank's own output at dstIx. Thread ranks know every buffer when the call starts: the
+  // pointers are set before the rank threads run, no ptrExchange is needed.
+  bool directOn = false;
+  char* sendDirect[kMaxArity] = {};
+  std::atomic<uint64_t>* directSlices = nullptr;  // the communicator's counters (nullable)
+  std::atomic<uint64_t>* fifoSlices = nullptr;
+  nexrSimpleDirectSet simpleDirectSet() const {
+    nexrSimpleDirectSet ds;
+    memset(&ds, 0, sizeof(ds));
+    if (!directOn) return ds;
+    for (int i = 0; i < nSend; i++) ds.sendDirect[i] = sendDirect[i];
+    ds.recvDirect[0] = nRecv == 1 ? 1 : 0;
+    return ds;
+  }
   void enableSimpleRecord() {
     if (proto != nexrRingProtoSimple || !device || !c->stepWaitWord) return;
     if (nRecv > NEXR_LL_STEPS_MAX_PEERS || nSend > NEXR_LL_STEPS_MAX_PEERS) return;
@@ -641,12 +663,17 @@ struct Prims {
     }
   }
 
-  // genericOp<DirectRecv=0, DirectSend=0, Recv, Send, SrcBuf, DstBuf> (prims_simple.h:190-330),
-  // with the non-direct FIFO pointers (waitPeer :150-164 default branch). srcs = [user src, recv
-  // peers...], dsts = [user dst, send peers...] (:131-132, :238-242).
+  // genericOp<DirectRecv1, DirectSend1, Recv, Send, SrcBuf, DstBuf> (prims_simple.h:190-330). srcs = [user
+  // src, recv peers...], dsts = [user dst, send peers...] (:131-132, :238-242). Without directOn the peer
+  // pointers are the FIFO slots (waitPeer :150-164 default branch) whatever directBits says (bit 0
+  // DirectRecv1, bit 1 DirectSend1); with it they are the DirectWrite ones (:148-150, :159-160), and a direct
+  // receive whose source is its own destination skips that copy (:258-269).
   bool genericOp(bool Recv, bool Send, int srcBuf, int dstBuf, int64_t srcIx, int64_t dstIx, int64_t nelem,
-                 bool postOp) {
+                 bool postOp, int directBits = 0) {
     const int nr = Recv ? nRecv : 0, ns = Send ? nSend : 0;
+    const bool dRecv = directOn && (directBits & NEXR_SIMPLE_DIRECT_RECV) && nr == 1;
+    const bool dSend = directOn && (directBits & NEXR_SIMPLE_DIRECT_SEND) && ns > 0;
+    const bool skip = dRecv && srcBuf == kNone && dstBuf == kOutput;  // srcs[0] == dsts[0]
     nelem = nelem < 0 ? 0 : nelem;
     int64_t sliceSize = stepSize * stepPerSlice;
     sliceSize = std::max(divUp(nelem, 16 * slicePerChunk) * 16, sliceSize / 32);
@@ -654,6 +681,7 @@ struct Prims {
     for (int slice = 0; slice < slicePerChunk; slice++) {
       sliceSize = std::min(sliceSize, nelem - offset);
       if (sliceSize < 0) sliceSize = 0;
+      if (ns > 0 && directSlices) (dSend ? directSlices : fifoSlices)->fetch_add((uint64_t)ns, std::memory_order_relaxed);
       if (simpleRecord) {  // no wait and no launch: the group launches' kernel waits and posts on the device
         if (sh->aborted()) {
           sh->fail(nexrRemoteError);
@@ -668,7 +696,8 @@ struct Prims {
         s.srcBuf = (int8_t)(srcBuf == kNone ? -1 : srcBuf);
         s.dstBuf = (int8_t)(dstBuf == kNone ? -1 : dstBuf);
         s.srcIx = srcBuf == kNone ? 0 : srcIx + offset;
-        s.dstIx = dstBuf == kNone ? 0 : dstIx + offset;
+        s.dstIx = dstBuf == kNone && !dRecv && !dSend ? 0 : dstIx + offset;  // a direct end reads it too
+        s.pad[0] = (uint8_t)((dRecv ? NEXR_SIMPLE_DIRECT_RECV : 0u) | (dSend ? NEXR_SIMPLE_DIRECT_SEND : 0u));
         s.nElts = (uint32_t)sliceSize;  // zero-size slices are recorded too: they advance and post
         s.recv = nr > 0;
         s.send = ns > 0;
@@ -687,20 +716,24 @@ struct Prims {
       for (int i = 0; i < nr; i++) {  // wait for the peer's data: tail >= step + StepPerSlice
         Conn* q = recv[i];
         if (!waitAtLeast(q->st->tail, q->recvStep + stepPerSlice)) return false;
-        srcs[k++] = q->fifo + (q->recvStep % kSteps) * slot(q);
+        srcs[k++] = dRecv ? userOutput + (dstIx + offset) * esz : q->fifo + (q->recvStep % kSteps) * slot(q);
       }
       for (int i = 0; i < ns; i++) {  // wait for credit: head + NCCL_STEPS >= step + StepPerSlice
         Conn* q = send[i];
         if (q->sendStep + stepPerSlice > (uint64_t)kSteps &&
             !waitAtLeast(q->st->head, q->sendStep + stepPerSlice - kSteps))
           return false;
-        dsts[m++] = q->fifo + (q->sendStep % kSteps) * slot(q);
+        dsts[m++] = dSend ? sendDirect[i] + (dstIx + offset) * esz : q->fifo + (q->sendStep % kSteps) * slot(q);
       }
+      // The skipped copy: the one source goes to the send destinations only, as bits (no pre-op, no post-op);
+      // a directRecv has none and makes no launch. It has waited, and posts below.
+      void* const* dstv = skip ? dsts + 1 : dsts;
+      if (skip) m--;
       if (sliceSize > 0 && k > 0 && m > 0) {
         // PreOpSrcs = SrcBuf != Input ? 0 : 1 (prims_simple.h:279-280); preOpArgs = redOpArgs.
         const int nPre = srcBuf == kInput ? 1 : 0;
-        nexrResult_t r = fn(k, srcs, m, dsts, (size_t)sliceSize, datatype, devOp, redOpArgs[0], nPre,
-                            nPre ? redOpArgs : nullptr, postOp ? 1 : 0, (nexrStream_t)stream);
+        nexrResult_t r = fn(k, srcs, m, dstv, (size_t)sliceSize, datatype, devOp, redOpArgs[0], nPre,
+                            nPre ? redOpArgs : nullptr, postOp && !skip ? 1 : 0, (nexrStream_t)stream);
         if (r == nexrSuccess && device) {
           if (!streamDone()) r = nexrUnhandledCudaError;  // data complete before the step is posted
         }
@@ -849,12 +882,32 @@ struct Prims {
     }
     return true;
   }
-  bool op(bool Recv, bool Send, int srcBuf, int dstBuf, int64_t srcIx, int64_t dstIx, int64_t n, bool postOp) {
+  bool op(bool Recv, bool Send, int srcBuf, int dstBuf, int64_t srcIx, int64_t dstIx, int64_t n, bool postOp,
+          int directBits = 0) {
     return proto != nexrRingProtoSimple ? genericOpLL(Recv, Send, srcBuf, dstBuf, srcIx, dstIx, n, postOp)
-                 : genericOp(Recv, Send, srcBuf, dstBuf, srcIx, dstIx, n, postOp);
+                 : genericOp(Recv, Send, srcBuf, dstBuf, srcIx, dstIx, n, postOp, directBits);
   }
-  // The primitives the schedules use (prims_simple.h:897-976; the direct* forms reduce to these
-  // without registered peer buffers).
+  // The primitives the schedules use (prims_simple.h:897-976). The direct* forms are the plain ones plus the
+  // template arguments that permit a direct end; without directOn (and under LL / LL128) they ARE the plain
+  // ones.
+  bool directSend(int64_t inpIx, int64_t outIx, int64_t n) {
+    return op(false, true, kInput, kNone, inpIx, outIx, n, false, NEXR_SIMPLE_DIRECT_SEND);
+  }
+  bool directCopySend(int64_t inpIx, int64_t outIx, int64_t n) {
+    return op(false, true, kInput, kOutput, inpIx, outIx, n, false, NEXR_SIMPLE_DIRECT_SEND);
+  }
+  bool directRecvReduceDirectSend(int64_t inpIx, int64_t outIx, int64_t n) {
+    return op(true, true, kInput, kNone, inpIx, outIx, n, false, NEXR_SIMPLE_DIRECT_RECV | NEXR_SIMPLE_DIRECT_SEND);
+  }
+  bool directRecvReduceCopyDirectSend(int64_t inpIx, int64_t outIx, int64_t n, bool postOp) {
+    return op(true, true, kInput, kOutput, inpIx, outIx, n, postOp, NEXR_SIMPLE_DIRECT_RECV | NEXR_SIMPLE_DIRECT_SEND);
+  }
+  bool directRecvCopyDirectSend(int64_t outIx, int64_t n) {
+    return op(true, true, kNone, kOutput, -1, outIx, n, false, NEXR_SIMPLE_DIRECT_RECV | NEXR_SIMPLE_DIRECT_SEND);
+  }
+  bool directRecv(int64_t outIx, int64_t n) {
+    return op(true, false, kNone, kOutput, -1, outIx, n, false, NEXR_SIMPLE_DIRECT_RECV);
+  }
   bool sendInput(int64_t inpIx, int64_t n) { return op(false, true, kInput, kNone, inpIx, -1, n, false); }
   bool copySend(int64_t inpIx, int64_t outIx, int64_t n) { return op(false, true, kInput, kOutput, inpIx, outIx, n, false); }
   bool sendFromOutput(int64_t outIx, int64_t n) { return op(false, true, kOutput, kNone, outIx, -1, n, false); }

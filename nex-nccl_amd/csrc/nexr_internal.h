@@ -176,6 +176,19 @@ static_assert(sizeof(SimpleStepsParams) % 8 == 0, "table entries stay 8-byte ali
 hipError_t launch_simple_group(int dt, int op, const SimpleStepsParams* table, int nMembers, int G, hipStream_t s);
 hipError_t simple_group_blocks_per_cu(int dt, int op, int* blocks);
 
+// The same with DirectWrite connections (nexrReduceCopySimpleStepsGroupDirect): a kernel variant of its own
+// (the FIFO-only kernels stay as they are) and a table entry that adds, per member, the peers' output
+// buffers of its direct send connections and whether its receive connection is direct.
+struct SimpleDirectParams : SimpleStepsParams {
+  char* sendDirect[NEXR_LL_STEPS_MAX_PEERS];  // nullptr: the connection uses its FIFO
+  int recvDirect;                             // receive connection 0 is direct (then nRecv == 1)
+  int pad;
+};
+static_assert(sizeof(SimpleDirectParams) % 8 == 0, "table entries stay 8-byte aligned");
+hipError_t launch_simple_group_direct(int dt, int op, const SimpleDirectParams* table, int nMembers, int G,
+                                      hipStream_t s);
+hipError_t simple_group_direct_blocks_per_cu(int dt, int op, int* blocks);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

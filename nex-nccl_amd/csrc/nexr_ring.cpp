@@ -190,23 +190,23 @@ void runRingAllReduce(Prims& p, int nranks, const ChannelPart& part) {
     int64_t offset, nelem;
     // step 0: push data to next GPU
     nelem = at(modRanks(ringIx + nranks - 1), &offset);
-    if (!p.sendInput(offset, nelem)) return;
+    if (!p.directSend(offset, offset, nelem)) return;
     // k-2 steps: reduce and copy to next GPU
     for (int j = 2; j < nranks; ++j) {
       nelem = at(modRanks(ringIx + nranks - j), &offset);
-      if (!p.recvReduceSend(offset, nelem)) return;
+      if (!p.directRecvReduceDirectSend(offset, offset, nelem)) return;
     }
     // step k-1: reduce this buffer and data -> final result, stored and pushed
     nelem = at(ringIx, &offset);
-    if (!p.recvReduceCopySend(offset, offset, nelem, /*postOp=*/true)) return;
+    if (!p.directRecvReduceCopyDirectSend(offset, offset, nelem, /*postOp=*/true)) return;
     // k-2 steps: copy to next GPU
     for (int j = 1; j < nranks - 1; ++j) {
       nelem = at(modRanks(ringIx + nranks - j), &offset);
-      if (!p.recvCopySend(offset, nelem)) return;
+      if (!p.directRecvCopyDirectSend(offset, nelem)) return;
     }
     // final copy from buffer to dest
     nelem = at(modRanks(ringIx + 1), &offset);
-    if (!p.recvOutput(offset, nelem)) return;
+    if (!p.directRecv(offset, nelem)) return;
   }
 }
 
@@ -237,14 +237,14 @@ void runRingAllGather(Prims& p, int nranks, int64_t count, const ChannelPart& pa
     int64_t offset = dataOffset + (int64_t)r * count;
     // in place when the input chunk already sits at its place in the output (:52-56)
     const bool inPlace = p.userInput + dataOffset * p.esz == p.userOutput + offset * p.esz;
-    if (!(inPlace ? p.sendInput(dataOffset, nelem) : p.copySend(dataOffset, offset, nelem))) return;
+    if (!(inPlace ? p.directSend(dataOffset, offset, nelem) : p.directCopySend(dataOffset, offset, nelem))) return;
     for (int j = 1; j < nranks - 1; ++j) {
       const int rankDest = (r + nranks - j) % nranks;
       offset = dataOffset + (int64_t)rankDest * count;
-      if (!p.recvCopySend(offset, nelem)) return;
+      if (!p.directRecvCopyDirectSend(offset, nelem)) return;
     }
     offset = dataOffset + (int64_t)((r + 1) % nranks) * count;
-    if (!p.recvOutput(offset, nelem)) return;
+    if (!p.directRecv(offset, nelem)) return;
   }
 }
 
@@ -269,9 +269,10 @@ void runRingBroadcast(Prims& p, int nranks, int root, const ChannelPart& part) {
     const int64_t offset = part.offset + elemOffset;
     const int64_t nelem = std::min(part.chunkCount, part.count - elemOffset);
     bool ok;
-    if (r == root) ok = p.userInput == p.userOutput ? p.sendInput(offset, nelem) : p.copySend(offset, offset, nelem);
-    else if (nextRank == root) ok = p.recvOutput(offset, nelem);
-    else ok = p.recvCopySend(offset, nelem);
+    if (r == root)
+      ok = p.userInput == p.userOutput ? p.directSend(offset, offset, nelem) : p.directCopySend(offset, offset, nelem);
+    else if (nextRank == root) ok = p.directRecv(offset, nelem);
+    else ok = p.directRecvCopyDirectSend(offset, nelem);
     if (!ok) return;
   }
 }
@@ -689,6 +690,7 @@ bool simpleGroupAllowed(const nexrRingComm* c, size_t nMembers) {
 struct GroupMember {
   nexrLLConnSet cs = {};
   nexrSimpleConnSet scs = {};  // SIMPLE members (Prims::enableSimpleRecord)
+  nexrSimpleDirectSet ds = {}; // their direct ends (Prims::directOn; all zero without)
   std::vector<nexrLLStep> steps;
   Conn* recv[kMaxArity] = {};
   int nRecv = 0;
@@ -697,7 +699,7 @@ struct GroupMember {
   // Takes what a recording Primitives collected (Prims::enableLLRecord), every connection of it.
   void take(Prims& p) {
     if (!p.run.empty()) {
-      if (p.simpleRecord) scs = p.simpleConnSet();
+      if (p.simpleRecord) scs = p.simpleConnSet(), ds = p.simpleDirectSet();
       else cs = p.connSet();
     }
     steps.swap(p.run);
@@ -711,10 +713,14 @@ struct GroupMember {
 // The recorded members as group launches on channel 0's first stream, one wait, then the host counters
 // (head / tail) as Prims::finishRun publishes them. nexrInvalidUsage from the group call (the grid is not
 // resident at once) comes back unchanged, with nothing launched: the caller falls back.
-nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int datatype, const nexrDevRedOpFull& red) {
+// direct: the members' records carry direct bits (a SIMPLE collective with nexrRingCommSetDirect): the call is
+// nexrReduceCopySimpleStepsGroupDirect with their nexrSimpleDirectSets and its own table size.
+nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int datatype, const nexrDevRedOpFull& red,
+                      bool direct = false) {
   const int n = (int)members.size();
   const bool simple = c->proto == nexrRingProtoSimple;
   std::vector<nexrSimpleConnSet> scs;
+  std::vector<nexrSimpleDirectSet> ds;
   std::vector<nexrLLConnSet> cs;
   std::vector<const nexrLLStep*> steps;
   std::vector<int> nSteps;
@@ -722,13 +728,16 @@ nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int da
   for (GroupMember& m : members) {
     cs.push_back(m.cs);
     scs.push_back(m.scs);
+    ds.push_back(m.ds);
     steps.push_back(m.steps.data());
     nSteps.push_back((int)m.steps.size());
     longest = std::max(longest, m.steps.size());
   }
   if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
   size_t perLaunch = 0;
-  nexrResult_t r = simple ? nexrSimpleGroupWorkspaceBytes(n, &perLaunch) : nexrLLGroupWorkspaceBytes(n, &perLaunch);
+  nexrResult_t r = simple && direct ? nexrSimpleGroupDirectWorkspaceBytes(n, &perLaunch)
+                   : simple         ? nexrSimpleGroupWorkspaceBytes(n, &perLaunch)
+                                    : nexrLLGroupWorkspaceBytes(n, &perLaunch);
   if (r != nexrSuccess) return r;
   perLaunch /= NEXR_LL_GROUP_LAUNCHES;
   hipStream_t stream = c->streams[0];
@@ -754,9 +763,10 @@ nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int da
       // is halved down to one workgroup per member before the collective gives the group up.
       int G = 0;
       for (;;) {
-        r = nexrReduceCopySimpleStepsGroup(n, scs.data(), steps.data(), nSteps.data(), datatype, red.op, red.scalarArg,
-                                           G, status, (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
-                                           (nexrStream_t)stream);
+        r = nexrReduceCopySimpleStepsGroupDirect(n, scs.data(), steps.data(), nSteps.data(), datatype, red.op,
+                                                 red.scalarArg, G, direct ? ds.data() : nullptr, status,
+                                                 (uint32_t)timeoutMs * 1000u, c->groupWs, c->groupWsBytes,
+                                                 (nexrStream_t)stream);
         if (r != nexrInvalidUsage || G == 1) break;
         if (G == 0) {
           const uint64_t tiles = (c->stepBytes * scs[0].stepPerSlice + 4095) / 4096;
@@ -825,6 +835,17 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
   std::vector<ChannelPart> parts = channelParts(c, (int64_t)count, esz, trafficPerByte);
   for (ChannelPart& part : parts) part.chunkCount = chunkElems(channelComm(c, part.channel), g, esz, false, 0);
   Shared sh;
+  // DirectWrite (nexrRingCommSetDirect), where the reference registers the user buffers (coll_reg.cc:177-178):
+  // AllGather and Broadcast always, AllReduce when every rank is out of place (the reduce-scatter half uses
+  // the outputs as scratch), ReduceScatter and Reduce never; and not for device memory on several GPUs.
+  bool direct = c->direct && c->proto == nexrRingProtoSimple &&
+                (coll == kAllGather || coll == kBroadcast || coll == kAllReduce);
+  for (int i = 0; direct && i < n; i++) {
+    if (coll == kAllReduce && sendbuffs[i] == recvbuffs[i]) direct = false;
+    if (c->cfg.memMode == nexrRingDeviceMemory && c->devices[i] != c->devices[0]) direct = false;
+  }
+  c->directSlices.store(0, std::memory_order_relaxed);
+  c->fifoSlices.store(0, std::memory_order_relaxed);
   const bool simpleGroup = tryGroup && simpleGroupAllowed(c, parts.size() * (size_t)n);
   const bool group = simpleGroup || (tryGroup && llGroupAllowed(c, parts.size() * (size_t)n));
   const bool llAsync = !group && llAsyncAllowed(c);
@@ -854,6 +875,10 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
         p.recv[p.nRecv++] = ck->conns[rank];
         p.send[p.nSend++] = ck->conns[(rank + 1) % n];
         p.attach();
+        p.directOn = direct;
+        p.sendDirect[0] = (char*)recvbuffs[(rank + 1) % n];
+        p.directSlices = &c->directSlices;
+        p.fifoSlices = &c->fifoSlices;
         if (member) {
           if (simpleGroup) p.enableSimpleRecord();
           else p.enableLLRecord();
@@ -886,7 +911,7 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
   members.erase(std::remove_if(members.begin(), members.end(), [](const GroupMember& m) { return m.steps.empty(); }),
                 members.end());
   if (members.empty()) return nexrSuccess;
-  r = runGroup(c, members, datatype, red);
+  r = runGroup(c, members, datatype, red, simpleGroup && direct);
   if (r == nexrInvalidUsage) {  // the grid does not fit the GPU at once: the usual mode, from the same counters
     size_t ix = 0, ch = 0;
     for (const ChannelPart& part : parts) {
@@ -1326,6 +1351,20 @@ NEXR_API nexrResult_t nexrRingCommSetSimpleGroup(nexrRingComm_t c, int on) {
       }
   }
   c->simpleGroup = on != 0;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrRingCommSetDirect(nexrRingComm_t c, int on) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer || c->proto != nexrRingProtoSimple) return nexrInvalidUsage;
+  c->direct = on != 0;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrRingCommGetDirect(nexrRingComm_t c, uint64_t* directSlices, uint64_t* fifoSlices) {
+  if (!c || !directSlices || !fifoSlices) return nexrInvalidArgument;
+  *directSlices = c->directSlices.load(std::memory_order_relaxed);
+  *fifoSlices = c->fifoSlices.load(std::memory_order_relaxed);
   return nexrSuccess;
 }
 

@@ -26,6 +26,10 @@
 // the same barrier); the sender's wave 0 polls it before the workgroup stores into the slot again.
 // A poll that times out (or finds the status word set) makes the whole workgroup leave, through the
 // verdict word: no wave is left at a barrier.
+//
+// DirectWrite (nexrReduceCopySimpleStepsGroupDirect; prims_simple.h:148-164, :258-269) is a second kernel,
+// reduce_copy_simple_group_direct_kernel, behind the first: the same waits, credits and posts, with a slice's
+// receive source and send destinations in user memory where the record and the connection say so.
 
 namespace nexr {
 
@@ -123,10 +127,16 @@ __device__ __forceinline__ u32x4 simple_fold(const SimpleStepArgs& a, bool hasSr
 // 16-byte accesses); slots are 16-byte aligned. The slice's last, partial pack (nBytes % 16 bytes) is left
 // to the lane that owns it, behind the loop: user bytes one at a time, the slot's pack loaded whole (it
 // lies inside the slot) and stored by bytes, so that a slot holds exactly the slice's bytes.
-template <int D, int OP, bool IsMin>
+//
+// Direct (nexrReduceCopySimpleStepsGroupDirect): a receive source or a send destination may be user memory
+// (the member's own output, a peer's output) in place of a slot, so those accesses are the unaligned ones too
+// and the last partial pack of a receive source is loaded by bytes: it no longer lies inside a slot.
+template <int D, int OP, bool IsMin, bool Direct = false>
 __device__ __forceinline__ void simple_tiles(const SimpleStepArgs& a, uint32_t w, uint32_t G, uint64_t nBytes,
                                              uint64_t nTiles) {
   constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  using RecvPack = typename std::conditional<Direct, g_cu32x4_a1, g_cu32x4>::type;
+  using SendPack = typename std::conditional<Direct, g_u32x4_a1, g_u32x4>::type;
   const bool hasSrc = a.src != nullptr;
   const bool canon = (hasSrc ? 1 : 0) + a.nFold >= 2 || (OP == nexrDevPreMulSum && a.preOp);
   const uint64_t fullBytes = nBytes & ~(uint64_t)15;
@@ -150,7 +160,7 @@ __device__ __forceinline__ void simple_tiles(const SimpleStepArgs& a, uint32_t w
 #pragma unroll
       for (int u = 0; u < kSimpleU; u++) {
         r[u][i] = (u32x4)0u;
-        if (i < a.nFold && valid[u]) r[u][i] = *(const g_cu32x4*)(a.recv[i] + off[u]);
+        if (i < a.nFold && valid[u]) r[u][i] = *(const RecvPack*)(a.recv[i] + off[u]);
       }
     }
 #pragma unroll
@@ -159,7 +169,7 @@ __device__ __forceinline__ void simple_tiles(const SimpleStepArgs& a, uint32_t w
       const u32x4 out = simple_fold<D, OP, IsMin>(a, hasSrc, canon, us[u], r[u]);
 #pragma unroll
       for (int j = 0; j < MP; j++)
-        if (j < a.nSend) *(g_u32x4*)(a.send[j] + off[u]) = out;
+        if (j < a.nSend) *(SendPack*)(a.send[j] + off[u]) = out;
       if (a.dst) *(g_u32x4_a1*)(a.dst + off[u]) = out;
     }
   }
@@ -172,7 +182,11 @@ __device__ __forceinline__ void simple_tiles(const SimpleStepArgs& a, uint32_t w
 #pragma unroll
       for (int i = 0; i < MP; i++) {
         r[i] = (u32x4)0u;
-        if (i < a.nFold) r[i] = *(const g_cu32x4*)(a.recv[i] + fullBytes);
+        if constexpr (Direct) {
+          if (i < a.nFold) r[i] = ld_bytes(a.recv[i] + fullBytes, rem);
+        } else {
+          if (i < a.nFold) r[i] = *(const g_cu32x4*)(a.recv[i] + fullBytes);
+        }
       }
       const u32x4 out = simple_fold<D, OP, IsMin>(a, hasSrc, canon, us, r);
 #pragma unroll
@@ -292,6 +306,142 @@ __global__ __launch_bounds__(kBlock) void reduce_copy_simple_group_kernel(const 
   }
 }
 
+// The kernel of nexrReduceCopySimpleStepsGroupDirect: reduce_copy_simple_group_kernel with DirectWrite ends.
+// A kernel of its own, so that the FIFO-only kernels keep their code: the waits, the credits, the barriers and
+// the posts are the same statements; what differs is where a slice's receive source and send destinations
+// point, and the slice that moves nothing.
+typedef const __attribute__((address_space(4))) SimpleDirectParams c_SimpleDirectParams;
+template <int D, int OP>
+__global__ __launch_bounds__(kBlock) void reduce_copy_simple_group_direct_kernel(const SimpleDirectParams* table,
+                                                                                 int nMembers, int G) {
+  constexpr uint64_t esz = 16 / Ty<D>::EPP;
+  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
+  __shared__ uint32_t verdict;
+  const uint32_t m = __builtin_amdgcn_readfirstlane(blockIdx.x / (uint32_t)G);
+  const uint32_t w = blockIdx.x - m * (uint32_t)G;
+  if (m >= (uint32_t)nMembers) return;
+  c_SimpleDirectParams& E = ((c_SimpleDirectParams*)table)[m];
+  c_SimpleStepsParams& P = E;  // the FIFO-only entry is its base
+  const bool lane0 = threadIdx.x == 0;
+  const int nSlots = P.nSlots, nRecv = P.nRecv, nSend = P.nSend, nSteps = P.nSteps;
+  const uint64_t sps = (uint64_t)P.stepPerSlice;
+  const uint64_t slotBytes = P.slotBytes, timeoutTicks = P.timeoutTicks;
+  uint32_t* const status = P.status;
+  const int firstWins = P.firstWins;
+  uint64_t rs[MP], ss[MP];
+#pragma unroll
+  for (int i = 0; i < MP; i++) rs[i] = P.recvStep[i], ss[i] = P.sendStep[i];
+  // Every earlier launch of this stream has completed, whatever ran its steps: the slots before recvStep
+  // are read and those before sendStep written. (The "return credits" store of a connection that host-
+  // sequenced steps used before.)
+  if (lane0) {
+    for (int i = 0; i < nRecv; i++)
+      __hip_atomic_store(credit_word(P.recvHead[i], w), rs[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (int j = 0; j < nSend; j++)
+      __hip_atomic_store(credit_word(P.sendTail[j], w), ss[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  SimpleStepArgs a;
+  a.redArg = P.redArg;
+  for (int k = 0; k < nSteps; k++) {
+    c_LLStep& st = P.step[k];  // scalar loads from the table
+    const uint64_t nBytes = (uint64_t)st.nElts * esz;
+    const uint64_t nTiles = (nBytes + kSimpleTileBytes - 1) / kSimpleTileBytes;
+    const bool stRecv = st.recv, stSend = st.send;
+    const bool owns = w < nTiles;  // workgroup-uniform, as everything the barriers below depend on
+    if (owns) {
+      if (stRecv || stSend) {
+        if (threadIdx.x < 64) {
+          bool ok = true;
+          uint64_t t0 = 0;
+#pragma unroll
+          for (int i = 0; i < MP; i++)  // waitPeer, receive side: tail >= step + StepPerSlice
+            if (ok && stRecv && i < nRecv)
+              ok = simple_wait(credit_word(P.recvTail[i], w), rs[i] + sps, t0, timeoutTicks, status);
+#pragma unroll
+          for (int j = 0; j < MP; j++)  // send side: head + NCCL_STEPS >= step + StepPerSlice
+            if (ok && stSend && j < nSend && ss[j] + sps > (uint64_t)nSlots)
+              ok = simple_wait(credit_word(P.sendHead[j], w), ss[j] + sps - (uint64_t)nSlots, t0, timeoutTicks, status);
+          if (stRecv) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the invalidate has completed before the barrier
+          }
+          if (lane0) verdict = ok ? 1u : 0u;
+        }
+        __syncthreads();
+        if (verdict == 0u) return;  // every wave of the workgroup: status is set, nothing of the slice is written
+      }
+      const int srcBuf = st.srcBuf, dstBuf = st.dstBuf;
+      a.src = srcBuf == 0 ? P.input + st.srcIx * esz : srcBuf == 1 ? P.output + st.srcIx * esz : nullptr;
+      a.dst = dstBuf == 0 ? const_cast<char*>(P.input) + st.dstIx * esz
+              : dstBuf == 1 ? P.output + st.dstIx * esz : nullptr;
+      // shipped semantics: every reduce returns acc = srcs[0], no pre-op, no post-op
+      a.nFold = !stRecv ? 0 : !firstWins ? nRecv : a.src ? 0 : 1;
+      a.nSend = stSend ? nSend : 0;
+      a.preOp = srcBuf == 0 && !firstWins;
+      a.postOp = st.postOp && !firstWins;
+#pragma unroll
+      for (int i = 0; i < MP; i++) {
+        a.recv[i] = P.recvFifo[i] + (rs[i] % (uint64_t)nSlots) * slotBytes;
+        a.send[i] = P.sendFifo[i] + (ss[i] % (uint64_t)nSlots) * slotBytes;
+      }
+      // waitPeer's DirectWrite pointers (prims_simple.h:148-164): an end is direct when the record permits it
+      // (pad[0]) and the connection is (the table entry). Both ends compute dstIx * esz alike.
+      const uint32_t bits = st.pad[0];
+      const bool dRecv = stRecv && (bits & NEXR_SIMPLE_DIRECT_RECV) && E.recvDirect;
+      if (dRecv) a.recv[0] = P.output + st.dstIx * esz;
+      if (bits & NEXR_SIMPLE_DIRECT_SEND) {
+#pragma unroll
+        for (int j = 0; j < MP; j++)
+          if (E.sendDirect[j]) a.send[j] = E.sendDirect[j] + st.dstIx * esz;
+      }
+      // :258-269: source 0 IS the user destination. Nothing goes to the output; a sending record copies the one
+      // source to its send destinations bit for bit (directRecvCopyDirectSend), any other moves no data
+      // (directRecv): it has waited, and advances and posts below.
+      bool moves = true;
+      if (dRecv && srcBuf == -1 && dstBuf == 1) {
+        a.dst = nullptr;
+        a.postOp = 0;
+        moves = stSend;
+      }
+      if (moves) {
+        if constexpr (OP == nexrDevMinMax) {
+          if ((a.redArg & 1) == 0) simple_tiles<D, OP, true, true>(a, w, (uint32_t)G, nBytes, nTiles);
+          else simple_tiles<D, OP, false, true>(a, w, (uint32_t)G, nBytes, nTiles);
+        } else {
+          simple_tiles<D, OP, false, true>(a, w, (uint32_t)G, nBytes, nTiles);
+        }
+      }
+      if (stRecv || stSend) {
+        // every wave: its stores to the send slots have completed and its loads of the receive slots returned
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+      }
+    }
+    // postPeer. A workgroup without a tile of the slice posts as well: nobody waits for it on this slice.
+    if (lane0) {
+      if (stSend) {
+        if (owns) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the write-back has completed before the tail goes out
+        }
+        for (int j = 0; j < nSend; j++)
+          __hip_atomic_store(credit_word(P.sendTail[j], w), ss[j] + sps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      if (stRecv)
+        for (int i = 0; i < nRecv; i++)
+          __hip_atomic_store(credit_word(P.recvHead[i], w), rs[i] + sps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (stRecv) {
+#pragma unroll
+      for (int i = 0; i < MP; i++) rs[i] += sps;
+    }
+    if (stSend) {
+#pragma unroll
+      for (int j = 0; j < MP; j++) ss[j] += sps;
+    }
+  }
+}
+
 template <int D>
 static const void* simple_group_fn_dt(int op) {
   switch (op) {
@@ -331,6 +481,50 @@ hipError_t launch_simple_group(int dt, int op, const SimpleStepsParams* table, i
 
 hipError_t simple_group_blocks_per_cu(int dt, int op, int* blocks) {
   const void* fn = simple_group_fn(dt, op);
+  if (!fn) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fn, kBlock, 0);
+}
+
+template <int D>
+static const void* simple_group_direct_fn_dt(int op) {
+  switch (op) {
+    case nexrDevSum: return (const void*)&reduce_copy_simple_group_direct_kernel<D, nexrDevSum>;
+    case nexrDevProd: return (const void*)&reduce_copy_simple_group_direct_kernel<D, nexrDevProd>;
+    case nexrDevMinMax: return (const void*)&reduce_copy_simple_group_direct_kernel<D, nexrDevMinMax>;
+    case nexrDevPreMulSum: return (const void*)&reduce_copy_simple_group_direct_kernel<D, nexrDevPreMulSum>;
+    case nexrDevSumPostDiv:
+      if constexpr (Ty<D>::kIsInt) return (const void*)&reduce_copy_simple_group_direct_kernel<D, nexrDevSumPostDiv>;
+      break;
+  }
+  return nullptr;
+}
+
+static const void* simple_group_direct_fn(int dt, int op) {
+  switch (dt) {
+    case nexrInt8: return simple_group_direct_fn_dt<nexrInt8>(op);
+    case nexrUint8: return simple_group_direct_fn_dt<nexrUint8>(op);
+    case nexrInt32: return simple_group_direct_fn_dt<nexrInt32>(op);
+    case nexrUint32: return simple_group_direct_fn_dt<nexrUint32>(op);
+    case nexrInt64: return simple_group_direct_fn_dt<nexrInt64>(op);
+    case nexrUint64: return simple_group_direct_fn_dt<nexrUint64>(op);
+    case nexrFloat16: return simple_group_direct_fn_dt<nexrFloat16>(op);
+    case nexrFloat32: return simple_group_direct_fn_dt<nexrFloat32>(op);
+    case nexrFloat64: return simple_group_direct_fn_dt<nexrFloat64>(op);
+    case nexrBfloat16: return simple_group_direct_fn_dt<nexrBfloat16>(op);
+  }
+  return nullptr;
+}
+
+hipError_t launch_simple_group_direct(int dt, int op, const SimpleDirectParams* table, int nMembers, int G,
+                                      hipStream_t s) {
+  const void* fn = simple_group_direct_fn(dt, op);
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {&table, &nMembers, &G};
+  return hipLaunchKernel(fn, dim3((unsigned)(nMembers * G)), dim3(kBlock), args, 0, s);
+}
+
+hipError_t simple_group_direct_blocks_per_cu(int dt, int op, int* blocks) {
+  const void* fn = simple_group_direct_fn(dt, op);
   if (!fn) return hipErrorInvalidValue;
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fn, kBlock, 0);
 }

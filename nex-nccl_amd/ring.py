@@ -21,7 +21,7 @@ EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
                     "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
-                    "nexrRingCommSetSimpleGroup",
+                    "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
                     "nexrRingCommSetLLFlagRule",
                     "nexrRingCommGetLLCleanup", "nexrRingCommDestroy", "nexrPeerRingCommCreate",
                     "nexrPeerRingAllReduce", "nexrPeerRingReduceScatter", "nexrPeerRingAllGather",
@@ -74,6 +74,8 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommSetLLGroup.argtypes = [vp, i32]
     L.nexrRingCommSetSimpleGroup.argtypes = [vp, i32]
+    L.nexrRingCommSetDirect.argtypes = [vp, i32]
+    L.nexrRingCommGetDirect.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.nexrRingCommSetLLFlagRule.argtypes = [vp, ctypes.POINTER(LLFlagRule)]
     L.nexrRingCommGetLLCleanup.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.nexrPeerRingCommCreate.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(PeerRingConfig)]
@@ -262,6 +264,21 @@ class RingComm:
         caller's fn, the hipStreamSynchronize step wait, more than 32 members, or a grid that is not resident
         at once even at one workgroup per member. tree_all_reduce does not take it."""
         _check(self._L.nexrRingCommSetSimpleGroup(self._h, 1 if on else 0), "nexrRingCommSetSimpleGroup")
+
+    def set_direct(self, on: bool) -> None:
+        """State that the user buffers of the following ring collectives are registered
+        (nexrRingCommSetDirect): SIMPLE senders then write into the next rank's recvbuff instead of a FIFO
+        slot (DirectWrite) in AllGather, Broadcast and out-of-place AllReduce; every other call runs as
+        without it. Between collectives; InvalidUsage unless the communicator is thread-rank and SIMPLE.
+        Combines with set_simple_group."""
+        _check(self._L.nexrRingCommSetDirect(self._h, 1 if on else 0), "nexrRingCommSetDirect")
+
+    def direct_slices(self) -> tuple:
+        """(direct, fifo): the last ring collective's send slices of either kind over all ranks and channels
+        (nexrRingCommGetDirect)."""
+        d, f = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.nexrRingCommGetDirect(self._h, ctypes.byref(d), ctypes.byref(f)), "nexrRingCommGetDirect")
+        return int(d.value), int(f.value)
 
     def set_ll_flag_rule(self, flag_max: int, clean_mask: int) -> None:
         """The LL flag rule of every channel (nexrRingCommSetLLFlagRule): (0, 0x7ffffff8) is the production
