@@ -75,6 +75,29 @@ def channel_parts(n_channels: int, count: int, esz: int, traffic_per_byte: int, 
     return parts
 
 
+def chunk_count(collective: str, proto: str, esz: int, buff_bytes: int) -> int:
+    """chunkCount in elements of one channel (calcCollChunking, reference src/enqueue.cc:1993-1999, aligned to
+    the protocol's grain, :2062): stepSize = buffSize / NCCL_STEPS; SIMPLE rings take chunkSteps of them (4
+    for all_reduce / reduce_scatter / all_gather, 1 for the reduce / broadcast pipes), everything else one;
+    LL carries half a step of data, LL128 15 of every 16 words. `collective`: "all_reduce", "reduce_scatter",
+    "all_gather", "reduce", "broadcast" or "tree". The tree's LL128 chunk also shrinks with the size above
+    32 KiB (:2039-2047); that rule is not restated, so such a FIFO is refused here."""
+    step_bytes = buff_bytes // 8
+    ring = collective in ("all_reduce", "reduce_scatter", "all_gather")
+    if collective not in ("all_reduce", "reduce_scatter", "all_gather", "reduce", "broadcast", "tree"):
+        raise ValueError(collective)
+    if proto == "simple":
+        return step_bytes * (4 if ring else 1) // 512 * 512 // esz
+    if proto == "ll":
+        return step_bytes // 2 // 16 * 16 // esz
+    if proto != "ll128":
+        raise ValueError(proto)
+    chunk = step_bytes // 16 * 15
+    if collective == "tree" and chunk > 32768:
+        raise ValueError("the tree's LL128 chunk depends on the size above 32 KiB")
+    return chunk // 1920 * 1920 // esz
+
+
 def ring_allreduce_expected(inputs, datatype: int, op: int, buff_bytes: int = 4 << 20, n_channels: int = 1):
     n = len(inputs)
     enc = host_to_dev_red_op(op, datatype, n)
@@ -92,9 +115,8 @@ def ring_allreduce_expected(inputs, datatype: int, op: int, buff_bytes: int = 4 
         else:
             out = inputs[0].copy()
         return [out]
-    step_bytes = buff_bytes // 8
     for _, grid, part_count in channel_parts(n_channels, count, esz, 2):
-        chunk = step_bytes * 4 // 512 * 512 // esz  # chunkSize aligned to the 512-B grain (enqueue.cc:2062)
+        chunk = chunk_count("all_reduce", "simple", esz, buff_bytes)  # aligned to the 512-B grain (enqueue.cc:2062)
         loop = n * chunk
         for elem_off in range(0, part_count, loop):
             rem = part_count - elem_off
@@ -141,10 +163,7 @@ def ring_allreduce_expected_ll(inputs, datatype: int, op: int, buff_bytes: int =
 
 def _ll_ring_part(step, inputs, out, grid, count, esz, buff_bytes, proto, datatype, dev_op, arg):
     n = len(inputs)
-    if proto == "ll":
-        chunk = (buff_bytes // 8) // 2 // 16 * 16 // esz
-    else:
-        chunk = (buff_bytes // 8) // 16 * 15 // 1920 * 1920 // esz
+    chunk = chunk_count("all_reduce", proto, esz, buff_bytes)
     loop = n * chunk
     for elem_off in range(0, count, loop):
         rem = count - elem_off

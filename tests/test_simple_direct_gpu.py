@@ -21,8 +21,9 @@ import pytest
 import ll_steps_cases as cases
 import make_golden as mg
 import simple_direct_model as dm
-import simple_steps_cases as sc
 import simple_steps_model as model
+from simple_direct_cases import DCase, all_reduce_case, types_and_ops_case
+from simple_direct_cases import blank as _blank
 from oracle.ring import (all_gather_expected, broadcast_expected, reduce_expected, reduce_scatter_expected,
                          ring_allreduce_expected)
 
@@ -33,7 +34,6 @@ TIMEOUT_US = 2_000_000
 GUARD = 64
 SLOTS = 8
 CREDIT = model.CREDIT_BYTES
-PATTERN = 0xA5
 
 
 @pytest.fixture(scope="module")
@@ -42,36 +42,6 @@ def stream():
     s = torch.cuda.Stream(device=torch.device("cuda:0"))
     yield s.cuda_stream
     torch.cuda.synchronize()
-
-
-class DCase:
-    """Members (dm.DMember, made by `build`, fresh for every run), their connections, and how to run them."""
-
-    def __init__(self, what, dt, op, arg, slot, sps, build, misalign=0):
-        self.what, self.dt, self.op, self.arg, self.slot, self.sps, self.misalign = what, dt, op, arg, slot, sps, misalign
-        self.members, self.conns = build()
-        for c in self.conns:
-            c.fifo[:] = PATTERN
-
-
-def _blank(n, dt):
-    return np.full(n * cases.esz_of(dt), cases.FILL, dtype=np.uint8).view(mg.STORE[dt])
-
-
-def all_reduce_case(dt=mg.F32, name="sum", slot=4096, sps=1, spc=1, loops=20, tail=None, misalign=0, n=2, seed=61):
-    """The n-member direct all-reduce: `loops` full loops (2 send slices a connection and loop at n = 2) and a
-    last loop of `tail` elements."""
-    _n, op, arg = cases.op_named(dt, name)
-    esz = cases.esz_of(dt)
-    step = slot // esz
-    tail = (16 * 1024 + 5 + esz - 1) // esz + 3 if tail is None else tail
-    count = loops * n * step * sps * spc + tail
-    xs = mg.gen_inputs(dt, n, count, seed + dt, special=True)
-
-    def build():
-        lists = dm.all_reduce_lists(n, count, esz, step, sps, spc)
-        return dm.ring_members(lists, xs, [_blank(count, dt) for _ in range(n)], slot, sps, start=6 * sps)
-    return DCase(f"all-reduce {mg.DT_NAMES[dt]} {name} slot={slot} sps={sps}", dt, op, arg, slot, sps, build, misalign)
 
 
 def all_gather_case(in_place, dt=mg.F16, slot=4096, sps=2, spc=2, n=3, seed=67):
@@ -240,9 +210,10 @@ def test_all_reduce_with_slices_of_zero_elements(nexr, oracle, stream, tail):
     Rig(all_reduce_case(spc=2, sps=2, loops=2, tail=tail)).run(nexr, stream)
 
 
-@pytest.mark.parametrize("dt,name", sc.CHAIN_PAIRS)
+@pytest.mark.parametrize("dt,name", cases.STAR_PAIRS)
 def test_all_reduce_types_and_ops(nexr, oracle, stream, dt, name):
-    Rig(all_reduce_case(dt, name, loops=3, n=3)).run(nexr, stream)
+    """Every (datatype, op) pair the API accepts: every instance of the kernel is launched."""
+    Rig(types_and_ops_case(dt, name)).run(nexr, stream)
 
 
 @pytest.mark.parametrize("dt", [mg.I8, mg.F16])

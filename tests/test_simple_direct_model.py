@@ -5,7 +5,9 @@ schedules run through FIFOs (where the outputs are the same too)."""
 import numpy as np
 import pytest
 
+import ll_steps_cases as cases
 import make_golden as mg
+import simple_direct_cases as dc
 import simple_direct_model as dm
 from oracle.ring import all_gather_expected, broadcast_expected, ring_allreduce_expected
 
@@ -91,6 +93,53 @@ def test_broadcast_from_every_root(oracle, n, in_place):
             assert f[r].output.tobytes() == np.asarray(exp[r]).tobytes(), (root, r)
         assert not any(c.mask.any() for c in dc)
         assert _counters(dc) == _counters(fc)
+
+
+def _ring_fold(xs, dt, op, arg, chunk0):
+    """The all-reduce of a SIMPLE ring by tests/golden/make_golden.py's numpy fold alone: chunk c starts at rank
+    c + 1 with the pre-op, every following rank folds its own pre-op'd input first, rank c ends with the post-op."""
+    n, count, esz = len(xs), xs[0].size, xs[0].itemsize
+    out = np.empty_like(xs[0])
+    chunk = chunk0
+    for elem in range(0, count, n * chunk0):
+        rem = count - elem
+        if rem < n * chunk0:
+            pack = 16 // esz
+            chunk = ((rem + n - 1) // n + pack - 1) // pack * pack
+        for c in range(n):
+            sl = slice(elem + c * chunk, elem + min(c * chunk + chunk, rem))
+            if sl.stop <= sl.start:
+                continue
+            acc = mg.reference_reduce(dt, op, arg, [xs[(c + 1) % n][sl]], [arg], False)
+            for k in range(2, n + 1):
+                acc = mg.reference_reduce(dt, op, arg, [xs[(c + k) % n][sl], acc], [arg], k == n)
+            out[sl] = acc
+    return out
+
+
+@pytest.mark.parametrize("dt,name", cases.STAR_PAIRS)
+def test_all_reduce_types_and_ops(oracle, dt, name):
+    """The lists of tests/test_simple_direct_gpu.py::test_all_reduce_types_and_ops, all 56 accepted pairs, without
+    a GPU: direct, every rank's output is the numpy fold of the ring order and the output of the same schedule run
+    through FIFOs, no FIFO byte is written, and the step counters agree."""
+    d = dc.types_and_ops_case(dt, name)
+    f = dc.types_and_ops_case(dt, name, direct=False)
+    xs = [m.input.copy() for m in d.members]
+    dm.run(d.members, d.dt, d.op, d.arg)
+    dm.run(f.members, f.dt, f.op, f.arg)
+    store = mg.STORE[dt]
+    exp = _ring_fold([x.view(store) for x in xs], dt, d.op, d.arg, d.slot // cases.esz_of(dt))
+    for r, (a, b) in enumerate(zip(d.members, f.members)):
+        assert mg.canon_bytes(dt, a.output.view(store)) == mg.canon_bytes(dt, exp), r
+        assert a.output.tobytes() == b.output.tobytes(), r
+        assert a.input.tobytes() == xs[r].tobytes(), r
+    assert not any(c.mask.any() for c in d.conns) and all((c.fifo == dc.PATTERN).all() for c in d.conns)
+    assert all(c.mask.any() for c in f.conns)
+    assert _counters(d.conns) == _counters(f.conns)
+
+
+def test_the_types_and_ops_cover_every_pair_the_api_accepts():
+    assert len(cases.STAR_PAIRS) == len(set(cases.STAR_PAIRS)) == 56
 
 
 def test_a_direct_receive_that_does_not_send_moves_no_data(oracle):
