@@ -648,6 +648,33 @@ nexrResult_t stageFor(size_t slotBytes, hipStream_t caller, StageLease* lease) {
   return nexrSuccess;
 }
 
+// hipMemcpyAsync between device memory and `bytes` of a host buffer that begins inside a pinned range the runtime
+// knows (hipHostRegister, hipHostMalloc) and may run past its end: the runtime refuses such a copy whole
+// (hipErrorInvalidValue: it finds the range by the host pointer and the copy does not fit it), so it is made in
+// pieces, each ending where the range that holds its first byte ends; a piece that begins in memory the runtime
+// does not know is an ordinary pageable copy to the buffer's end.
+hipError_t hostCopyPieces(char* dev, char* host, size_t bytes, bool toDevice, hipStream_t s) {
+  while (bytes > 0) {
+    size_t piece = bytes;
+    uintptr_t beg = 0;
+    size_t size = 0;
+    if (hipPointerGetAttribute(&beg, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, (hipDeviceptr_t)host) == hipSuccess &&
+        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, (hipDeviceptr_t)host) == hipSuccess &&
+        (uintptr_t)host >= beg && (uintptr_t)host < beg + size) {
+      if (beg + size - (uintptr_t)host < piece) piece = beg + size - (uintptr_t)host;
+    } else {
+      (void)hipGetLastError();  // pageable memory reports an error: not a failure of this call
+    }
+    const hipError_t e = toDevice ? hipMemcpyAsync(dev, host, piece, hipMemcpyHostToDevice, s)
+                                  : hipMemcpyAsync(host, dev, piece, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+    dev += piece;
+    host += piece;
+    bytes -= piece;
+  }
+  return hipSuccess;
+}
+
 // ---- host-staged variant, large pageable calls: a CPU copy team and pinned zero-copy slots -------
 // The runtime's pageable hipMemcpyAsync copies through its own staging buffer with one CPU memcpy
 // before each DMA, which held the C2 mix to 49 GB/s against an ~86 GB/s PCIe floor
@@ -1096,6 +1123,8 @@ NEXR_API nexrResult_t nexrReduceCopyHost(int nSrcs, const void* const* srcs, int
   const void* zsrc[NEXR_MAX_SRCS];
   void* zdst[NEXR_MAX_DSTS];
   bool psrc[NEXR_MAX_SRCS], pdst[NEXR_MAX_DSTS];  // pinned (device-mapped) buffers
+  // begins inside a pinned range and runs past its end: staged, and by the runtime only in pieces (hostCopyPieces)
+  bool csrc[NEXR_MAX_SRCS] = {}, cdst[NEXR_MAX_DSTS] = {};
   // Classification: the registration cache first (no HIP call); otherwise the runtime's pointer
   // query, trusted only when the whole buffer lies inside the pinned range it reports.
   static const long zeroCopy = envLong("NEXR_HOST_ZERO_COPY", 1);
@@ -1107,7 +1136,7 @@ NEXR_API nexrResult_t nexrReduceCopyHost(int nSrcs, const void* const* srcs, int
   for (int k = 0; k < nSrcs + nDsts; k++) {
     const void* hp = k < nSrcs ? srcs[k] : dsts[k - nSrcs];
     void* dev = nullptr;
-    bool pin = false;
+    bool pin = false, cut = false;
     if (zeroCopy != 0) {
       if (regLookup(hp, bufBytes, &dev)) {
         pin = true;
@@ -1124,17 +1153,21 @@ NEXR_API nexrResult_t nexrReduceCopyHost(int nSrcs, const void* const* srcs, int
           size_t size = 0;
           if (hipPointerGetAttribute(&beg, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, (hipDeviceptr_t)hp) != hipSuccess ||
               hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, (hipDeviceptr_t)hp) != hipSuccess ||
-              (uintptr_t)hp < beg || (uintptr_t)hp + bufBytes > beg + size)
+              (uintptr_t)hp < beg || (uintptr_t)hp + bufBytes > beg + size) {
             pin = false;
+            cut = true;
+          }
         }
         (void)hipGetLastError();  // pageable memory reports an error: not a failure of this call
       }
     }
     if (k < nSrcs) {
       psrc[k] = pin;
+      csrc[k] = cut;
       zsrc[k] = pin ? dev : nullptr;
     } else {
       pdst[k - nSrcs] = pin;
+      cdst[k - nSrcs] = cut;
       zdst[k - nSrcs] = pin ? dev : nullptr;
     }
     nPinned += pin ? 1 : 0;
@@ -1194,7 +1227,10 @@ NEXR_API nexrResult_t nexrReduceCopyHost(int nSrcs, const void* const* srcs, int
         continue;
       }
       dsrc[k] = base + chunkBytes * k;
-      NEXR_HIP(hipMemcpyAsync((void*)dsrc[k], (const char*)srcs[k] + e0 * esz, n * esz, hipMemcpyHostToDevice, s));
+      if (csrc[k])
+        NEXR_HIP(hostCopyPieces((char*)dsrc[k], (char*)srcs[k] + e0 * esz, n * esz, true, s));
+      else
+        NEXR_HIP(hipMemcpyAsync((void*)dsrc[k], (const char*)srcs[k] + e0 * esz, n * esz, hipMemcpyHostToDevice, s));
     }
     void* ddst[NEXR_MAX_DSTS + 1];
     int m = 0;
@@ -1207,9 +1243,13 @@ NEXR_API nexrResult_t nexrReduceCopyHost(int nSrcs, const void* const* srcs, int
     if (r != nexrSuccess) return r;
     NEXR_HIP(hipEventRecord(st->kernelDone[slot], s));
     NEXR_HIP(hipStreamWaitEvent(st->out, st->kernelDone[slot], 0));
-    for (int d = 0; d < nDsts; d++)
-      if (!pdst[d])
+    for (int d = 0; d < nDsts; d++) {
+      if (pdst[d]) continue;
+      if (cdst[d])
+        NEXR_HIP(hostCopyPieces(staged, (char*)dsts[d] + e0 * esz, n * esz, false, st->out));
+      else
         NEXR_HIP(hipMemcpyAsync((char*)dsts[d] + e0 * esz, staged, n * esz, hipMemcpyDeviceToHost, st->out));
+    }
     NEXR_HIP(hipEventRecord(st->outDone[slot], st->out));
   }
   const uint64_t tw = nowNs();

@@ -1,7 +1,11 @@
 """GPU tests of the emulated ring collectives (reduce-scatter, all-gather, reduce, broadcast) and the
 tree all-reduce with the MI355X kernels underneath: device-memory mode (buffers and FIFOs in HBM,
 nexrReduceCopy / nexrReduceCopyLL / nexrReduceCopyLL128 per step) for every protocol, and host-memory
-mode (every step through nexrReduceCopyHost). Outputs are compared bit for bit with oracle/ring.py."""
+mode (every step through nexrReduceCopyHost). Outputs are compared bit for bit with oracle/ring.py.
+
+Host memory has one test here (reduce-scatter and the tree, pageable buffers, large counts);
+tests/test_ring_host_memory_gpu.py is the host-memory coverage: all six collectives from every root at small
+counts on pageable, registered, runtime-pinned and partly registered user buffers, with set_direct."""
 import importlib
 
 import numpy as np

@@ -223,6 +223,49 @@ def test_buffer_past_a_registered_range_is_staged(hip):
         nexr.host_deregister(h)
 
 
+@pytest.mark.parametrize("cut", ["output-end", "source-end", "source-begin"])
+def test_buffer_across_a_registration_edge_through_the_runtime_copies(hip, cut):
+    """The same, at a size the chunk pipeline serves (more than 4 MiB of pageable bytes: the runtime's
+    hipMemcpyAsync, not the copy team's memcpy; copyNs == 0 says so). The runtime refuses a copy whose host
+    pointer lies inside a registered range and which runs past its end, so the library makes it in pieces
+    (round 13: such a call returned nexrUnhandledCudaError). output-end / source-end: the registration ends
+    inside `out` / inside `a`; source-begin: it begins inside `a`. Page-aligned cuts at odd element offsets of
+    buffers that are not page-aligned."""
+    nexr = importlib.import_module("nex-nccl_amd")
+    n = (1 << 20) + 4099
+    gap = 4096 + 48
+    offs = [gap, 2 * gap + 4 * n, 3 * gap + 8 * n]
+    reg = Region(hip, offs[-1] + 4 * n + gap, register=False)
+    rng = np.random.default_rng(13)
+    a, b, out = (reg.f32(o, n) for o in offs)
+    _fill(rng, a)
+    _fill(rng, b)
+    half = 2 * n // 4096 * 4096   # a page boundary about half way into a buffer that starts at offs[i]
+    if cut == "output-end":
+        h = nexr.host_register(reg.base, offs[2] // 4096 * 4096 + half)
+        want = (2, 1)
+    elif cut == "source-end":
+        h = nexr.host_register(reg.base, offs[0] // 4096 * 4096 + half)
+        want = (0, 3)
+    else:
+        start = offs[0] // 4096 * 4096 + half
+        h = nexr.host_register(reg.base + start, reg.buf.size - start)
+        want = (2, 1)
+    try:
+        out[:] = np.nan
+        guard = reg.buf[offs[2] - 64:offs[2]].copy(), reg.buf[offs[2] + 4 * n:offs[2] + 4 * n + 64].copy()
+        nexr.host_path_stats(reset=True)
+        nexr.reduce_copy_ptrs([reg.base + offs[0], reg.base + offs[1]], [reg.base + offs[2]], n, 7, 0, host=True)
+        st = nexr.host_path_stats()
+        assert (st["zeroCopyCalls"], st["registeredHits"], st["pointerQueries"]) == (0,) + want, st
+        assert st["copyNs"] == 0, st
+        assert np.array_equal(out.view(np.uint32), (a + b).view(np.uint32))
+        assert np.array_equal(reg.buf[offs[2] - 64:offs[2]], guard[0])
+        assert np.array_equal(reg.buf[offs[2] + 4 * n:offs[2] + 4 * n + 64], guard[1])
+    finally:
+        nexr.host_deregister(h)
+
+
 def test_register_inside_an_allocation_then_free(hip):
     """Advisor r5 (medium): memory from nexrHostMemAlloc may be registered (the reference's
     ncclMemAlloc-then-ncclCommRegister pattern). The registration is one more reference on the

@@ -1,7 +1,11 @@
 """GPU tests of the emulated ring all-reduce with the MI355X reduce-copy underneath (BASELINE
 configs[0]: fp32 sum all-reduce, 4 MiB, 2 CPU-emulated ranks): host-memory mode (every reduceCopy
 site goes through nexrReduceCopyHost, the staging FIFOs stay in host memory) and device-memory mode
-(buffers and FIFOs in HBM, nexrReduceCopy + stream sync per slice)."""
+(buffers and FIFOs in HBM, nexrReduceCopy + stream sync per slice).
+
+The host-memory calls here are single large ones on pageable buffers. tests/test_ring_host_memory_gpu.py is the
+host-memory coverage: every collective, root, datatype and op at small counts on pageable, registered,
+runtime-pinned and partly registered user buffers, with set_direct, on 1 to 8 ranks and 1 and 2 channels."""
 import importlib
 
 import numpy as np
