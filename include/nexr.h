@@ -38,7 +38,7 @@ extern "C" {
  * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup, nexrReduceCopyLL128StepsGroup
  * for LL128 step lists, and nexrSimpleGroupWorkspaceBytes / nexrReduceCopySimpleStepsGroup with
  * nexrSimpleConnSet for SIMPLE ones, nexrSimpleGroupDirectWorkspaceBytes / nexrReduceCopySimpleStepsGroupDirect
- * with nexrSimpleDirectSet for their DirectWrite form): additions only, no existing entry point or struct layout changed, so the version
+ * with nexrSimpleDirectSet for their DirectWrite form) and the symmetric all-reduce (nexrSymAllReduce): additions only, no existing entry point or struct layout changed, so the version
  * stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
@@ -628,6 +628,59 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const n
                                                            int workgroupsPerMember, const nexrSimpleDirectSet* direct,
                                                            uint32_t* status, uint32_t timeoutUs, void* workspace,
                                                            size_t workspaceBytes, nexrStream_t stream);
+
+/*
+ * nexrSymAllReduce — the symmetric all-reduce ncclSymRun_AllReduce_RSxLD_AGxST (reference
+ * src/device/symmetric/all_reduce.hh:6-276) of nRanks ranks that live on ONE GPU, as one launch: peer loads
+ * and peer stores only, no FIFO, no credits, no fences, n reads and n writes per element. inputs[r] /
+ * outputs[r] are rank r's buffers of nElts elements (the reference's symmetric windows; here plain device
+ * memory). Additions only: the ABI stays 0.3. The multicast kernels (…MC), the LL variants (AGxLL_R) and the
+ * symmetric ReduceScatter_LD / AllGather_ST are not built.
+ *
+ * Ownership rule. n = nRanks (2..NEXR_SYM_MAX_RANKS), B = nBlocks (1..64, ncclSymMaxBlocks,
+ * src/include/symmetric.h:8; 0 means 1), esz = 2 or 4, nBytes = nElts * esz. The geometry comes from rank 0's
+ * pointers, as in the reference ("move to rank 0", all_reduce.hh:199-209): A = inputs[0] mod 16,
+ * D = (inputs[0] - outputs[0]) mod 16. With pre = min((16 - A) mod 16, nBytes) and cursor = pre (:207-209):
+ *   pass 1 (:213-228), only when D = 0: c1 = floor((nBytes - cursor) / 8192), c1 -= c1 mod (n * B); the
+ *     c1 * 8192 bytes from cursor are cut into 2048-byte pieces, piece i owned by rank i mod n;
+ *     cursor += c1 * 8192;
+ *   pass 2 (:230-245), when esz = 4 or D mod 4 = 0: c2 = floor((nBytes - cursor) / 2048),
+ *     c2 -= c2 mod (n * B); the c2 * 2048 bytes from cursor are cut into 512-byte pieces, piece i owned by
+ *     rank i mod n; cursor += c2 * 2048;
+ *   ends (:249-251, :134-135): the pre / esz leading elements followed by the (nBytes - cursor) / esz trailing
+ *     ones, numbered e = 0, 1, ...; element e is owned by rank floor(e / 32) mod n.
+ * (A piece is one iteration of a reference warp, 4 packs x 32 lanes x 16 or 4 bytes, and the warps are
+ * numbered by rank first, :262-267, so iteration i is rank i mod n's whatever the block size.) B fixes only
+ * the pass boundaries: it is the reference's CTA count, which it derives from a bandwidth model of NVIDIA
+ * hardware (src/symmetric.cc:105-289) that is not restated; the caller passes B, and the launch geometry here
+ * does not depend on it.
+ *
+ * An element owned by rank o is acc = inputs[o], then acc = acc + inputs[(o + j) mod n] for j = 1..n-1 in that
+ * order, the accumulator as first operand (allreduceDeep :23-81, allreduceEnds :134-169), the additions in
+ * fp32 for all three datatypes (ncclSymAccumType, symmetric/primitives.hh:426-434): fp16 and bf16 are
+ * widened exactly and rounded back once at the end, round-to-nearest-even, every NaN to 0x7fff; fp32
+ * denormals are kept and nothing is contracted. The result is stored to outputs[o], outputs[o + 1], ..., all n
+ * outputs (:83-104, :171-188). This fold order and accumulator type are no nexrReduceCopy call's.
+ *
+ * Barriers. The reference kernel arrives at a cross-rank barrier when it starts and waits for it before its
+ * first peer load, and arrives (release) and waits again when it ends (all_reduce.hh:269-275), so that no
+ * rank reads a peer's input before that peer has reached the collective and no rank leaves while a peer still
+ * reads its input or writes its output. With every rank on one GPU both are the stream's order: the launch
+ * starts after everything queued on `stream` before it and completes before anything queued behind it.
+ *
+ * datatype is nexrFloat32, nexrFloat16 or nexrBfloat16 and devRedOp nexrDevSum (symmetric/generate.py:48-50;
+ * redOpArg is ignored). In place (outputs[r] == inputs[r]) is allowed, and any output may equal any input
+ * whole, because every element is read by its one owner before it is written; partial overlap is undefined.
+ * Under nexrSemanticsShipped every add returns its first operand, so each element is its owner's input
+ * through the two casts; nccl and fork are identical here. Stream-ordered: one launch, no workspace, and
+ * nothing of the caller's arrays is read after the call returns. nElts == 0 succeeds without a launch.
+ * nexrInvalidArgument, before any device call: null arrays or entries, nRanks outside 2..64, nBlocks outside
+ * 0..64, another datatype or op, a pointer not aligned to esz.
+ */
+#define NEXR_SYM_MAX_RANKS 64
+NEXR_API nexrResult_t nexrSymAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                       size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                       int nBlocks, nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

@@ -118,6 +118,25 @@ NEXR_API nexrResult_t nexrRingBroadcast(nexrRingComm_t comm, const void* const* 
 NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op);
 
+/* ncclAllReduce as the reference's symmetric kernel RSxLD_AGxST (src/device/symmetric/all_reduce.hh:6-276):
+ * ONE nexrSymAllReduce (include/nexr.h: the ownership rule, the owner-first fp32 fold, nBlocks) over every
+ * rank's buffers on the communicator's first stream, then the wait the other collectives end with. No FIFO, no
+ * step, no credit: it touches no connection and no step counter, so it mixes freely with ring and tree calls in
+ * every mode, and it leaves nexrRingCommGetQueued as it was. Its bytes are NOT the ring's or the tree's: the
+ * fold starts at the element's owner and accumulates in fp32 (one rounding for fp16 / bf16). It applies to thread
+ * ranks, device memory and every rank on one GPU: anything else is nexrInvalidUsage; an op other than ncclSum,
+ * a datatype other than float32 / float16 / bfloat16, nBlocks outside 0..64 or more than NEXR_SYM_MAX_RANKS
+ * ranks is nexrInvalidArgument; one rank takes the one-rank path and count == 0 succeeds. In place allowed.
+ * The multicast and LL symmetric kernels, ReduceScatter_LD and AllGather_ST are not built. Measured on one
+ * MI355X, a 4 MiB fp32 all-reduce per rank, p25-p75 of 20 calls on the host clock
+ * (profiles/r14a_sym_all_reduce_probe.json): 0.018 / 0.026-0.031 /
+ * 0.028-0.032 ms at 2 / 4 / 8 ranks against 0.140-0.191 / 0.335-0.377 / 1.030-1.119 for the host-sequenced ring
+ * and 0.159-0.186 / 0.319-0.348 / 0.774-0.842 for the ring in group launches, the three alternated call by
+ * call in one process, every call exact (tools/sym_all_reduce_probe.py). */
+NEXR_API nexrResult_t nexrRingAllReduceSymmetric(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                 void* const* recvbuffs, size_t count, int datatype, int op,
+                                                 int nBlocks);
+
 /* The tree links of `rank` in this communicator's topology: *up (-1 at the root) and down[0..2]
  * (-1 when absent, children packed first as setTreeDown does). */
 NEXR_API nexrResult_t nexrTreeTopology(nexrRingComm_t comm, int rank, int* up, int* down);

@@ -88,7 +88,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrReduceCopyLL", "nexrReduceCopyLL128", "nexrReduceCopyLLSteps", "nexrReduceCopyLLStepsRule",
                "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrReduceCopyLL128StepsGroup",
                "nexrSimpleGroupWorkspaceBytes", "nexrReduceCopySimpleStepsGroup",
-               "nexrSimpleGroupDirectWorkspaceBytes", "nexrReduceCopySimpleStepsGroupDirect",
+               "nexrSimpleGroupDirectWorkspaceBytes", "nexrReduceCopySimpleStepsGroupDirect", "nexrSymAllReduce",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -317,6 +317,8 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopySimpleStepsGroupDirect.argtypes = [i32, P(SimpleConnSet), P(P(LLStep)), P(i32), i32, i32, u64, i32,
                                                        P(SimpleDirectSet), vp, ctypes.c_uint32, vp, sz, vp]
     L.nexrReduceCopySimpleStepsGroupDirect.restype = i32
+    L.nexrSymAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, i32, vp]
+    L.nexrSymAllReduce.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -780,6 +782,24 @@ def reduce_copy_ll_steps(input_ptr: int, output_ptr: int, recv: Sequence[tuple],
                                              int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(_ll_rule(rule)),
                                              *tail)
         _check(rc, "nexrReduceCopyLLStepsRule")
+
+
+SYM_MAX_RANKS = 64  # NEXR_SYM_MAX_RANKS
+
+
+def sym_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int, n_blocks: int = 0,
+                   dev_red_op: int = DevRedOp.Sum, red_op_arg: int = 0, stream: int = 0) -> None:
+    """The symmetric all-reduce RSxLD_AGxST of len(inputs) ranks on one GPU in one launch (``nexrSymAllReduce``):
+    rank r's device addresses inputs[r] / outputs[r], ``n_elts`` elements each of float32, float16 or bfloat16,
+    Sum only. Each element is folded by its owner, its own input first, in fp32, and stored to every output;
+    ``n_blocks`` (0 = 1, at most 64) is the reference's CTA count, which only decides where the passes end
+    (include/nexr.h). In place allowed. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrSymAllReduce(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, int(n_blocks),
+                                ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrSymAllReduce")
 
 
 def ll_clean_slot(send_lines: Sequence[int], send_flags: Sequence[int], first_line: int, slot_lines: int,

@@ -2158,6 +2158,66 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const n
                           status, timeoutUs, workspace, workspaceBytes, stream);
 }
 
+// The ownership plan of nexrSymAllReduce from rank 0's pointers (include/nexr.h; reference
+// src/device/symmetric/all_reduce.hh:199-252): the two passes' piece counts and where the ends lie.
+static void symPlan(uintptr_t in0, uintptr_t out0, uint64_t nElts, uint64_t esz, uint64_t nRanksBlocks,
+                    nexr::SymParams* p) {
+  const uint64_t nBytes = nElts * esz;
+  const uint64_t pre = std::min<uint64_t>((16u - in0) % 16u, nBytes);  // nPreBytes (:207-208)
+  const uint64_t d = (in0 - out0) % 16u;
+  uint64_t cursor = pre;
+  p->p1Off = cursor;
+  p->p1Pieces = 0;
+  if (d == 0) {  // 16-byte packs: chunks of 4 warps x 4 packs x 32 lanes (:213-228)
+    uint64_t chunks = (nBytes - cursor) / 8192;
+    chunks -= chunks % nRanksBlocks;
+    p->p1Pieces = chunks * 4;
+    cursor += chunks * 8192;
+  }
+  p->p2Off = cursor;
+  p->p2Pieces = 0;
+  if (esz == 4 || d % 4 == 0) {  // 4-byte packs (:230-245)
+    uint64_t chunks = (nBytes - cursor) / 2048;
+    chunks -= chunks % nRanksBlocks;
+    p->p2Pieces = chunks * 4;
+    cursor += chunks * 2048;
+  }
+  p->preElts = pre / esz;  // the ends (:249-251): nPreElts, then nSufElts from the cursor
+  p->sufOff = cursor;
+  p->nEnds = p->preElts + (nBytes - cursor) / esz;
+}
+
+NEXR_API nexrResult_t nexrSymAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                       int datatype, int devRedOp, uint64_t redOpArg, int nBlocks,
+                                       nexrStream_t stream) {
+  (void)redOpArg;
+  if (!inputs || !outputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS || nBlocks < 0 || nBlocks > 64) return nexrInvalidArgument;
+  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
+  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
+  const uint64_t esz = typeSize(datatype);
+  SymParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
+    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+  }
+  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
+  if (nElts == 0) return nexrSuccess;
+  symPlan((uintptr_t)inputs[0], (uintptr_t)outputs[0], nElts, esz, (uint64_t)nRanks * (uint64_t)(nBlocks ? nBlocks : 1),
+          &p);
+  p.nRanks = nRanks;
+  p.nFold = semantics() == nexrSemanticsShipped ? 1 : nRanks;  // SKIP_COMP: every add returns its first operand
+  // One-shot: a wave per piece or group of 32 end elements, four waves per workgroup; beyond the cap the
+  // kernel strides.
+  const uint64_t items = p.p1Pieces + p.p2Pieces + (p.nEnds + 31) / 32;
+  const uint64_t grid = std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+  NEXR_HIP(launch_sym_all_reduce(datatype, p, (unsigned)grid, (hipStream_t)stream));
+  return nexrSuccess;
+}
+
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,
                                       size_t slotLines, nexrStream_t stream) {
   if (nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;

@@ -189,6 +189,22 @@ hipError_t launch_simple_group_direct(int dt, int op, const SimpleDirectParams* 
                                       hipStream_t s);
 hipError_t simple_group_direct_blocks_per_cu(int dt, int op, int* blocks);
 
+// The symmetric all-reduce in one launch (nexrSymAllReduce; nexr_sym.hip): the 2n pointers and the ownership
+// plan the host derives from rank 0's pointers (symPlan, nexr_api.cpp; reference
+// src/device/symmetric/all_reduce.hh:199-252). Offsets are bytes from every buffer's start.
+struct SymParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t p1Off, p1Pieces;  // pass 1: 2048-byte pieces from p1Off, piece i owned by rank i % n
+  uint64_t p2Off, p2Pieces;  // pass 2: 512-byte pieces from p2Off, piece i owned by rank i % n
+  uint64_t preElts, sufOff;  // ends: element e < preElts at e, the others from byte sufOff on;
+  uint64_t nEnds;            //   nEnds elements in all, element e owned by rank (e / 32) % n
+  int nRanks;
+  int nFold;  // inputs that enter the fold from the owner's on: nRanks, or 1 under nexrSemanticsShipped
+};
+static_assert(sizeof(SymParams) <= 4096, "kernel argument block");
+hipError_t launch_sym_all_reduce(int dt, const SymParams& p, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -1193,3 +1193,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 
 // SIMPLE step lists in group launches: the same code object (tests/test_code_objects.py counts them).
 #include "nexr_simple.hip"
+// The symmetric all-reduce in one launch: the same code object again.
+#include "nexr_sym.hip"

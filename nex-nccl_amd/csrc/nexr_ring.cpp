@@ -1156,6 +1156,51 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
   return r;
 }
 
+// The symmetric all-reduce (nexrRingAllReduceSymmetric): one nexrSymAllReduce over every rank's buffers on the
+// communicator's first stream, then the wait every collective ends with (the completion word where the
+// communicator uses it, as runGroup; hipStreamSynchronize otherwise). No connection, no step counter and no
+// report of the last collective's mode is touched.
+nexrResult_t symAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                          int datatype, int op, int nBlocks) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
+  if (op != nexrSum || nBlocks < 0 || nBlocks > 64) return nexrInvalidArgument;
+  const int n = c->cfg.nRanks;
+  for (int i = 0; i < n; i++)
+    if (count != 0 && (!sendbuffs[i] || !recvbuffs[i])) return nexrInvalidArgument;
+  if (c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || (int)c->devices.size() < n ||
+      c->streams.empty() || !c->streams[0])
+    return nexrInvalidUsage;
+  for (int i = 0; i < n; i++)
+    if (c->devices[i] != c->devices[0]) return nexrInvalidUsage;
+  if (n > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (count == 0) return nexrSuccess;
+  if (n == 1) {
+    nexrDevRedOpFull red;
+    const nexrResult_t r = nexrHostToDevRedOp(&red, op, datatype, 1);
+    return r != nexrSuccess ? r : oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, nexrTypeSize(datatype));
+  }
+  if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+  hipStream_t stream = c->streams[0];
+  nexrResult_t r = nexrSymAllReduce(n, sendbuffs, recvbuffs, count, datatype, nexrDevSum, 0, nBlocks,
+                                    (nexrStream_t)stream);
+  if (r != nexrSuccess) return r;
+  uint32_t* done = c->stepWaitWord && !c->done.empty() ? c->done[0] : nullptr;
+  if (done) {
+    const int timeoutMs = c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000;
+    const uint32_t t = ++done[1];
+    if (hipStreamWriteValue32(stream, done, t, 0) == hipSuccess) {
+      auto t0 = std::chrono::steady_clock::now();
+      for (unsigned spins = 0;; spins++) {
+        if ((int32_t)(__atomic_load_n(done, __ATOMIC_ACQUIRE) - t) >= 0) return nexrSuccess;
+        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeoutMs)) break;
+        if (spins >= 4096) std::this_thread::yield();
+      }
+    }
+  }
+  return hipStreamSynchronize(stream) == hipSuccess ? nexrSuccess : nexrUnhandledCudaError;
+}
+
 // A communicator touches HIP when its FIFOs live in device memory or when any of its steps runs the
 // built-in (HIP) reduce-copy; one whose steps are all caller-supplied (a CPU checker) never does.
 bool needsHip(const nexrRingConfig& cfg) {
@@ -1301,6 +1346,13 @@ NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t c, const void* const* sen
                                         size_t count, int datatype, int op) {
   DeviceGuard dg(c && c->needHip);
   return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+}
+
+NEXR_API nexrResult_t nexrRingAllReduceSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
+                                                 void* const* recvbuffs, size_t count, int datatype, int op,
+                                                 int nBlocks) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
 }
 
 NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t c, int* word) {

@@ -1,0 +1,239 @@
+// nexr_sym.hip — the symmetric all-reduce RSxLD_AGxST as ONE launch (nexrSymAllReduce), for gfx950. Included
+// at the end of nexr_ll.hip behind nexr_simple.hip: the LL / LL128 object stays the one code object beside the
+// per-datatype ones.
+//
+// What it computes is ncclSymRun_AllReduce_RSxLD_AGxST (reference src/device/symmetric/all_reduce.hh:6-276)
+// on a communicator whose ranks all live on this GPU: every "peer window" is a plain device buffer, and the
+// cross-rank barriers at both ends of the reference kernel (:269-275) are the stream's order. Each rank owns
+// every n-th piece of the buffer; the owner o of an element loads it from every rank's input, folds
+// acc = in[o]; acc = acc + in[(o + j) % n], j = 1..n-1 (allreduceDeep :23-81, allreduceEnds :134-169), in
+// fp32 for all three datatypes (ncclSymAccumType, symmetric/primitives.hh:426-434; fp16 / bf16 widened
+// exactly, ONE round-to-nearest-even back, every NaN to 0x7fff), and stores the result to every rank's
+// output (:83-104, :171-188). Which bytes are which rank's is planned on the host (symPlan, nexr_api.cpp)
+// from rank 0's pointers as the reference does (:199-252) and arrives as SymParams:
+//   pass 1   p1Pieces pieces of 2048 bytes from byte p1Off, piece i owned by rank i % n (16-byte packs);
+//   pass 2   p2Pieces pieces of 512 bytes from byte p2Off, piece i owned by rank i % n (4-byte packs);
+//   ends     nEnds elements: the preElts leading ones, then those from byte sufOff; element e owned by rank
+//            (e / 32) % n, one element per lane.
+// The reference reaches this map with warps of 32 numbered rank, block, warp (:262-267): a warp's iteration
+// is 4 packs x 32 lanes, and warp w takes iterations w, w + wn, ... with n | wn.
+//
+// MI355X mapping. A wave takes whole pieces, so the owner is wave-uniform and the 2n pointers are scalar
+// loads from the kernel arguments: no lane holds a pointer per rank. A 2048-byte piece is two 16-byte packs
+// per lane of a wave64, a 512-byte piece two 4-byte packs, a group of 32 end elements the wave's low half.
+// All the loads of a wave's piece, for up to kSymPeers peers, are issued before the first add; beyond
+// kSymPeers ranks the fold goes on in groups of kSymPeers so that the registers stay bounded. Rank 0's
+// buffers decide the passes (its pass-1 packs are 16-byte aligned, its pass-2 packs 4-byte aligned); the
+// other ranks' buffers may sit at any element-aligned address, so every pack access is the unaligned-capable
+// form (nexr_types.hpp). No LDS, no cross-lane traffic, plain cache policy, a one-shot grid over the pieces.
+// An element is read by its one owner before anybody writes it, so any output may be any input.
+
+namespace nexr {
+
+constexpr int kSymPeers = 8;         // peers whose packs a wave has in flight at once
+constexpr int kSymPiece16 = 2048;    // pass 1: 4 packs x 32 lanes x 16 bytes of the reference
+constexpr int kSymPiece4 = 512;      // pass 2: 4 packs x 32 lanes x 4 bytes
+constexpr int kSymEndGroup = 32;     // ends: the reference's warp
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// a 4-byte pack of two 16-bit elements at any 2-byte aligned address
+typedef uint32_t __attribute__((aligned(1))) u32_a1;
+typedef __attribute__((address_space(1))) const u32_a1 g_cu32_a1;
+typedef __attribute__((address_space(1))) u32_a1 g_u32_a1;
+typedef __attribute__((address_space(1))) const uint16_t g_cu16;
+typedef __attribute__((address_space(1))) uint16_t g_u16;
+typedef __attribute__((address_space(1))) const uint32_t g_cu32;
+typedef __attribute__((address_space(1))) uint32_t g_u32;
+
+// ncclFromFloat's NaN (0x7fff) for a vector of fp16 / bf16 bit patterns; infBits = 0x7c00 / 0x7f80
+template <typename UV>
+__device__ __forceinline__ UV sym_canon(UV x, uint16_t infBits) {
+  const auto isnan = (x & (uint16_t)0x7fff) > infBits;
+  return isnan ? (UV)(uint16_t)0x7fff : x;
+}
+
+// Per datatype: the fp32 accumulator of a 16-byte pack, a 4-byte pack and one element, widened exactly and
+// rounded back once. bf16 rounds with v_cvt_pk_bf16_f32 (RNE, f32 denormals kept) as nexr_types.hpp does.
+template <int D> struct Sym;
+
+template <> struct Sym<nexrFloat32> {
+  static constexpr int kEsz = 4;
+  using A16 = f32x4;
+  using A4 = float;
+  using E = uint32_t;
+  __device__ static A16 widen16(u32x4 x) { return bc<f32x4>(x); }
+  __device__ static u32x4 narrow16(A16 a) { return bc<u32x4>(a); }
+  __device__ static A4 widen4(uint32_t x) { return bc<float>(x); }
+  __device__ static uint32_t narrow4(A4 a) { return bc<uint32_t>(a); }
+  __device__ static float widen1(E x) { return bc<float>(x); }
+  __device__ static E narrow1(float a) { return bc<uint32_t>(a); }
+};
+
+template <> struct Sym<nexrFloat16> {
+  static constexpr int kEsz = 2;
+  using A16 = f32x8;
+  using A4 = f32x2;
+  using E = uint16_t;
+  __device__ static A16 widen16(u32x4 x) { return __builtin_convertvector(bc<f16x8>(x), f32x8); }
+  __device__ static u32x4 narrow16(A16 a) {
+    return bc<u32x4>(sym_canon(bc<u16x8>(__builtin_convertvector(a, f16x8)), 0x7c00));
+  }
+  __device__ static A4 widen4(uint32_t x) { return __builtin_convertvector(bc<f16x2>(x), f32x2); }
+  __device__ static uint32_t narrow4(A4 a) {
+    return bc<uint32_t>(sym_canon(bc<u16x2>(__builtin_convertvector(a, f16x2)), 0x7c00));
+  }
+  __device__ static float widen1(E x) { return (float)bc<_Float16>(x); }
+  __device__ static E narrow1(float a) {
+    const uint16_t h = bc<uint16_t>((_Float16)a);
+    return (h & 0x7fff) > 0x7c00 ? (uint16_t)0x7fff : h;
+  }
+};
+
+template <> struct Sym<nexrBfloat16> {
+  static constexpr int kEsz = 2;
+  using A16 = f32x8;
+  using A4 = f32x2;
+  using E = uint16_t;
+  __device__ static A16 widen16(u32x4 x) { return Ty<nexrBfloat16>::widen(bc<u16x8>(x)); }
+  __device__ static u32x4 narrow16(A16 a) {
+    return bc<u32x4>(sym_canon(bc<u16x8>(__builtin_convertvector(a, bf16x8)), 0x7f80));
+  }
+  __device__ static A4 widen4(uint32_t x) { return bc<f32x2>((u32x2){x << 16, x & 0xffff0000u}); }
+  __device__ static uint32_t narrow4(A4 a) {
+    return bc<uint32_t>(sym_canon(bc<u16x2>(__builtin_convertvector(a, bf16x2)), 0x7f80));
+  }
+  __device__ static float widen1(E x) { return bc<float>((uint32_t)x << 16); }
+  __device__ static E narrow1(float a) {
+    const f32x2 two = {a, 0.0f};
+    const uint16_t h = bc<u16x2>(__builtin_convertvector(two, bf16x2)).x;
+    return (h & 0x7fff) > 0x7f80 ? (uint16_t)0x7fff : h;
+  }
+};
+
+// One piece of a pass: kPacks packs per lane, kStride bytes apart, for the wave that owns it. Pack is the
+// access type (the unaligned-capable 16-byte or 4-byte form), Acc its fp32 accumulator.
+template <typename Acc, typename Bits, typename LoadPtr, typename StorePtr, int kStride, typename Widen,
+          typename Narrow>
+__device__ __forceinline__ void sym_piece(const SymParams& P, uint32_t own, uint64_t off, Widen widen,
+                                          Narrow narrow) {
+  const uint32_t n = (uint32_t)P.nRanks, nFold = (uint32_t)P.nFold;
+  Acc acc[2];
+  uint32_t r = own;
+  for (uint32_t base = 0; base < nFold; base += kSymPeers) {  // wave-uniform, as everything below
+    Bits v[kSymPeers][2];
+#pragma unroll
+    for (int j = 0; j < kSymPeers; j++) {
+      if (base + j < nFold) {
+        const char* p = P.in[r] + off;  // scalar load of the pointer
+        v[j][0] = *(LoadPtr*)(p);
+        v[j][1] = *(LoadPtr*)(p + kStride);
+        r = r + 1 == n ? 0 : r + 1;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSymPeers; j++) {
+      if (base + j < nFold) {
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+          const Acc a = widen(v[j][u]);
+          if (j == 0 && base == 0) acc[u] = a;  // the owner's own input
+          else acc[u] = acc[u] + a;             // accumulator first
+        }
+      }
+    }
+  }
+  const Bits out0 = narrow(acc[0]), out1 = narrow(acc[1]);
+  r = own;
+  for (uint32_t k = 0; k < n; k++) {  // out[o], out[o + 1], ...
+    char* q = P.out[r] + off;
+    *(StorePtr*)(q) = out0;
+    *(StorePtr*)(q + kStride) = out1;
+    r = r + 1 == n ? 0 : r + 1;
+  }
+}
+
+// A group of 32 end elements, one per lane of the wave's low half.
+template <int D>
+__device__ __forceinline__ void sym_ends(const SymParams& P, uint32_t own, uint64_t e0, uint32_t lane) {
+  using S = Sym<D>;
+  using E = typename S::E;
+  using LoadPtr = typename std::conditional<S::kEsz == 2, g_cu16, g_cu32>::type;
+  using StorePtr = typename std::conditional<S::kEsz == 2, g_u16, g_u32>::type;
+  const uint64_t e = e0 + lane;
+  if (lane >= kSymEndGroup || e >= P.nEnds) return;
+  const uint64_t off = e < P.preElts ? e * S::kEsz : P.sufOff + (e - P.preElts) * S::kEsz;
+  const uint32_t n = (uint32_t)P.nRanks, nFold = (uint32_t)P.nFold;
+  float acc = 0.0f;
+  uint32_t r = own;
+  for (uint32_t base = 0; base < nFold; base += kSymPeers) {
+    E v[kSymPeers];
+#pragma unroll
+    for (int j = 0; j < kSymPeers; j++) {
+      if (base + j < nFold) {
+        v[j] = *(LoadPtr*)(P.in[r] + off);
+        r = r + 1 == n ? 0 : r + 1;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSymPeers; j++) {
+      if (base + j < nFold) {
+        const float a = S::widen1(v[j]);
+        if (j == 0 && base == 0) acc = a;
+        else acc = acc + a;
+      }
+    }
+  }
+  const E out = S::narrow1(acc);
+  r = own;
+  for (uint32_t k = 0; k < n; k++) {
+    *(StorePtr*)(P.out[r] + off) = out;
+    r = r + 1 == n ? 0 : r + 1;
+  }
+}
+
+// i % n for a wave-uniform i: the 32-bit division whenever i fits (always, below 2 TiB per rank)
+__device__ __forceinline__ uint32_t sym_owner(uint64_t i, uint32_t n) {
+  return (i >> 32) ? (uint32_t)(i % n) : (uint32_t)i % n;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void sym_all_reduce_kernel(SymParams P) {
+  using S = Sym<D>;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t n = (uint32_t)P.nRanks;
+  const uint64_t p1 = P.p1Pieces, p2 = P.p2Pieces;
+  const uint64_t nItems = p1 + p2 + (P.nEnds + kSymEndGroup - 1) / kSymEndGroup;
+  const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
+  for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < nItems; it += nWaves) {
+    if (it < p1) {
+      sym_piece<typename S::A16, u32x4, g_cu32x4_a1, g_u32x4_a1, kSymPiece16 / 2>(
+          P, sym_owner(it, n), P.p1Off + it * kSymPiece16 + lane * 16u, [](u32x4 x) { return S::widen16(x); },
+          [](typename S::A16 a) { return S::narrow16(a); });
+    } else if (it < p1 + p2) {
+      const uint64_t i = it - p1;
+      sym_piece<typename S::A4, uint32_t, g_cu32_a1, g_u32_a1, kSymPiece4 / 2>(
+          P, sym_owner(i, n), P.p2Off + i * kSymPiece4 + lane * 4u, [](uint32_t x) { return S::widen4(x); },
+          [](typename S::A4 a) { return S::narrow4(a); });
+    } else {
+      const uint64_t g = it - p1 - p2;
+      sym_ends<D>(P, sym_owner(g, n), g * kSymEndGroup, lane);
+    }
+  }
+}
+
+hipError_t launch_sym_all_reduce(int dt, const SymParams& p, unsigned grid, hipStream_t s) {
+  const void* fn = dt == nexrFloat32    ? (const void*)&sym_all_reduce_kernel<nexrFloat32>
+                   : dt == nexrFloat16  ? (const void*)&sym_all_reduce_kernel<nexrFloat16>
+                   : dt == nexrBfloat16 ? (const void*)&sym_all_reduce_kernel<nexrBfloat16>
+                                        : nullptr;
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {const_cast<SymParams*>(&p)};
+  return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, s);
+}
+
+}  // namespace nexr

@@ -19,7 +19,8 @@ RING_LIB_PATH = os.path.join(_HERE, "libnexr_ring.so")
 # Opt-in (make -C nex-nccl_amd/csrc EXTRAS=1): include/nexr_extras.h, a superset of libnexr_ring.so.
 EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
-                    "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrTreeTopology",
+                    "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrRingAllReduceSymmetric",
+                    "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
                     "nexrRingCommSetLLFlagRule",
@@ -69,6 +70,7 @@ def _bind_ring(L: ctypes.CDLL) -> None:
                         ("nexrPeerRingAllGather", []), ("nexrPeerRingReduce", [i32, i32]),
                         ("nexrPeerRingBroadcast", [i32])):
         getattr(L, name).argtypes = [vp, vp, vp, sz, i32] + extra
+    L.nexrRingAllReduceSymmetric.argtypes = [vp, arr, arr, sz, i32, i32, i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
@@ -215,6 +217,17 @@ class RingComm:
     def tree_all_reduce(self, sendbuffs, recvbuffs, count: int, datatype: int, op: int) -> None:
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrTreeAllReduce(self._h, s, r, int(count), int(datatype), int(op)), "nexrTreeAllReduce")
+
+    def all_reduce_symmetric(self, sendbuffs, recvbuffs, count: int, datatype: int, op: int,
+                             n_blocks: int = 0) -> None:
+        """ncclAllReduce as the reference's symmetric kernel RSxLD_AGxST in ONE launch
+        (nexrRingAllReduceSymmetric): every element folded by its owner, its own input first, in fp32, and
+        stored to every rank's recvbuff; n_blocks (0 = 1) only decides where the passes end. Thread ranks,
+        device memory, every rank on one GPU (else InvalidUsage); Sum of float32 / float16 / bfloat16 (else
+        InvalidArgument). Touches no connection: mixes with ring and tree calls, queued() stays as it was."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllReduceSymmetric(self._h, s, r, int(count), int(datatype), int(op), int(n_blocks)),
+               "nexrRingAllReduceSymmetric")
 
     def send_recv(self, sendbuffs, send_peers, recvbuffs, recv_peers, nbytes: int) -> None:
         """ncclSend/ncclRecv of every rank in one group: rank r sends nbytes of sendbuffs[r] to
