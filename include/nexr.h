@@ -38,7 +38,8 @@ extern "C" {
  * group launches (nexrLLGroupWorkspaceBytes, nexrReduceCopyLLStepsGroup, nexrReduceCopyLL128StepsGroup
  * for LL128 step lists, and nexrSimpleGroupWorkspaceBytes / nexrReduceCopySimpleStepsGroup with
  * nexrSimpleConnSet for SIMPLE ones, nexrSimpleGroupDirectWorkspaceBytes / nexrReduceCopySimpleStepsGroupDirect
- * with nexrSimpleDirectSet for their DirectWrite form) and the symmetric all-reduce (nexrSymAllReduce): additions only, no existing entry point or struct layout changed, so the version
+ * with nexrSimpleDirectSet for their DirectWrite form) and the symmetric all-reduce, reduce-scatter and
+ * all-gather (nexrSymAllReduce, nexrSymReduceScatter, nexrSymAllGather): additions only, no existing entry point or struct layout changed, so the version
  * stays. */
 #define NEXR_VERSION_MAJOR 0
 #define NEXR_VERSION_MINOR 3
@@ -634,8 +635,10 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const n
  * src/device/symmetric/all_reduce.hh:6-276) of nRanks ranks that live on ONE GPU, as one launch: peer loads
  * and peer stores only, no FIFO, no credits, no fences, n reads and n writes per element. inputs[r] /
  * outputs[r] are rank r's buffers of nElts elements (the reference's symmetric windows; here plain device
- * memory). Additions only: the ABI stays 0.3. The multicast kernels (…MC), the LL variants (AGxLL_R) and the
- * symmetric ReduceScatter_LD / AllGather_ST are not built.
+ * memory). Additions only: the ABI stays 0.3. Its siblings ncclSymRun_ReduceScatter_LD and
+ * ncclSymRun_AllGather_ST are nexrSymReduceScatter and nexrSymAllGather below. The all-reduce's multicast
+ * kernels (…MC) and LL variants (AGxLL_R) and the multicast forms (…MC) of the symmetric
+ * ReduceScatter_LD / AllGather_ST are not built, and the LL variants of those (…LL, …LLMC) neither.
  *
  * Ownership rule. n = nRanks (2..NEXR_SYM_MAX_RANKS), B = nBlocks (1..64, ncclSymMaxBlocks,
  * src/include/symmetric.h:8; 0 means 1), esz = 2 or 4, nBytes = nElts * esz. The geometry comes from rank 0's
@@ -681,6 +684,65 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const n
 NEXR_API nexrResult_t nexrSymAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
                                        size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
                                        int nBlocks, nexrStream_t stream);
+
+/*
+ * nexrSymReduceScatter — the symmetric reduce-scatter ncclSymRun_ReduceScatter_LD (reference
+ * src/device/symmetric/reduce_scatter.hh:6-241) of nRanks ranks that live on ONE GPU, as one launch: peer
+ * loads only, one store per element. inputs[r] holds nRanks * nElts elements, outputs[r] holds nElts.
+ * Additions only: the ABI stays 0.3.
+ *
+ * Rule. For every rank r and element e: acc = inputs[r][r * nElts + e], then
+ * acc = acc + inputs[(r + j) mod n][r * nElts + e] for j = 1..n-1 in that order, the accumulator as first
+ * operand (reduceDeep :23-89, reduceEnds :118-157; the kernel hands rank r its chunk as
+ * input + prim.rank*args->nElts, :237). Chunk r is folded from rank r's own input, not rank 0's. The sum is in
+ * fp32 for all three datatypes (ncclSymAccumType, symmetric/primitives.hh:426-434): fp16 and bf16 are widened
+ * exactly and rounded back once at the end, round-to-nearest-even, every NaN to 0x7fff; fp32 denormals are
+ * kept and nothing is contracted. The result goes to outputs[r][e] only. No ring or tree entry point folds in
+ * this order or with this accumulator (the ring's reduce-scatter is rank-ordered through FIFOs with one
+ * rounding per step).
+ *
+ * No ownership map. The reference's pass ladder and CTA count (reduce_scatter.hh:160-220: 16-byte packs,
+ * 4-byte packs, element-wise ends, chunks rounded to n * nBlocks) only spread one rank's elements over that
+ * rank's own warps; every path folds in the same order with the same accumulator. So no output byte depends
+ * on alignment or on nBlocks: the entry takes no nBlocks, and the device layout (every chunk cut from its byte
+ * 0 into 2048-byte pieces, 16-byte packs and single elements) is free.
+ *
+ * Barriers. The reference kernel arrives at a cross-rank barrier when it starts, waits for it before its first
+ * peer load, and arrives and waits again when it ends (reduce_scatter.hh:234-240). With every rank on one GPU
+ * both are the stream's order, as for nexrSymAllReduce.
+ *
+ * datatype is nexrFloat32, nexrFloat16 or nexrBfloat16 and devRedOp nexrDevSum (symmetric/generate.py:48-50;
+ * redOpArg is ignored). Aliasing: outputs[r] may be chunk r of any rank's input, that is the address
+ * inputs[s] + r * nElts * esz for some s (NCCL's in-place form is s = r): such an element is read by the one
+ * lane that writes it, before the write. Any other overlap of an output with an input or another output is
+ * undefined, as in the reference. Under nexrSemanticsShipped every add returns its first operand, so the
+ * result is rank r's own chunk through the two casts; nccl and fork are identical here. Stream-ordered: one
+ * launch, no workspace, and nothing of the caller's arrays is read after the call returns. nElts == 0
+ * succeeds without a launch. nexrInvalidArgument, before any device call: null arrays or entries, nRanks
+ * outside 2..NEXR_SYM_MAX_RANKS, another datatype or op, a pointer not aligned to esz, nRanks * nElts * esz
+ * overflowing size_t.
+ */
+NEXR_API nexrResult_t nexrSymReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                           size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                           nexrStream_t stream);
+
+/*
+ * nexrSymAllGather — the symmetric all-gather ncclSymRun_AllGather_ST (reference
+ * src/device/symmetric/all_gather.hh:5-177) of nRanks ranks that live on ONE GPU, as one launch: one load
+ * and n peer stores per byte. inputs[r] holds nBytes bytes, outputs[s] holds nRanks * nBytes.
+ *
+ * Rule. outputs[s][r * nBytes + b] = inputs[r][b] for every s, r and b: a bit copy at any byte alignment, so
+ * there is no datatype (the reference runs it on char, :173). When inputs[r] == outputs[r] + r * nBytes, rank
+ * r skips its own output: the reference's inPlace (:105, :33, :81), decided per rank. Any other overlap of an
+ * input with an output is undefined. The reference's pass ladder (:101-158) only picks the width of a copy,
+ * so the device layout is free here too. Its barriers (:170-176) are the stream's order.
+ *
+ * Stream-ordered: one launch, no workspace. nBytes == 0 succeeds without a launch. nexrInvalidArgument,
+ * before any device call: null arrays or entries, nRanks outside 2..NEXR_SYM_MAX_RANKS, nRanks * nBytes
+ * overflowing size_t.
+ */
+NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
+                                       nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

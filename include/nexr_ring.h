@@ -127,7 +127,8 @@ NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t comm, const void* const* 
  * ranks, device memory and every rank on one GPU: anything else is nexrInvalidUsage; an op other than ncclSum,
  * a datatype other than float32 / float16 / bfloat16, nBlocks outside 0..64 or more than NEXR_SYM_MAX_RANKS
  * ranks is nexrInvalidArgument; one rank takes the one-rank path and count == 0 succeeds. In place allowed.
- * The multicast and LL symmetric kernels, ReduceScatter_LD and AllGather_ST are not built. Measured on one
+ * ReduceScatter_LD and AllGather_ST are the two entries below; the multicast and LL symmetric kernels are not
+ * built. Measured on one
  * MI355X, a 4 MiB fp32 all-reduce per rank, p25-p75 of 20 calls on the host clock
  * (profiles/r14a_sym_all_reduce_probe.json): 0.018 / 0.026-0.031 /
  * 0.028-0.032 ms at 2 / 4 / 8 ranks against 0.140-0.191 / 0.335-0.377 / 1.030-1.119 for the host-sequenced ring
@@ -136,6 +137,35 @@ NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t comm, const void* const* 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetric(nexrRingComm_t comm, const void* const* sendbuffs,
                                                  void* const* recvbuffs, size_t count, int datatype, int op,
                                                  int nBlocks);
+
+/* ncclReduceScatter as the reference's symmetric kernel ReduceScatter_LD
+ * (src/device/symmetric/reduce_scatter.hh:6-241): ONE nexrSymReduceScatter (include/nexr.h) over every rank's
+ * buffers. sendbuffs[r] holds nRanks*recvcount elements, recvbuffs[r] receives chunk r folded from rank r's
+ * own input on (then r + 1, ..., wrapping), in fp32 with one rounding for fp16 / bf16: NOT the ring's bytes,
+ * whose fold is rank-ordered through FIFOs with a rounding per step. recvbuffs[r] may be chunk r of
+ * sendbuffs[r] (ncclReduceScatter's in-place form). Everything else is as nexrRingAllReduceSymmetric states
+ * it, through the same helper: the communicator's first stream and its wait, it touches no connection and no
+ * step counter, it leaves nexrRingCommGetQueued as it was, thread ranks on one GPU with device memory or
+ * anything else is nexrInvalidUsage, ncclSum of float32 / float16 / bfloat16 or nexrInvalidArgument, one rank
+ * takes the one-rank path, recvcount == 0 succeeds. Never chosen automatically. Measured on one MI355X, a 4 MiB
+ * fp32 input per rank, p25-p75 of 20 calls on the host clock (profiles/r15a_sym_rs_ag_probe.json):
+ * 0.014-0.020 / 0.020-0.025 / 0.022-0.025 ms at 2 / 4 / 8 ranks against 0.128-0.160 / 0.260-0.285 /
+ * 0.645-0.692 for the ring's own host-sequenced reduce-scatter and 0.129-0.160 / 0.243-0.254 / 0.516-0.560 in
+ * group launches, alternated call by call in one process, every call exact (tools/sym_rs_ag_probe.py). */
+NEXR_API nexrResult_t nexrRingReduceScatterSymmetric(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                     void* const* recvbuffs, size_t recvcount, int datatype,
+                                                     int op);
+
+/* ncclAllGather as the reference's symmetric kernel AllGather_ST (src/device/symmetric/all_gather.hh:5-177):
+ * ONE nexrSymAllGather of sendcount * sizeof(datatype) bytes per rank. recvbuffs[s] (nRanks*sendcount
+ * elements) receives every rank's sendbuff in rank order, a bit copy, so the bytes ARE the ring's all-gather's;
+ * a rank with sendbuffs[r] == recvbuffs[r] + r*sendcount elements is in place and skips its own output.
+ * Every datatype the ring's all-gather takes. The same helper and the same rules as the two calls above: it
+ * touches no connection and no step counter, it leaves nexrRingCommGetQueued as it was, anything but thread
+ * ranks on one GPU with device memory is nexrInvalidUsage, one rank takes the one-rank path, sendcount == 0
+ * succeeds. Never chosen automatically (tools/sym_rs_ag_probe.py). */
+NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                 void* const* recvbuffs, size_t sendcount, int datatype);
 
 /* The tree links of `rank` in this communicator's topology: *up (-1 at the root) and down[0..2]
  * (-1 when absent, children packed first as setTreeDown does). */

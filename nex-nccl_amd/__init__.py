@@ -89,6 +89,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrReduceCopyLL128StepsGroup",
                "nexrSimpleGroupWorkspaceBytes", "nexrReduceCopySimpleStepsGroup",
                "nexrSimpleGroupDirectWorkspaceBytes", "nexrReduceCopySimpleStepsGroupDirect", "nexrSymAllReduce",
+               "nexrSymReduceScatter", "nexrSymAllGather",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -319,6 +320,10 @@ def lib() -> ctypes.CDLL:
     L.nexrReduceCopySimpleStepsGroupDirect.restype = i32
     L.nexrSymAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, i32, vp]
     L.nexrSymAllReduce.restype = i32
+    L.nexrSymReduceScatter.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, vp]
+    L.nexrSymReduceScatter.restype = i32
+    L.nexrSymAllGather.argtypes = [i32, P(vp), P(vp), sz, vp]
+    L.nexrSymAllGather.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -800,6 +805,32 @@ def sym_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, d
                                 int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, int(n_blocks),
                                 ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrSymAllReduce")
+
+
+def sym_reduce_scatter(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                       dev_red_op: int = DevRedOp.Sum, red_op_arg: int = 0, stream: int = 0) -> None:
+    """The symmetric reduce-scatter ReduceScatter_LD of len(inputs) ranks on one GPU in one launch
+    (``nexrSymReduceScatter``): inputs[r] holds len(inputs) * ``n_elts`` elements of float32, float16 or
+    bfloat16, outputs[r] receives chunk r folded from rank r's own input on, in fp32 with one rounding. Sum
+    only. outputs[r] may be chunk r of any rank's input. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrSymReduceScatter(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                    int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                    ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrSymReduceScatter")
+
+
+def sym_all_gather(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int, stream: int = 0) -> None:
+    """The symmetric all-gather AllGather_ST of len(inputs) ranks on one GPU in one launch
+    (``nexrSymAllGather``): every outputs[s] receives the ``n_bytes`` bytes of inputs[r] at byte r * n_bytes, a
+    bit copy at any alignment; a rank whose input already lies at its place in its own output skips that
+    store. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrSymAllGather(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
+                                ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrSymAllGather")
 
 
 def ll_clean_slot(send_lines: Sequence[int], send_flags: Sequence[int], first_line: int, slot_lines: int,

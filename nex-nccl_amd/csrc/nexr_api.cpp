@@ -2218,6 +2218,63 @@ NEXR_API nexrResult_t nexrSymAllReduce(int nRanks, const void* const* inputs, vo
   return nexrSuccess;
 }
 
+// The one-shot grid of the symmetric reduce-scatter and all-gather: every chunk of chunkBytes is whole
+// 2048-byte pieces, groups of 64 16-byte packs and one tail item; a wave per item and rank, four waves per
+// workgroup; beyond the cap the kernels stride.
+static unsigned symChunkGrid(uint64_t chunkBytes, uint64_t esz, int nRanks) {
+  const uint64_t rem = chunkBytes % 2048;
+  const uint64_t perRank = chunkBytes / 2048 + (rem / 16 + 63) / 64 + (rem % 16 / esz ? 1 : 0);
+  const uint64_t items = perRank * (uint64_t)nRanks;
+  return (unsigned)std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+}
+
+NEXR_API nexrResult_t nexrSymReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                           size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                           nexrStream_t stream) {
+  (void)redOpArg;
+  if (!inputs || !outputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
+  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
+  const uint64_t esz = typeSize(datatype);
+  SymRsParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
+    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+  }
+  if (nElts > (size_t)-1 / esz / (size_t)nRanks) return nexrInvalidArgument;  // an input's nRanks * nElts * esz bytes
+  if (nElts == 0) return nexrSuccess;
+  p.chunkBytes = (uint64_t)nElts * esz;
+  p.nRanks = nRanks;
+  p.nFold = semantics() == nexrSemanticsShipped ? 1 : nRanks;  // SKIP_COMP: every add returns its first operand
+  NEXR_HIP(launch_sym_reduce_scatter(datatype, p, symChunkGrid(p.chunkBytes, esz, nRanks), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
+                                       nexrStream_t stream) {
+  if (!inputs || !outputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (nBytes > (size_t)-1 / (size_t)nRanks) return nexrInvalidArgument;  // an output's nRanks * nBytes bytes
+  SymAgParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+    // the reference's inPlace, per rank
+    if ((uintptr_t)inputs[r] == (uintptr_t)outputs[r] + (uintptr_t)r * nBytes) p.inPlace |= 1ull << r;
+  }
+  if (nBytes == 0) return nexrSuccess;
+  p.nBytes = nBytes;
+  p.nRanks = nRanks;
+  NEXR_HIP(launch_sym_all_gather(p, symChunkGrid(nBytes, 1, nRanks), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,
                                       size_t slotLines, nexrStream_t stream) {
   if (nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;

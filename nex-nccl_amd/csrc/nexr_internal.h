@@ -205,6 +205,28 @@ struct SymParams {
 static_assert(sizeof(SymParams) <= 4096, "kernel argument block");
 hipError_t launch_sym_all_reduce(int dt, const SymParams& p, unsigned grid, hipStream_t s);
 
+// The symmetric reduce-scatter and all-gather in one launch (nexrSymReduceScatter, nexrSymAllGather;
+// nexr_sym.hip). Chunk r of an input (reduce-scatter) or of an output (all-gather) starts at byte
+// r * chunkBytes / r * nBytes; the kernels cut every chunk from its byte 0 themselves.
+struct SymRsParams {
+  const char* in[NEXR_SYM_MAX_RANKS];  // nRanks * chunkBytes bytes each
+  char* out[NEXR_SYM_MAX_RANKS];       // chunkBytes bytes each
+  uint64_t chunkBytes;                 // nElts * esz
+  int nRanks;
+  int nFold;  // inputs that enter the fold from rank r's on: nRanks, or 1 under nexrSemanticsShipped
+};
+struct SymAgParams {
+  const char* in[NEXR_SYM_MAX_RANKS];  // nBytes bytes each
+  char* out[NEXR_SYM_MAX_RANKS];       // nRanks * nBytes bytes each
+  uint64_t nBytes;
+  uint64_t inPlace;  // bit r: inputs[r] == outputs[r] + r * nBytes, rank r's own output is not stored
+  int nRanks;
+};
+static_assert(NEXR_SYM_MAX_RANKS <= 64, "SymAgParams::inPlace is one bit per rank");
+static_assert(sizeof(SymRsParams) <= 4096 && sizeof(SymAgParams) <= 4096, "kernel argument block");
+hipError_t launch_sym_reduce_scatter(int dt, const SymRsParams& p, unsigned grid, hipStream_t s);
+hipError_t launch_sym_all_gather(const SymAgParams& p, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -1156,15 +1156,16 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
   return r;
 }
 
-// The symmetric all-reduce (nexrRingAllReduceSymmetric): one nexrSymAllReduce over every rank's buffers on the
-// communicator's first stream, then the wait every collective ends with (the completion word where the
-// communicator uses it, as runGroup; hipStreamSynchronize otherwise). No connection, no step counter and no
-// report of the last collective's mode is touched.
-nexrResult_t symAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                          int datatype, int op, int nBlocks) {
-  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
-  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
-  if (op != nexrSum || nBlocks < 0 || nBlocks > 64) return nexrInvalidArgument;
+// The symmetric collectives (nexrRingAllReduceSymmetric, nexrRingReduceScatterSymmetric,
+// nexrRingAllGatherSymmetric) behind their own argument checks: the buffers, the communicator's kind (thread
+// ranks, device memory, every rank on one GPU: nexrInvalidUsage otherwise), the empty call, the one-rank path,
+// then `launch` (one nexrSym* call over every rank's buffers) on the communicator's first stream and the wait
+// every collective ends with (the completion word where the communicator uses it, as runGroup;
+// hipStreamSynchronize otherwise). No connection, no step counter and no report of the last collective's mode
+// is touched. `count` is what the one-rank path copies.
+template <typename Launch>
+nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                           int datatype, Launch launch) {
   const int n = c->cfg.nRanks;
   for (int i = 0; i < n; i++)
     if (count != 0 && (!sendbuffs[i] || !recvbuffs[i])) return nexrInvalidArgument;
@@ -1177,13 +1178,12 @@ nexrResult_t symAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* c
   if (count == 0) return nexrSuccess;
   if (n == 1) {
     nexrDevRedOpFull red;
-    const nexrResult_t r = nexrHostToDevRedOp(&red, op, datatype, 1);
+    const nexrResult_t r = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
     return r != nexrSuccess ? r : oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, nexrTypeSize(datatype));
   }
   if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
   hipStream_t stream = c->streams[0];
-  nexrResult_t r = nexrSymAllReduce(n, sendbuffs, recvbuffs, count, datatype, nexrDevSum, 0, nBlocks,
-                                    (nexrStream_t)stream);
+  nexrResult_t r = launch(n, (nexrStream_t)stream);
   if (r != nexrSuccess) return r;
   uint32_t* done = c->stepWaitWord && !c->done.empty() ? c->done[0] : nullptr;
   if (done) {
@@ -1199,6 +1199,40 @@ nexrResult_t symAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* c
     }
   }
   return hipStreamSynchronize(stream) == hipSuccess ? nexrSuccess : nexrUnhandledCudaError;
+}
+
+static bool symDatatype(int datatype) {
+  return datatype == nexrFloat32 || datatype == nexrFloat16 || datatype == nexrBfloat16;
+}
+
+nexrResult_t symAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                          int datatype, int op, int nBlocks) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (!symDatatype(datatype) || op != nexrSum || nBlocks < 0 || nBlocks > 64) return nexrInvalidArgument;
+  return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int n, nexrStream_t stream) {
+    return nexrSymAllReduce(n, sendbuffs, recvbuffs, count, datatype, nexrDevSum, 0, nBlocks, stream);
+  });
+}
+
+nexrResult_t symReduceScatter(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs,
+                              size_t recvcount, int datatype, int op) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (!symDatatype(datatype) || op != nexrSum) return nexrInvalidArgument;
+  return symCollective(c, sendbuffs, recvbuffs, recvcount, datatype, [&](int n, nexrStream_t stream) {
+    return nexrSymReduceScatter(n, sendbuffs, recvbuffs, recvcount, datatype, nexrDevSum, 0, stream);
+  });
+}
+
+// A bit copy: every datatype the ring's all-gather takes, sendcount * esz bytes per rank.
+nexrResult_t symAllGather(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t sendcount,
+                          int datatype) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  const size_t esz = nexrTypeSize(datatype);
+  if (esz == 0 || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
+  if (sendcount > (size_t)-1 / esz) return nexrInvalidArgument;
+  return symCollective(c, sendbuffs, recvbuffs, sendcount, datatype, [&](int n, nexrStream_t stream) {
+    return nexrSymAllGather(n, sendbuffs, recvbuffs, sendcount * esz, stream);
+  });
 }
 
 // A communicator touches HIP when its FIFOs live in device memory or when any of its steps runs the
@@ -1353,6 +1387,19 @@ NEXR_API nexrResult_t nexrRingAllReduceSymmetric(nexrRingComm_t c, const void* c
                                                  int nBlocks) {
   DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
   return symAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+}
+
+NEXR_API nexrResult_t nexrRingReduceScatterSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
+                                                     void* const* recvbuffs, size_t recvcount, int datatype,
+                                                     int op) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symReduceScatter(c, sendbuffs, recvbuffs, recvcount, datatype, op);
+}
+
+NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
+                                                 void* const* recvbuffs, size_t sendcount, int datatype) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
 }
 
 NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t c, int* word) {

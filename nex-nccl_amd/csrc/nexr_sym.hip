@@ -1,6 +1,7 @@
-// nexr_sym.hip — the symmetric all-reduce RSxLD_AGxST as ONE launch (nexrSymAllReduce), for gfx950. Included
-// at the end of nexr_ll.hip behind nexr_simple.hip: the LL / LL128 object stays the one code object beside the
-// per-datatype ones.
+// nexr_sym.hip — the symmetric all-reduce RSxLD_AGxST as ONE launch (nexrSymAllReduce), for gfx950, and behind
+// it its siblings ReduceScatter_LD and AllGather_ST (nexrSymReduceScatter, nexrSymAllGather; their own comment
+// below). Included at the end of nexr_ll.hip behind nexr_simple.hip: the LL / LL128 object stays the one code
+// object beside the per-datatype ones.
 //
 // What it computes is ncclSymRun_AllReduce_RSxLD_AGxST (reference src/device/symmetric/all_reduce.hh:6-276)
 // on a communicator whose ranks all live on this GPU: every "peer window" is a plain device buffer, and the
@@ -48,6 +49,8 @@ typedef __attribute__((address_space(1))) const uint16_t g_cu16;
 typedef __attribute__((address_space(1))) uint16_t g_u16;
 typedef __attribute__((address_space(1))) const uint32_t g_cu32;
 typedef __attribute__((address_space(1))) uint32_t g_u32;
+typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+typedef __attribute__((address_space(1))) uint8_t g_u8;
 
 // ncclFromFloat's NaN (0x7fff) for a vector of fp16 / bf16 bit patterns; infBits = 0x7c00 / 0x7f80
 template <typename UV>
@@ -224,6 +227,201 @@ __global__ __launch_bounds__(kBlock) void sym_all_reduce_kernel(SymParams P) {
       sym_ends<D>(P, sym_owner(g, n), g * kSymEndGroup, lane);
     }
   }
+}
+
+// ---- ReduceScatter_LD and AllGather_ST (nexrSymReduceScatter, nexrSymAllGather) -----------------------------
+// ncclSymRun_ReduceScatter_LD (reference src/device/symmetric/reduce_scatter.hh:6-241) and
+// ncclSymRun_AllGather_ST (symmetric/all_gather.hh:5-177) on the same terms as the all-reduce above: ranks on
+// this GPU, the barriers at both ends (:234-240, :170-176) the stream's order. Rank r's chunk is a run of
+// chunkBytes bytes; nothing about it is shared between ranks, so the reference's pass ladder and CTA count
+// (reduce_scatter.hh:160-220) only spread a rank's elements over its own warps, and the layout here is free:
+// every chunk is cut from its byte 0, with no head, into
+//   pieces   whole 2048-byte pieces, two 16-byte packs per lane 1024 bytes apart (as sym_piece);
+//   packs    the remainder below 2048 bytes as 16-byte packs, one per lane, in groups of 64;
+//   tail     the last bytes below 16, one element (ReduceScatter) or one byte (AllGather) per lane.
+// An item is (rank, piece | group | tail), numbered with the rank fastest (item i is rank i mod n's item
+// i / n) so that a grid of few waves still touches every rank; a wave takes whole items, so the rank is
+// wave-uniform and the pointers are scalar loads. A chunk's phase is (inputs[s] + r * chunkBytes) mod 16,
+// which differs by rank and by count: every pack access is the unaligned-capable form. Offsets are 64-bit
+// (r * chunkBytes passes 4 GiB). No LDS, no cross-lane traffic, plain cache policy.
+
+// item i -> (i / n, i mod n) for a wave-uniform i: the 32-bit division whenever i fits
+__device__ __forceinline__ void sym_split(uint64_t i, uint32_t n, uint64_t* k, uint32_t* r) {
+  if (i >> 32) {
+    *k = i / n;
+    *r = (uint32_t)(i % n);
+  } else {
+    *k = (uint32_t)i / n;
+    *r = (uint32_t)i % n;
+  }
+}
+
+// K peers' packs of one wave, straight-line: the K * kPacks loads (kPacks packs per lane, kStride bytes apart,
+// at byte `off` of the inputs of ranks r, r + 1, ...), then the adds, the accumulator first. kFirst: the first
+// of them is the chunk's own rank and starts the accumulator. Bits is the pack as loaded, LoadPtr its access
+// type, Acc its fp32 accumulator.
+template <int K, bool kFirst, typename Acc, typename Bits, typename LoadPtr, int kPacks, int kStride, typename Widen>
+__device__ __forceinline__ void sym_fold_k(const SymRsParams& P, uint32_t& r, uint64_t off, Widen widen,
+                                           Acc (&acc)[kPacks]) {
+  const uint32_t n = (uint32_t)P.nRanks;
+  Bits v[K][kPacks];
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const char* p = P.in[r] + off;  // scalar load of the pointer
+#pragma unroll
+    for (int u = 0; u < kPacks; u++) v[j][u] = *(LoadPtr*)(p + u * kStride);
+    r = r + 1 == n ? 0 : r + 1;
+  }
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+#pragma unroll
+    for (int u = 0; u < kPacks; u++) {
+      const Acc a = widen(v[j][u]);
+      if (kFirst && j == 0) acc[u] = a;
+      else acc[u] = acc[u] + a;
+    }
+  }
+}
+
+// The fold of a chunk's packs from rank `first` on: a wave-uniform switch on the number of peers, so that
+// every case is the loads of up to kSymPeers peers and then the adds with no branch between them; beyond
+// kSymPeers ranks the fold goes on in groups of kSymPeers, the last part in groups of 4, 2 and 1.
+template <typename Acc, typename Bits, typename LoadPtr, int kPacks, int kStride, typename Widen>
+__device__ __forceinline__ void sym_fold(const SymRsParams& P, uint32_t first, uint64_t off, Widen widen,
+                                         Acc (&acc)[kPacks]) {
+  static_assert(kSymPeers == 8, "the switch below");
+  uint32_t r = first, left = (uint32_t)P.nFold;
+#define NEXR_SYM_CASE(K)                                                                 \
+  case K:                                                                                \
+    sym_fold_k<K, true, Acc, Bits, LoadPtr, kPacks, kStride>(P, r, off, widen, acc);     \
+    left -= K;                                                                           \
+    break;
+  switch (left < kSymPeers ? left : (uint32_t)kSymPeers) {
+    NEXR_SYM_CASE(1) NEXR_SYM_CASE(2) NEXR_SYM_CASE(3) NEXR_SYM_CASE(4)
+    NEXR_SYM_CASE(5) NEXR_SYM_CASE(6) NEXR_SYM_CASE(7) NEXR_SYM_CASE(8)
+  }
+#undef NEXR_SYM_CASE
+  for (; left >= kSymPeers; left -= kSymPeers)
+    sym_fold_k<kSymPeers, false, Acc, Bits, LoadPtr, kPacks, kStride>(P, r, off, widen, acc);
+  if (left & 4) sym_fold_k<4, false, Acc, Bits, LoadPtr, kPacks, kStride>(P, r, off, widen, acc);
+  if (left & 2) sym_fold_k<2, false, Acc, Bits, LoadPtr, kPacks, kStride>(P, r, off, widen, acc);
+  if (left & 1) sym_fold_k<1, false, Acc, Bits, LoadPtr, kPacks, kStride>(P, r, off, widen, acc);
+}
+
+// ReduceScatter_LD: outputs[r][e] = in[r][r * nElts + e] + in[r + 1][...] + ..., the accumulator first, in
+// fp32, rounded once (reduceDeep :23-89, reduceEnds :118-157; the chunk of rank r at :237). A lane loads its
+// bytes from every input before it stores them, so outputs[r] may be chunk r of any rank's input.
+template <int D>
+__global__ __launch_bounds__(kBlock) void sym_reduce_scatter_kernel(SymRsParams P) {
+  using S = Sym<D>;
+  using E = typename S::E;
+  using A16 = typename S::A16;
+  using ELoad = typename std::conditional<S::kEsz == 2, g_cu16, g_cu32>::type;
+  using EStore = typename std::conditional<S::kEsz == 2, g_u16, g_u32>::type;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t n = (uint32_t)P.nRanks;
+  const uint64_t chunk = P.chunkBytes;
+  const uint64_t pieces = chunk / kSymPiece16;
+  const uint32_t rem = (uint32_t)(chunk % kSymPiece16), packs = rem / 16u, tail = (rem % 16u) / S::kEsz;
+  const uint32_t groups = (packs + 63u) / 64u;
+  const uint64_t nItems = (pieces + groups + (tail ? 1u : 0u)) * n;
+  const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
+  const auto widen16 = [](u32x4 x) { return S::widen16(x); };
+  for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < nItems; it += nWaves) {
+    uint64_t k;
+    uint32_t r;
+    sym_split(it, n, &k, &r);
+    const uint64_t at = (uint64_t)r * chunk;  // chunk r of every input
+    if (k < pieces) {
+      const uint64_t o = k * kSymPiece16 + lane * 16u;
+      A16 acc[2];
+      sym_fold<A16, u32x4, g_cu32x4_a1, 2, kSymPiece16 / 2>(P, r, at + o, widen16, acc);
+      char* q = P.out[r] + o;
+      *(g_u32x4_a1*)(q) = S::narrow16(acc[0]);
+      *(g_u32x4_a1*)(q + kSymPiece16 / 2) = S::narrow16(acc[1]);
+    } else if (k < pieces + groups) {
+      const uint32_t p = (uint32_t)(k - pieces) * 64u + lane;
+      if (p < packs) {
+        const uint64_t o = pieces * kSymPiece16 + p * 16u;
+        A16 acc[1];
+        sym_fold<A16, u32x4, g_cu32x4_a1, 1, 0>(P, r, at + o, widen16, acc);
+        *(g_u32x4_a1*)(P.out[r] + o) = S::narrow16(acc[0]);
+      }
+    } else if (lane < tail) {
+      const uint64_t o = pieces * kSymPiece16 + packs * 16u + lane * S::kEsz;
+      float acc[1];
+      sym_fold<float, E, ELoad, 1, 0>(P, r, at + o, [](E x) { return S::widen1(x); }, acc);
+      *(EStore*)(P.out[r] + o) = S::narrow1(acc[0]);
+    }
+  }
+}
+
+// AllGather_ST: outputs[s][r * nBytes + b] = inputs[r][b], a bit copy (the reference runs it on char, :173).
+// One load of the item, then a store to every rank from r on; rank r's own output is skipped when its input
+// already lies there (the reference's inPlace, :105, :33, :81: bit r of P.inPlace).
+__global__ __launch_bounds__(kBlock) void sym_all_gather_kernel(SymAgParams P) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t n = (uint32_t)P.nRanks;
+  const uint64_t chunk = P.nBytes;
+  const uint64_t pieces = chunk / kSymPiece16;
+  const uint32_t rem = (uint32_t)(chunk % kSymPiece16), packs = rem / 16u, tail = rem % 16u;
+  const uint32_t groups = (packs + 63u) / 64u;
+  const uint64_t nItems = (pieces + groups + (tail ? 1u : 0u)) * n;
+  const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
+  for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < nItems; it += nWaves) {
+    uint64_t k;
+    uint32_t r;
+    sym_split(it, n, &k, &r);
+    const uint64_t at = (uint64_t)r * chunk;  // chunk r of every output
+    const uint32_t skip = (uint32_t)(P.inPlace >> r) & 1u;
+    uint32_t s = skip ? (r + 1 == n ? 0 : r + 1) : r;  // out[r], out[r + 1], ...
+    if (k < pieces) {
+      const uint64_t o = k * kSymPiece16 + lane * 16u;
+      const char* p = P.in[r] + o;
+      const u32x4 v0 = *(g_cu32x4_a1*)(p), v1 = *(g_cu32x4_a1*)(p + kSymPiece16 / 2);
+#pragma unroll 4
+      for (uint32_t j = skip; j < n; j++) {
+        char* q = P.out[s] + at + o;
+        *(g_u32x4_a1*)(q) = v0;
+        *(g_u32x4_a1*)(q + kSymPiece16 / 2) = v1;
+        s = s + 1 == n ? 0 : s + 1;
+      }
+    } else if (k < pieces + groups) {
+      const uint32_t i = (uint32_t)(k - pieces) * 64u + lane;
+      if (i < packs) {
+        const uint64_t o = pieces * kSymPiece16 + i * 16u;
+        const u32x4 v = *(g_cu32x4_a1*)(P.in[r] + o);
+        for (uint32_t j = skip; j < n; j++) {
+          *(g_u32x4_a1*)(P.out[s] + at + o) = v;
+          s = s + 1 == n ? 0 : s + 1;
+        }
+      }
+    } else if (lane < tail) {
+      const uint64_t o = pieces * kSymPiece16 + packs * 16u + lane;
+      const uint8_t v = *(g_cu8*)(P.in[r] + o);
+      for (uint32_t j = skip; j < n; j++) {
+        *(g_u8*)(P.out[s] + at + o) = v;
+        s = s + 1 == n ? 0 : s + 1;
+      }
+    }
+  }
+}
+
+hipError_t launch_sym_reduce_scatter(int dt, const SymRsParams& p, unsigned grid, hipStream_t s) {
+  const void* fn = dt == nexrFloat32    ? (const void*)&sym_reduce_scatter_kernel<nexrFloat32>
+                   : dt == nexrFloat16  ? (const void*)&sym_reduce_scatter_kernel<nexrFloat16>
+                   : dt == nexrBfloat16 ? (const void*)&sym_reduce_scatter_kernel<nexrBfloat16>
+                                        : nullptr;
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {const_cast<SymRsParams*>(&p)};
+  return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, s);
+}
+
+hipError_t launch_sym_all_gather(const SymAgParams& p, unsigned grid, hipStream_t s) {
+  void* args[] = {const_cast<SymAgParams*>(&p)};
+  return hipLaunchKernel((const void*)&sym_all_gather_kernel, dim3(grid), dim3(kBlock), args, 0, s);
 }
 
 hipError_t launch_sym_all_reduce(int dt, const SymParams& p, unsigned grid, hipStream_t s) {

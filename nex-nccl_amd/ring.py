@@ -20,6 +20,7 @@ RING_LIB_PATH = os.path.join(_HERE, "libnexr_ring.so")
 EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
                     "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrRingAllReduceSymmetric",
+                    "nexrRingReduceScatterSymmetric", "nexrRingAllGatherSymmetric",
                     "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
@@ -71,6 +72,8 @@ def _bind_ring(L: ctypes.CDLL) -> None:
                         ("nexrPeerRingBroadcast", [i32])):
         getattr(L, name).argtypes = [vp, vp, vp, sz, i32] + extra
     L.nexrRingAllReduceSymmetric.argtypes = [vp, arr, arr, sz, i32, i32, i32]
+    L.nexrRingReduceScatterSymmetric.argtypes = [vp, arr, arr, sz, i32, i32]
+    L.nexrRingAllGatherSymmetric.argtypes = [vp, arr, arr, sz, i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
@@ -228,6 +231,24 @@ class RingComm:
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrRingAllReduceSymmetric(self._h, s, r, int(count), int(datatype), int(op), int(n_blocks)),
                "nexrRingAllReduceSymmetric")
+
+    def reduce_scatter_symmetric(self, sendbuffs, recvbuffs, recvcount: int, datatype: int, op: int) -> None:
+        """ncclReduceScatter as the reference's symmetric kernel ReduceScatter_LD in ONE launch
+        (nexrRingReduceScatterSymmetric): recvbuffs[r] receives chunk r of the n_ranks * recvcount elements,
+        folded from rank r's own input on, in fp32 with one rounding. In place on chunk r of sendbuffs[r]
+        allowed. Usage and argument rules as all_reduce_symmetric; queued() stays as it was."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingReduceScatterSymmetric(self._h, s, r, int(recvcount), int(datatype), int(op)),
+               "nexrRingReduceScatterSymmetric")
+
+    def all_gather_symmetric(self, sendbuffs, recvbuffs, sendcount: int, datatype: int) -> None:
+        """ncclAllGather as the reference's symmetric kernel AllGather_ST in ONE launch
+        (nexrRingAllGatherSymmetric): every recvbuffs[s] receives every rank's sendcount elements in rank
+        order, a bit copy; a rank whose sendbuff is its own place in its recvbuff skips that store. Usage rules
+        as all_reduce_symmetric; queued() stays as it was."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllGatherSymmetric(self._h, s, r, int(sendcount), int(datatype)),
+               "nexrRingAllGatherSymmetric")
 
     def send_recv(self, sendbuffs, send_peers, recvbuffs, recv_peers, nbytes: int) -> None:
         """ncclSend/ncclRecv of every rank in one group: rank r sends nbytes of sendbuffs[r] to
