@@ -636,9 +636,10 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const n
  * and peer stores only, no FIFO, no credits, no fences, n reads and n writes per element. inputs[r] /
  * outputs[r] are rank r's buffers of nElts elements (the reference's symmetric windows; here plain device
  * memory). Additions only: the ABI stays 0.3. Its siblings ncclSymRun_ReduceScatter_LD and
- * ncclSymRun_AllGather_ST are nexrSymReduceScatter and nexrSymAllGather below. The all-reduce's multicast
- * kernels (…MC) and LL variants (AGxLL_R) and the multicast forms (…MC) of the symmetric
- * ReduceScatter_LD / AllGather_ST are not built, and the LL variants of those (…LL, …LLMC) neither.
+ * ncclSymRun_AllGather_ST are nexrSymReduceScatter and nexrSymAllGather below, and the family's LL members
+ * (AllReduce_AGxLL_R, ReduceScatter_LL, AllGather_LL) the nexrSymLL* calls behind them. The all-reduce's
+ * multicast kernels (…MC, …LLMC) and the multicast forms (…MC) of the symmetric
+ * ReduceScatter_LD / AllGather_ST are not built.
  *
  * Ownership rule. n = nRanks (2..NEXR_SYM_MAX_RANKS), B = nBlocks (1..64, ncclSymMaxBlocks,
  * src/include/symmetric.h:8; 0 means 1), esz = 2 or 4, nBytes = nElts * esz. The geometry comes from rank 0's
@@ -743,6 +744,98 @@ NEXR_API nexrResult_t nexrSymReduceScatter(int nRanks, const void* const* inputs
  */
 NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
                                        nexrStream_t stream);
+
+/*
+ * nexrSymLLAllReduce, nexrSymLLReduceScatter, nexrSymLLAllGather — the LL members of the symmetric family,
+ * ncclSymRun_AllReduce_AGxLL_R (reference src/device/symmetric/all_reduce.hh:356-428),
+ * ncclSymRun_ReduceScatter_LL (reduce_scatter.hh:320-388) and ncclSymRun_AllGather_LL (all_gather.hh:256-363),
+ * which the reference runs for small messages, of nRanks ranks that live on ONE GPU, each as one launch. They
+ * sit on ncclSymPrims' sendLL / bcastLL / recvLL / recvReduceLL / endLL (symmetric/primitives.hh:212-377): data
+ * travels as 16-byte lines {lo, flag, hi, flag} through per-rank windows. Additions only: the ABI stays 0.3.
+ * Opt-in like their siblings: nothing chooses them automatically. n = nRanks (2..NEXR_SYM_MAX_RANKS), esz = 2
+ * or 4.
+ *
+ * AllReduce (AGxLL_R). inputs[r] / outputs[r] hold nElts elements. For every element e and every rank s:
+ * acc = inputs[0][e], then acc = acc + inputs[j][e] for j = 1..n-1 in rank order, the accumulator as first
+ * operand (recvReduceLL folds rank 0 first on every rank, primitives.hh:349-377), in fp32 for fp32, fp16 and
+ * bf16 (ncclSymAccumType, primitives.hh:425-434): fp16 and bf16 are widened exactly and rounded back once,
+ * round-to-nearest-even, every NaN to 0x7fff; fp32 denormals are kept and nothing is contracted. The result is
+ * stored to outputs[s][e]. Beyond 8 ranks the reference folds in groups of 8; the order stays rank order. There
+ * is no ownership map: no byte depends on alignment, on nBlocks or on the 8-byte pack. These are not
+ * nexrSymAllReduce's bytes (owner first) and not the ring's or tree's (a rounding per step).
+ *
+ * ReduceScatter (LL). inputs[r] holds n * nElts elements, outputs[r] holds nElts. outputs[r][e] is the same
+ * rank-0-first fp32 fold of inputs[j][r * nElts + e], j = 0..n-1. For chunks r >= 1 and n >= 3 these are not
+ * nexrSymReduceScatter's bytes (chunk r from rank r on).
+ *
+ * AllGather (LL). inputs[r] holds nBytes bytes, outputs[s] holds n * nBytes.
+ * outputs[s][r * nBytes + b] = inputs[r][b]: a bit copy at any byte alignment, without a datatype.
+ *
+ * Common. datatype is nexrFloat32, nexrFloat16 or nexrBfloat16 and devRedOp nexrDevSum (symmetric/generate.py;
+ * redOpArg is ignored). Under nexrSemanticsShipped every add returns its first operand: the all-reduce is
+ * rank 0's input through the two casts and the reduce-scatter chunk r of rank 0's input; nccl and fork are
+ * identical here. Allowed aliasing: outputs[r] == inputs[r] (all-reduce), outputs[r] == inputs[r] +
+ * r * nElts * esz (reduce-scatter), inputs[r] == outputs[r] + r * nBytes (all-gather): a lane loads its pack
+ * before it stores it. Any other overlap is undefined. The reference's 8-byte-aligned and element-wise paths
+ * (all_reduce.hh:369-423) only pick access widths: the entries take any element-aligned pointers, the
+ * all-gather any byte-aligned ones.
+ *
+ * Windows. windows[r] is rank r's window: caller-owned device memory, 16-byte aligned, at least
+ * nexrSymLLWindowBytes(nRanks, B) bytes, zeroed once before its first use, touched by nothing else.
+ *   header    uint32_t llEpoch[64] (as ncclSymDevBase, src/include/symmetric.h:20-31), padded to
+ *             NEXR_SYM_LL_HEADER_BYTES: word b is block b's stored epoch, the next flag minus 2;
+ *   lines     from byte NEXR_SYM_LL_HEADER_BYTES: per block b two buffers, for even and odd flags, of
+ *             n * NEXR_SYM_LL_ROUND_PACKS 16-byte lines each; block b's start at line
+ *             2 * b * n * NEXR_SYM_LL_ROUND_PACKS, whatever B is. Nothing else about the line area is fixed.
+ * A group of windows serves ONE nRanks (the line layout depends on it; nBlocks may change from call to call):
+ * zero all of them before using them with another. All windows of a group carry equal epoch words. Zeroing ALL windows of a group (header and lines) resets it;
+ * the words may also be set by plain copies while every window's lines are consistent with them (zero lines
+ * are: flags 0 and 1 never occur, so a zeroed window matches nothing).
+ *
+ * Protocol. B = nBlocks (1..64, 0 means 1). The grid is n * B teams of one workgroup, team w = (rank w mod n,
+ * block w / n). With P = ceil(bytes / 8) 8-byte packs (bytes = nElts * esz, the chunk's for the
+ * reduce-scatter, nBytes for the all-gather), team (r, b) takes floor(P / B) packs plus one for b < P mod B,
+ * consecutive from block 0 on, in rounds of at most NEXR_SYM_LL_ROUND_PACKS packs. Round k of a call uses flag
+ * f = llEpoch[b] + 2 + k in 32 bits, and after 0xffffffff the next flag is 2; when the team ends it stores
+ * (next flag - 2) back. A block without packs runs no round and leaves its word. In a round the team puts pack
+ * t of its round as the line {lo, f, hi, f} into slot r * NEXR_SYM_LL_ROUND_PACKS + t of block b's parity-f
+ * buffer in EVERY window, its own included (the reduce-scatter: the pack of chunk s into window s), then polls
+ * the n lines of each of its packs in its own window, and ends the round with a team barrier (endLL): no lane
+ * of a rank sends round k + 1 before its team has read round k, which is what makes two buffers enough. In a
+ * round whose flag is >= 0xfffffffe the team zeroes that parity's whole buffer after its reads, with
+ * system-coherent 16-byte stores that every wave drains before the barrier, so that no line of the cycle that
+ * ends can satisfy a poll of the next.
+ *
+ * status and timeoutUs are nexrReduceCopyLL's: a line that does not arrive within timeoutUs (0 = 1 s) sets
+ * *status = 1 (optional device or host-mapped word); a non-zero *status ends the other polls early. The team
+ * of a poll that gave up skips its later polls and stores but reaches all its barriers: the launch always
+ * ends. After a non-zero status the outputs and the windows are undefined and the caller zeroes ALL windows
+ * before the next call.
+ *
+ * Stream-ordered, one launch. A count of 0 succeeds without a launch and leaves the epoch words alone.
+ * nexrInvalidArgument, before any device call: null arrays or entries; nRanks outside
+ * 2..NEXR_SYM_MAX_RANKS; another datatype or op; an input or output not aligned to esz or a window not aligned
+ * to 16; nBlocks outside 0..64; windowBytes below nexrSymLLWindowBytes(nRanks, B); nElts * esz or nBytes (for
+ * the reduce-scatter n * nElts * esz too) at or above 2^31 (the reference's int nElts: these are the
+ * small-message kernels); an overflowing product. nexrInvalidUsage, without a launch: the grid of n * B
+ * workgroups is not resident as a whole on the current device (teams poll each other, so a queued team could
+ * keep resident ones waiting until their timeouts).
+ */
+#define NEXR_SYM_LL_HEADER_BYTES 256 /* uint32_t llEpoch[64] */
+#define NEXR_SYM_LL_ROUND_PACKS 256  /* 8-byte packs per team and round */
+#define NEXR_SYM_LL_MAX_BLOCKS 64
+NEXR_API nexrResult_t nexrSymLLWindowBytes(int nRanks, int maxBlocks, size_t* bytes);
+NEXR_API nexrResult_t nexrSymLLAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                         int datatype, int devRedOp, uint64_t redOpArg, void* const* windows,
+                                         size_t windowBytes, int nBlocks, uint32_t* status, uint32_t timeoutUs,
+                                         nexrStream_t stream);
+NEXR_API nexrResult_t nexrSymLLReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                             size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                             void* const* windows, size_t windowBytes, int nBlocks,
+                                             uint32_t* status, uint32_t timeoutUs, nexrStream_t stream);
+NEXR_API nexrResult_t nexrSymLLAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
+                                         void* const* windows, size_t windowBytes, int nBlocks, uint32_t* status,
+                                         uint32_t timeoutUs, nexrStream_t stream);
 
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines

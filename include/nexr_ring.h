@@ -127,8 +127,8 @@ NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t comm, const void* const* 
  * ranks, device memory and every rank on one GPU: anything else is nexrInvalidUsage; an op other than ncclSum,
  * a datatype other than float32 / float16 / bfloat16, nBlocks outside 0..64 or more than NEXR_SYM_MAX_RANKS
  * ranks is nexrInvalidArgument; one rank takes the one-rank path and count == 0 succeeds. In place allowed.
- * ReduceScatter_LD and AllGather_ST are the two entries below; the multicast and LL symmetric kernels are not
- * built. Measured on one
+ * ReduceScatter_LD and AllGather_ST are the two entries below and the family's LL members the three
+ * ...SymmetricLL entries behind them; the multicast symmetric kernels are not built. Measured on one
  * MI355X, a 4 MiB fp32 all-reduce per rank, p25-p75 of 20 calls on the host clock
  * (profiles/r14a_sym_all_reduce_probe.json): 0.018 / 0.026-0.031 /
  * 0.028-0.032 ms at 2 / 4 / 8 ranks against 0.140-0.191 / 0.335-0.377 / 1.030-1.119 for the host-sequenced ring
@@ -166,6 +166,34 @@ NEXR_API nexrResult_t nexrRingReduceScatterSymmetric(nexrRingComm_t comm, const 
  * succeeds. Never chosen automatically (tools/sym_rs_ag_probe.py). */
 NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t comm, const void* const* sendbuffs,
                                                  void* const* recvbuffs, size_t sendcount, int datatype);
+
+/* ncclAllReduce, ncclReduceScatter and ncclAllGather as the reference's symmetric LL kernels AllReduce_AGxLL_R,
+ * ReduceScatter_LL and AllGather_LL (src/device/symmetric/all_reduce.hh:356-428, reduce_scatter.hh:320-388,
+ * all_gather.hh:256-363), which it runs for small messages: ONE nexrSymLLAllReduce / nexrSymLLReduceScatter /
+ * nexrSymLLAllGather (include/nexr.h: the rank-0-first fp32 fold, the windows, the protocol) over every rank's
+ * buffers, through the helper of the three entries above, so their usage rules hold: the communicator's first
+ * stream and its wait, thread ranks on one GPU with device memory or nexrInvalidUsage, ncclSum of float32 /
+ * float16 / bfloat16 (the all-gather: every datatype the ring's takes) or nexrInvalidArgument, one rank takes
+ * the one-rank path, a count of 0 succeeds, no connection and no step counter is touched and
+ * nexrRingCommGetQueued stays as it was. The reduce-scatter's bytes are NOT nexrRingReduceScatterSymmetric's
+ * (chunk r is folded from rank 0 on, not from rank r on) and the all-reduce's NOT nexrRingAllReduceSymmetric's
+ * (rank 0 first, not owner first); neither are the ring's (fp32 accumulator, one rounding). In-place forms as
+ * ncclAllReduce / ncclReduceScatter / ncclAllGather define them. The communicator allocates its n windows,
+ * zeroed and sized for 16 blocks, on first use and frees them when it is destroyed: nBlocks is 0..16 (0 means
+ * 1), anything else nexrInvalidArgument; a message of 2 GiB or more per rank is nexrInvalidArgument and a grid
+ * that is not resident as a whole nexrInvalidUsage, as nexrSymLL* return them. The timeout is the
+ * communicator's timeoutMs and the status word the one its LL paths report in: a call whose kernel reports a
+ * timeout returns nexrInternalError, as those paths do, and the windows are zeroed again before the next
+ * symmetric LL call. Never chosen automatically (tools/sym_ll_probe.py). */
+NEXR_API nexrResult_t nexrRingAllReduceSymmetricLL(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                   void* const* recvbuffs, size_t count, int datatype, int op,
+                                                   int nBlocks);
+NEXR_API nexrResult_t nexrRingReduceScatterSymmetricLL(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                       void* const* recvbuffs, size_t recvcount, int datatype,
+                                                       int op, int nBlocks);
+NEXR_API nexrResult_t nexrRingAllGatherSymmetricLL(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                   void* const* recvbuffs, size_t sendcount, int datatype,
+                                                   int nBlocks);
 
 /* The tree links of `rank` in this communicator's topology: *up (-1 at the root) and down[0..2]
  * (-1 when absent, children packed first as setTreeDown does). */

@@ -89,7 +89,8 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrLLGroupWorkspaceBytes", "nexrReduceCopyLLStepsGroup", "nexrReduceCopyLL128StepsGroup",
                "nexrSimpleGroupWorkspaceBytes", "nexrReduceCopySimpleStepsGroup",
                "nexrSimpleGroupDirectWorkspaceBytes", "nexrReduceCopySimpleStepsGroupDirect", "nexrSymAllReduce",
-               "nexrSymReduceScatter", "nexrSymAllGather",
+               "nexrSymReduceScatter", "nexrSymAllGather", "nexrSymLLWindowBytes", "nexrSymLLAllReduce",
+               "nexrSymLLReduceScatter", "nexrSymLLAllGather",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -324,6 +325,15 @@ def lib() -> ctypes.CDLL:
     L.nexrSymReduceScatter.restype = i32
     L.nexrSymAllGather.argtypes = [i32, P(vp), P(vp), sz, vp]
     L.nexrSymAllGather.restype = i32
+    L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
+    L.nexrSymLLWindowBytes.restype = i32
+    L.nexrSymLLAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, P(vp), sz, i32, vp, ctypes.c_uint32, vp]
+    L.nexrSymLLAllReduce.restype = i32
+    L.nexrSymLLReduceScatter.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, P(vp), sz, i32, vp, ctypes.c_uint32,
+                                         vp]
+    L.nexrSymLLReduceScatter.restype = i32
+    L.nexrSymLLAllGather.argtypes = [i32, P(vp), P(vp), sz, P(vp), sz, i32, vp, ctypes.c_uint32, vp]
+    L.nexrSymLLAllGather.restype = i32
     L.nexrLLCleanSlot.argtypes = [i32, P(vp), P(ctypes.c_uint32), sz, sz, vp]
     L.nexrLLCleanSlot.restype = i32
     L.nexrTypeSize.argtypes = [i32]
@@ -831,6 +841,73 @@ def sym_all_gather(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int, 
     rc = lib().nexrSymAllGather(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
                                 ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrSymAllGather")
+
+
+SYM_LL_HEADER_BYTES = 256  # NEXR_SYM_LL_HEADER_BYTES
+SYM_LL_ROUND_PACKS = 256   # NEXR_SYM_LL_ROUND_PACKS
+SYM_LL_MAX_BLOCKS = 64     # NEXR_SYM_LL_MAX_BLOCKS
+
+
+def sym_ll_window_bytes(n_ranks: int, max_blocks: int) -> int:
+    """Bytes of one rank's window of the symmetric LL calls for ``n_ranks`` ranks and up to ``max_blocks`` blocks
+    (``nexrSymLLWindowBytes``): the header of 64 epoch words, then per block two buffers of
+    n_ranks * SYM_LL_ROUND_PACKS 16-byte lines. A window is device memory, zeroed once."""
+    out = ctypes.c_size_t()
+    _check(lib().nexrSymLLWindowBytes(int(n_ranks), int(max_blocks), ctypes.byref(out)), "nexrSymLLWindowBytes")
+    return out.value
+
+
+def _sym_ll_tail(windows, window_bytes, n_blocks, status, timeout_us, stream):
+    return (_ptr_array(windows), int(window_bytes), int(n_blocks), ctypes.c_void_p(int(status)) if status else None,
+            int(timeout_us), ctypes.c_void_p(int(stream)) if stream else None)
+
+
+def sym_ll_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                      windows: Sequence[int], window_bytes: int, n_blocks: int = 0, status: int = 0,
+                      timeout_us: int = 0, dev_red_op: int = DevRedOp.Sum, red_op_arg: int = 0,
+                      stream: int = 0) -> None:
+    """The symmetric LL all-reduce AllReduce_AGxLL_R of len(inputs) ranks on one GPU in one launch
+    (``nexrSymLLAllReduce``): every rank's packs travel as flagged 16-byte lines into every rank's window, and
+    every output element is inputs[0] + inputs[1] + ... in rank order, in fp32 with one rounding. float32,
+    float16 or bfloat16, Sum only, fewer than 2 GiB. ``windows[r]`` is rank r's zeroed window of
+    ``window_bytes`` >= sym_ll_window_bytes(n, n_blocks); ``status`` / ``timeout_us`` as reduce_copy_ll. In
+    place allowed. Stream-ordered."""
+    if len(inputs) != len(outputs) or len(inputs) != len(windows):
+        raise NexrError(Result.InvalidArgument, "one input, one output and one window per rank")
+    rc = lib().nexrSymLLAllReduce(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                  int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                  *_sym_ll_tail(windows, window_bytes, n_blocks, status, timeout_us, stream))
+    _check(rc, "nexrSymLLAllReduce")
+
+
+def sym_ll_reduce_scatter(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                          windows: Sequence[int], window_bytes: int, n_blocks: int = 0, status: int = 0,
+                          timeout_us: int = 0, dev_red_op: int = DevRedOp.Sum, red_op_arg: int = 0,
+                          stream: int = 0) -> None:
+    """The symmetric LL reduce-scatter ReduceScatter_LL (``nexrSymLLReduceScatter``): inputs[r] holds
+    len(inputs) * ``n_elts`` elements, outputs[r] receives chunk r folded from rank 0's input on in rank order,
+    in fp32 with one rounding. outputs[r] may be chunk r of inputs[r]. Windows, status and timeout as
+    sym_ll_all_reduce. Stream-ordered."""
+    if len(inputs) != len(outputs) or len(inputs) != len(windows):
+        raise NexrError(Result.InvalidArgument, "one input, one output and one window per rank")
+    rc = lib().nexrSymLLReduceScatter(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts),
+                                      int(datatype), int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                      *_sym_ll_tail(windows, window_bytes, n_blocks, status, timeout_us, stream))
+    _check(rc, "nexrSymLLReduceScatter")
+
+
+def sym_ll_all_gather(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int, windows: Sequence[int],
+                      window_bytes: int, n_blocks: int = 0, status: int = 0, timeout_us: int = 0,
+                      stream: int = 0) -> None:
+    """The symmetric LL all-gather AllGather_LL (``nexrSymLLAllGather``): every outputs[s] receives the
+    ``n_bytes`` bytes of inputs[r] at byte r * n_bytes, a bit copy at any alignment, through the windows'
+    lines. inputs[r] may lie at its place in outputs[r]. Windows, status and timeout as sym_ll_all_reduce.
+    Stream-ordered."""
+    if len(inputs) != len(outputs) or len(inputs) != len(windows):
+        raise NexrError(Result.InvalidArgument, "one input, one output and one window per rank")
+    rc = lib().nexrSymLLAllGather(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
+                                  *_sym_ll_tail(windows, window_bytes, n_blocks, status, timeout_us, stream))
+    _check(rc, "nexrSymLLAllGather")
 
 
 def ll_clean_slot(send_lines: Sequence[int], send_flags: Sequence[int], first_line: int, slot_lines: int,

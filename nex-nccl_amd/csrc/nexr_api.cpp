@@ -2275,6 +2275,118 @@ NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, vo
   return nexrSuccess;
 }
 
+// ---- nexrSymLLAllReduce, nexrSymLLReduceScatter, nexrSymLLAllGather -----------------------------------------
+// Two things make a launch finish: its grid of nRanks * nBlocks teams is resident as a whole (the occupancy
+// check below), and every poll of its kernel is bounded (nexr_sym.hip). There is no dry run: a round needs
+// nothing from a later launch.
+NEXR_API nexrResult_t nexrSymLLWindowBytes(int nRanks, int maxBlocks, size_t* bytes) {
+  if (!bytes || nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS || maxBlocks < 1 || maxBlocks > NEXR_SYM_LL_MAX_BLOCKS)
+    return nexrInvalidArgument;
+  *bytes = (size_t)NEXR_SYM_LL_HEADER_BYTES + (size_t)maxBlocks * 2u * (size_t)nRanks * NEXR_SYM_LL_ROUND_PACKS * 16u;
+  return nexrSuccess;
+}
+
+namespace {
+// Workgroups of a symmetric LL kernel the current device keeps resident, as simpleGroupResident: the
+// occupancy query's answer, capped at 4 per CU, less one (the query over-reports by one for 256-thread
+// workgroups of kernels with many scalar registers; a surplus team would queue behind teams that poll it).
+// Test hook: NEXR_TEST_SYM_LL_RESIDENT=k makes the next calls take k as that number (read per call).
+nexrResult_t symLLResident(int coll, int dt, int64_t* resident) {
+  if (const char* e = getenv("NEXR_TEST_SYM_LL_RESIDENT"))
+    if (*e) {
+      *resident = strtoll(e, nullptr, 10);
+      return nexrSuccess;
+    }
+  constexpr int kDevs = 16;
+  static std::atomic<int64_t> cache[3][kDevs][nexrNumTypes];
+  int dev = 0;
+  NEXR_HIP(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < kDevs;
+  if (cached) {
+    const int64_t v = cache[coll][dev][dt].load(std::memory_order_relaxed);
+    if (v > 0) {
+      *resident = v;
+      return nexrSuccess;
+    }
+  }
+  int cus = 0, blocks = 0;
+  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  NEXR_HIP(sym_ll_blocks_per_cu(coll, dt, &blocks));
+  if (blocks > 4) blocks = 4;
+  if (blocks > 1) blocks--;
+  *resident = (int64_t)blocks * cus;
+  if (cached && *resident > 0) cache[coll][dev][dt].store(*resident, std::memory_order_relaxed);
+  return nexrSuccess;
+}
+
+// The host side of the three calls. coll: 0 all-reduce (count elements per buffer), 1 reduce-scatter (count
+// elements per chunk), 2 all-gather (count bytes, esz 1).
+nexrResult_t symLL(int coll, int nRanks, const void* const* inputs, void* const* outputs, size_t count, int datatype,
+                   void* const* windows, size_t windowBytes, int nBlocks, uint32_t* status, uint32_t timeoutUs,
+                   nexrStream_t stream) {
+  if (!inputs || !outputs || !windows) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS || nBlocks < 0 || nBlocks > NEXR_SYM_LL_MAX_BLOCKS)
+    return nexrInvalidArgument;
+  const int B = nBlocks ? nBlocks : 1;
+  const uint64_t esz = coll == 2 ? 1 : typeSize(datatype);
+  SymLLParams p;
+  memset(&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r] || !windows[r]) return nexrInvalidArgument;
+    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
+    if ((uintptr_t)windows[r] & 15) return nexrInvalidArgument;
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+    p.win[r] = (char*)windows[r];
+  }
+  size_t need = 0;
+  if (nexrSymLLWindowBytes(nRanks, B, &need) != nexrSuccess || windowBytes < need) return nexrInvalidArgument;
+  // the reference's int nElts: a buffer (for the reduce-scatter the whole input) stays below 2^31 bytes
+  const uint64_t limit = (1ull << 31) / esz / (coll == 1 ? (uint64_t)nRanks : 1u);
+  if ((uint64_t)count >= limit) return nexrInvalidArgument;
+  if (count == 0) return nexrSuccess;
+  int64_t resident = 0;
+  const nexrResult_t rr = symLLResident(coll, coll == 2 ? nexrFloat32 : datatype, &resident);
+  if (rr != nexrSuccess) return rr;
+  if ((int64_t)nRanks * B > resident) return nexrInvalidUsage;
+  p.nBytes = (uint64_t)count * esz;
+  p.status = status;
+  p.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;  // s_memrealtime: 100 MHz
+  p.nRanks = nRanks;
+  p.nBlocks = B;
+  p.firstWins = semantics() == nexrSemanticsShipped;  // SKIP_COMP: every add returns its first operand
+  NEXR_HIP(launch_sym_ll(coll, datatype, p, (hipStream_t)stream));
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrSymLLAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                         int datatype, int devRedOp, uint64_t redOpArg, void* const* windows,
+                                         size_t windowBytes, int nBlocks, uint32_t* status, uint32_t timeoutUs,
+                                         nexrStream_t stream) {
+  (void)redOpArg;
+  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
+  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
+  return symLL(0, nRanks, inputs, outputs, nElts, datatype, windows, windowBytes, nBlocks, status, timeoutUs, stream);
+}
+
+NEXR_API nexrResult_t nexrSymLLReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                             size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                             void* const* windows, size_t windowBytes, int nBlocks,
+                                             uint32_t* status, uint32_t timeoutUs, nexrStream_t stream) {
+  (void)redOpArg;
+  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
+  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
+  return symLL(1, nRanks, inputs, outputs, nElts, datatype, windows, windowBytes, nBlocks, status, timeoutUs, stream);
+}
+
+NEXR_API nexrResult_t nexrSymLLAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
+                                         void* const* windows, size_t windowBytes, int nBlocks, uint32_t* status,
+                                         uint32_t timeoutUs, nexrStream_t stream) {
+  return symLL(2, nRanks, inputs, outputs, nBytes, nexrFloat32, windows, windowBytes, nBlocks, status, timeoutUs,
+               stream);
+}
+
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,
                                       size_t slotLines, nexrStream_t stream) {
   if (nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;

@@ -208,6 +208,12 @@ struct nexrRingComm {
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;
+  // The symmetric LL entries (nexrRing*SymmetricLL): one window per rank on the ranks' GPU, made and zeroed by
+  // the first such call, sized for kSymLLRingBlocks blocks; symLLDirty: a call reported a timeout, so the
+  // windows are zeroed again before the next one.
+  std::vector<void*> symLLWin;
+  size_t symLLWinBytes = 0;
+  bool symLLDirty = false;
   bool ownQueues = true;  // every rank stream has a hardware queue of its own (createRankStream)
   // LL flag rule of this channel (nexrRingCommSetLLFlagRule, only before the first collective: the flags
   // of steps in flight must not change under them) and the cleaning send steps it has run, over all of

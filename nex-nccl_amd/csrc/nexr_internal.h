@@ -227,6 +227,24 @@ static_assert(sizeof(SymRsParams) <= 4096 && sizeof(SymAgParams) <= 4096, "kerne
 hipError_t launch_sym_reduce_scatter(int dt, const SymRsParams& p, unsigned grid, hipStream_t s);
 hipError_t launch_sym_all_gather(const SymAgParams& p, unsigned grid, hipStream_t s);
 
+// The symmetric LL collectives in one launch (nexrSymLLAllReduce, nexrSymLLReduceScatter, nexrSymLLAllGather;
+// nexr_sym.hip): a grid of nRanks * nBlocks teams, rank fastest. coll: 0 all-reduce, 1 reduce-scatter, 2
+// all-gather. nBytes is what a team splits into 8-byte packs: the all-reduce's buffer, the reduce-scatter's
+// chunk (= output), the all-gather's input; below 2^31.
+struct SymLLParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  char* win[NEXR_SYM_MAX_RANKS];  // the windows: header, then per block two buffers of nRanks * round lines
+  uint64_t nBytes;
+  uint32_t* status;
+  uint64_t timeoutTicks;
+  int nRanks, nBlocks;
+  int firstWins;  // nexrSemanticsShipped: every add returns its first operand
+};
+static_assert(sizeof(SymLLParams) <= 4096, "kernel argument block");
+hipError_t launch_sym_ll(int coll, int dt, const SymLLParams& p, hipStream_t s);
+hipError_t sym_ll_blocks_per_cu(int coll, int dt, int* blocks);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

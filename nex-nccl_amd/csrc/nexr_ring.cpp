@@ -1235,6 +1235,90 @@ nexrResult_t symAllGather(nexrRingComm* c, const void* const* sendbuffs, void* c
   });
 }
 
+// The symmetric LL entries (nexrRingAllReduceSymmetricLL, nexrRingReduceScatterSymmetricLL,
+// nexrRingAllGatherSymmetricLL): symCollective with the communicator's own windows and the status word of its
+// LL paths. `call` is one nexrSymLL* call given the windows, their size, the status word and the timeout.
+constexpr int kSymLLRingBlocks = 16;
+
+template <typename Call>
+nexrResult_t symLLCollective(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                             int datatype, Call call) {
+  bool launched = false;
+  nexrResult_t r = symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int n, nexrStream_t stream) {
+    if (c->status.empty()) return nexrInvalidUsage;
+    if (!c->status[0]) {
+      const nexrResult_t res = allocStatus(c, &c->status[0]);
+      if (res != nexrSuccess) return res;
+    }
+    if (c->symLLWin.empty()) {  // first use: n windows, zeroed
+      size_t bytes = 0;
+      const nexrResult_t res = nexrSymLLWindowBytes(n, kSymLLRingBlocks, &bytes);
+      if (res != nexrSuccess) return res;
+      std::vector<void*> win(n, nullptr);
+      bool ok = true;
+      for (int i = 0; i < n && ok; i++) ok = hipMalloc(&win[i], bytes) == hipSuccess;
+      if (!ok) {
+        for (void* p : win)
+          if (p) (void)hipFree(p);
+        return nexrUnhandledCudaError;
+      }
+      c->symLLWin = win;
+      c->symLLWinBytes = bytes;
+      c->symLLDirty = true;
+    }
+    if (c->symLLDirty) {
+      for (void* p : c->symLLWin)
+        if (hipMemsetAsync(p, 0, c->symLLWinBytes, (hipStream_t)stream) != hipSuccess) return nexrUnhandledCudaError;
+      c->symLLDirty = false;
+    }
+    __atomic_store_n(c->status[0], 0u, __ATOMIC_RELEASE);
+    const int timeoutMs = c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000;
+    launched = true;
+    return call(n, c->symLLWin.data(), c->symLLWinBytes, c->status[0], (uint32_t)timeoutMs * 1000u, stream);
+  });
+  if (launched && (r != nexrSuccess || __atomic_load_n(c->status[0], __ATOMIC_ACQUIRE) != 0)) {
+    c->symLLDirty = true;  // a poll gave up (or the call failed half-way): the windows are undefined
+    if (r == nexrSuccess) r = nexrInternalError;
+  }
+  return r;
+}
+
+nexrResult_t symLLAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                            int datatype, int op, int nBlocks) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (!symDatatype(datatype) || op != nexrSum || nBlocks < 0 || nBlocks > kSymLLRingBlocks) return nexrInvalidArgument;
+  return symLLCollective(c, sendbuffs, recvbuffs, count, datatype,
+                         [&](int n, void* const* win, size_t winBytes, uint32_t* status, uint32_t us, nexrStream_t s) {
+                           return nexrSymLLAllReduce(n, sendbuffs, recvbuffs, count, datatype, nexrDevSum, 0, win,
+                                                     winBytes, nBlocks, status, us, s);
+                         });
+}
+
+nexrResult_t symLLReduceScatter(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs,
+                                size_t recvcount, int datatype, int op, int nBlocks) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (!symDatatype(datatype) || op != nexrSum || nBlocks < 0 || nBlocks > kSymLLRingBlocks) return nexrInvalidArgument;
+  return symLLCollective(c, sendbuffs, recvbuffs, recvcount, datatype,
+                         [&](int n, void* const* win, size_t winBytes, uint32_t* status, uint32_t us, nexrStream_t s) {
+                           return nexrSymLLReduceScatter(n, sendbuffs, recvbuffs, recvcount, datatype, nexrDevSum, 0,
+                                                         win, winBytes, nBlocks, status, us, s);
+                         });
+}
+
+// A bit copy: every datatype the ring's all-gather takes, sendcount * esz bytes per rank.
+nexrResult_t symLLAllGather(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t sendcount,
+                            int datatype, int nBlocks) {
+  if (!c || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  const size_t esz = nexrTypeSize(datatype);
+  if (esz == 0 || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
+  if (sendcount > (size_t)-1 / esz || nBlocks < 0 || nBlocks > kSymLLRingBlocks) return nexrInvalidArgument;
+  return symLLCollective(c, sendbuffs, recvbuffs, sendcount, datatype,
+                         [&](int n, void* const* win, size_t winBytes, uint32_t* status, uint32_t us, nexrStream_t s) {
+                           return nexrSymLLAllGather(n, sendbuffs, recvbuffs, sendcount * esz, win, winBytes, nBlocks,
+                                                     status, us, s);
+                         });
+}
+
 // A communicator touches HIP when its FIFOs live in device memory or when any of its steps runs the
 // built-in (HIP) reduce-copy; one whose steps are all caller-supplied (a CPU checker) never does.
 bool needsHip(const nexrRingConfig& cfg) {
@@ -1402,6 +1486,27 @@ NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t c, const void* c
   return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
 }
 
+NEXR_API nexrResult_t nexrRingAllReduceSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,
+                                                   void* const* recvbuffs, size_t count, int datatype, int op,
+                                                   int nBlocks) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symLLAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+}
+
+NEXR_API nexrResult_t nexrRingReduceScatterSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,
+                                                       void* const* recvbuffs, size_t recvcount, int datatype,
+                                                       int op, int nBlocks) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symLLReduceScatter(c, sendbuffs, recvbuffs, recvcount, datatype, op, nBlocks);
+}
+
+NEXR_API nexrResult_t nexrRingAllGatherSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,
+                                                   void* const* recvbuffs, size_t sendcount, int datatype,
+                                                   int nBlocks) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symLLAllGather(c, sendbuffs, recvbuffs, sendcount, datatype, nBlocks);
+}
+
 NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t c, int* word) {
   if (!c || !word) return nexrInvalidArgument;
   *word = c->stepWaitWord ? 1 : 0;
@@ -1536,6 +1641,10 @@ NEXR_API nexrResult_t nexrRingCommDestroy(nexrRingComm_t c) {
   if (c->groupWs) {
     (void)hipSetDevice(c->groupWsDevice);
     (void)hipFree(c->groupWs);
+  }
+  if (!c->symLLWin.empty()) {
+    (void)hipSetDevice(c->devices[0]);
+    for (void* p : c->symLLWin) (void)hipFree(p);
   }
   for (Conn* k : c->conns) freeConn(c, k);
   for (Conn* k : c->treeUp) freeConn(c, k);

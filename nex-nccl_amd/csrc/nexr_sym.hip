@@ -1,6 +1,7 @@
 // nexr_sym.hip — the symmetric all-reduce RSxLD_AGxST as ONE launch (nexrSymAllReduce), for gfx950, and behind
 // it its siblings ReduceScatter_LD and AllGather_ST (nexrSymReduceScatter, nexrSymAllGather; their own comment
-// below). Included at the end of nexr_ll.hip behind nexr_simple.hip: the LL / LL128 object stays the one code
+// below) and the family's LL members AllReduce_AGxLL_R, ReduceScatter_LL and AllGather_LL (nexrSymLL*; at the end
+// of the file). Included at the end of nexr_ll.hip behind nexr_simple.hip: the LL / LL128 object stays the one code
 // object beside the per-datatype ones.
 //
 // What it computes is ncclSymRun_AllReduce_RSxLD_AGxST (reference src/device/symmetric/all_reduce.hh:6-276)
@@ -407,6 +408,167 @@ __global__ __launch_bounds__(kBlock) void sym_all_gather_kernel(SymAgParams P) {
       }
     }
   }
+}
+
+// ---- the LL members: AllReduce_AGxLL_R, ReduceScatter_LL, AllGather_LL (nexrSymLL*) -------------------------
+// ncclSymRun_AllReduce_AGxLL_R (reference src/device/symmetric/all_reduce.hh:356-428), ncclSymRun_ReduceScatter_LL
+// (reduce_scatter.hh:320-388) and ncclSymRun_AllGather_LL (all_gather.hh:256-363) over sendLL / bcastLL /
+// recvLL / recvReduceLL / endLL (symmetric/primitives.hh:212-377), for ranks on this GPU. The rules and the
+// window layout are in include/nexr.h; what is kept of the protocol is the per-block epoch word that outlives
+// the call, the two line buffers chosen by the flag's parity, the broadcast of a rank's packs into every
+// window, the rank-0-first fp32 fold and the cleanup at the wrap. Inside the line area the layout is free.
+//
+// A team is one workgroup, (rank w mod n, block w / n) of a grid of n * B. It takes its share of the 8-byte
+// packs (the reference's split: P / B, one more for b < P mod B) in rounds of kSymLLRound = kBlock packs,
+// ONE pack per lane and round: the lane loads its pack with a plain load, stores it as the line
+// {lo, f, hi, f} into slot rank * kSymLLRound + lane of the parity-f buffer of block b in every window (the
+// reduce-scatter: pack p of chunk s into window s), then polls slots j * kSymLLRound + lane, j = 0..n-1, of
+// its OWN window, kSymPeers lines in flight, folds them in rank order and stores the result with a plain
+// store. A line is one 16-byte sc0 sc1 buffer store and one such load per try (wire_st / wire_ld). The round
+// ends with a workgroup barrier: no lane of a rank sends round k + 1 before all of that rank's team have read
+// round k, and a peer's round k + 2 lines (the same buffer) follow its receipt of this team's round k + 1
+// lines. A poll is bounded as wait_head is; a lane whose poll gave up marks the team dead in LDS, and from
+// the next barrier on the team skips its polls and stores but still sends and still reaches every barrier.
+constexpr int kSymLLRound = NEXR_SYM_LL_ROUND_PACKS;
+static_assert(kSymLLRound == kBlock, "one pack per lane and round");
+enum { kSymLLAllReduce = 0, kSymLLReduceScatter = 1, kSymLLAllGather = 2 };
+
+__device__ __forceinline__ bool sym_ll_match(u32x4 x, uint32_t f) { return x.y == f && x.w == f; }
+
+// recvLL's loop (primitives.hh:302-335) for one line that was not there at the first try
+__device__ __forceinline__ bool sym_ll_poll(__amdgpu_buffer_rsrc_t r, uint32_t off, uint32_t f, u32x4& x,
+                                            uint64_t timeoutTicks, uint32_t* status) {
+  uint64_t t0 = 0;
+  for (uint32_t tries = 1;; tries++) {
+    __builtin_amdgcn_s_sleep(1);
+    x = wire_ld(r, off);
+    if (sym_ll_match(x, f)) return true;
+    if (tries % kLLAbortEvery == 0 && ll_aborted(status)) return false;
+    if (tries % kLLClockEvery) continue;
+    const uint64_t now = __builtin_amdgcn_s_memrealtime();
+    if (!t0) t0 = now;
+    else if (now - t0 > timeoutTicks) {
+      if (status) __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      return false;
+    }
+  }
+}
+
+template <int K, int D>
+__device__ __forceinline__ void sym_ll_team(const SymLLParams& P) {
+  using S = Sym<D>;
+  using A4 = typename S::A4;
+  __shared__ uint32_t teamDead;
+  const uint32_t n = (uint32_t)P.nRanks, B = (uint32_t)P.nBlocks;
+  const uint32_t rank = blockIdx.x % n, blk = blockIdx.x / n;  // rank fastest
+  const uint32_t t = threadIdx.x;
+  const uint64_t nBytes = P.nBytes;
+  const uint32_t packs = (uint32_t)((nBytes + 7) / 8);  // the host keeps nBytes below 2^31
+  const uint32_t share = packs / B + (blk < packs % B ? 1u : 0u);
+  const uint32_t first = blk * (packs / B) + (blk < packs % B ? blk : packs % B);
+  if (share == 0) return;  // the whole team: no round, the epoch word stays
+  if (t == 0) teamDead = 0;
+  char* mine = P.win[rank];
+  g_u32* word = (g_u32*)mine + blk;
+  uint32_t f = __builtin_amdgcn_readfirstlane(*word) + 2u;
+  const uint32_t bufBytes = n * kSymLLRound * 16u;
+  bool dead = false, bad = false;
+  __syncthreads();
+  for (uint32_t done = 0; done < share; done += kSymLLRound) {
+    const bool have = t < share - done;
+    const uint32_t p = first + done + t;
+    const uint64_t lines = NEXR_SYM_LL_HEADER_BYTES + (uint64_t)(blk * 2u + (f & 1u)) * bufBytes;
+    // bcastLL / sendLL: own window first, then rank + 1, ...
+    if (have) {
+      uint64_t d = 0;
+      if (K != kSymLLReduceScatter) d = ld_line(P.in[rank], p, nBytes);
+      uint32_t s = rank;
+      for (uint32_t k = 0; k < n; k++) {
+        if (K == kSymLLReduceScatter) d = ld_line(P.in[rank] + (uint64_t)s * nBytes, p, nBytes);
+        wire_st(wire_rsrc(P.win[s] + lines, bufBytes), (rank * kSymLLRound + t) * 16u,
+                (u32x4){(uint32_t)d, f, (uint32_t)(d >> 32), f});
+        s = s + 1 == n ? 0 : s + 1;
+      }
+    }
+    const auto own = wire_rsrc(mine + lines, bufBytes);
+    if (have && !dead) {
+      A4 lo, hi;
+      for (uint32_t base = 0; base < n; base += kSymPeers) {  // team-uniform
+        u32x4 v[kSymPeers];
+#pragma unroll
+        for (int j = 0; j < kSymPeers; j++)  // all in flight, no branch between them; past rank n - 1 the
+          v[j] = wire_ld(own, ((base + j) * kSymLLRound + t) * 16u);  // descriptor clips: zeros, no access
+#pragma unroll
+        for (int j = 0; j < kSymPeers; j++) {
+          if (base + j < n && !bad) {
+            if (!sym_ll_match(v[j], f))
+              bad = !sym_ll_poll(own, ((base + j) * kSymLLRound + t) * 16u, f, v[j], P.timeoutTicks, P.status);
+            if (bad) continue;
+            if (K == kSymLLAllGather) {
+              st_line(P.out[rank] + (uint64_t)(base + j) * nBytes, p, nBytes, (uint64_t)v[j].z << 32 | v[j].x);
+            } else {  // recvReduceLL: rank 0 first, the accumulator first
+              const A4 a = S::widen4(v[j].x), b = S::widen4(v[j].z);
+              if (j == 0 && base == 0) lo = a, hi = b;
+              else if (!P.firstWins) lo = lo + a, hi = hi + b;
+            }
+          }
+        }
+      }
+      if (K != kSymLLAllGather && !bad)
+        st_line(P.out[rank], p, nBytes, (uint64_t)S::narrow4(hi) << 32 | S::narrow4(lo));
+    }
+    if (bad) teamDead = 1;
+    // endLL: at the wrap this parity's buffer is zeroed, after everybody's reads and drained before the barrier
+    if (f >= 0xfffffffeu) {
+      __syncthreads();
+      for (uint32_t i = t; i < n * kSymLLRound; i += kBlock) wire_st(own, i * 16u, (u32x4){0u, 0u, 0u, 0u});
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    dead = teamDead != 0;
+    f = f == 0xffffffffu ? 2u : f + 1u;
+  }
+  if (t == 0) *word = f - 2u;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void sym_ll_all_reduce_kernel(SymLLParams P) {
+  sym_ll_team<kSymLLAllReduce, D>(P);
+}
+template <int D>
+__global__ __launch_bounds__(kBlock) void sym_ll_reduce_scatter_kernel(SymLLParams P) {
+  sym_ll_team<kSymLLReduceScatter, D>(P);
+}
+__global__ __launch_bounds__(kBlock) void sym_ll_all_gather_kernel(SymLLParams P) {
+  sym_ll_team<kSymLLAllGather, nexrFloat32>(P);  // a bit copy: the datatype is not used
+}
+
+static const void* sym_ll_fn(int coll, int dt) {
+  if (coll == kSymLLAllGather) return (const void*)&sym_ll_all_gather_kernel;
+  if (coll == kSymLLAllReduce)
+    return dt == nexrFloat32    ? (const void*)&sym_ll_all_reduce_kernel<nexrFloat32>
+           : dt == nexrFloat16  ? (const void*)&sym_ll_all_reduce_kernel<nexrFloat16>
+           : dt == nexrBfloat16 ? (const void*)&sym_ll_all_reduce_kernel<nexrBfloat16>
+                                : nullptr;
+  if (coll == kSymLLReduceScatter)
+    return dt == nexrFloat32    ? (const void*)&sym_ll_reduce_scatter_kernel<nexrFloat32>
+           : dt == nexrFloat16  ? (const void*)&sym_ll_reduce_scatter_kernel<nexrFloat16>
+           : dt == nexrBfloat16 ? (const void*)&sym_ll_reduce_scatter_kernel<nexrBfloat16>
+                                : nullptr;
+  return nullptr;
+}
+
+hipError_t launch_sym_ll(int coll, int dt, const SymLLParams& p, hipStream_t s) {
+  const void* fn = sym_ll_fn(coll, dt);
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {const_cast<SymLLParams*>(&p)};
+  return hipLaunchKernel(fn, dim3((unsigned)(p.nRanks * p.nBlocks)), dim3(kBlock), args, 0, s);
+}
+
+hipError_t sym_ll_blocks_per_cu(int coll, int dt, int* blocks) {
+  const void* fn = sym_ll_fn(coll, dt);
+  if (!fn) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, fn, kBlock, 0);
 }
 
 hipError_t launch_sym_reduce_scatter(int dt, const SymRsParams& p, unsigned grid, hipStream_t s) {

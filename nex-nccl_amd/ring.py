@@ -21,6 +21,8 @@ EXTRAS_LIB_PATH = os.path.join(_HERE, "libnexr_extras.so")
 RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceScatter", "nexrRingAllGather",
                     "nexrRingReduce", "nexrRingBroadcast", "nexrTreeAllReduce", "nexrRingAllReduceSymmetric",
                     "nexrRingReduceScatterSymmetric", "nexrRingAllGatherSymmetric",
+                    "nexrRingAllReduceSymmetricLL", "nexrRingReduceScatterSymmetricLL",
+                    "nexrRingAllGatherSymmetricLL",
                     "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
@@ -74,6 +76,9 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingAllReduceSymmetric.argtypes = [vp, arr, arr, sz, i32, i32, i32]
     L.nexrRingReduceScatterSymmetric.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingAllGatherSymmetric.argtypes = [vp, arr, arr, sz, i32]
+    L.nexrRingAllReduceSymmetricLL.argtypes = [vp, arr, arr, sz, i32, i32, i32]
+    L.nexrRingReduceScatterSymmetricLL.argtypes = [vp, arr, arr, sz, i32, i32, i32]
+    L.nexrRingAllGatherSymmetricLL.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
@@ -249,6 +254,35 @@ class RingComm:
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrRingAllGatherSymmetric(self._h, s, r, int(sendcount), int(datatype)),
                "nexrRingAllGatherSymmetric")
+
+    def all_reduce_symmetric_ll(self, sendbuffs, recvbuffs, count: int, datatype: int, op: int,
+                                n_blocks: int = 0) -> None:
+        """ncclAllReduce as the reference's symmetric LL kernel AllReduce_AGxLL_R in ONE launch
+        (nexrRingAllReduceSymmetricLL): every element is rank 0's input plus rank 1's, ... in rank order, in
+        fp32 with one rounding, on every rank. The communicator owns the windows (made on first use, sized for
+        16 blocks: n_blocks is 0..16). Usage and argument rules as all_reduce_symmetric; a message of 2 GiB or
+        more is InvalidArgument; queued() stays as it was."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllReduceSymmetricLL(self._h, s, r, int(count), int(datatype), int(op), int(n_blocks)),
+               "nexrRingAllReduceSymmetricLL")
+
+    def reduce_scatter_symmetric_ll(self, sendbuffs, recvbuffs, recvcount: int, datatype: int, op: int,
+                                    n_blocks: int = 0) -> None:
+        """ncclReduceScatter as the reference's symmetric LL kernel ReduceScatter_LL in ONE launch
+        (nexrRingReduceScatterSymmetricLL): recvbuffs[r] receives chunk r folded from rank 0's input on (not
+        from rank r's, as reduce_scatter_symmetric), in fp32 with one rounding. Rules as
+        all_reduce_symmetric_ll."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingReduceScatterSymmetricLL(self._h, s, r, int(recvcount), int(datatype), int(op),
+                                                        int(n_blocks)), "nexrRingReduceScatterSymmetricLL")
+
+    def all_gather_symmetric_ll(self, sendbuffs, recvbuffs, sendcount: int, datatype: int, n_blocks: int = 0) -> None:
+        """ncclAllGather as the reference's symmetric LL kernel AllGather_LL in ONE launch
+        (nexrRingAllGatherSymmetricLL): a bit copy through the communicator's windows; the bytes are the ring's
+        all-gather's. Rules as all_reduce_symmetric_ll, every datatype the ring's all-gather takes."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllGatherSymmetricLL(self._h, s, r, int(sendcount), int(datatype), int(n_blocks)),
+               "nexrRingAllGatherSymmetricLL")
 
     def send_recv(self, sendbuffs, send_peers, recvbuffs, recv_peers, nbytes: int) -> None:
         """ncclSend/ncclRecv of every rank in one group: rank r sends nbytes of sendbuffs[r] to
