@@ -838,6 +838,78 @@ NEXR_API nexrResult_t nexrSymLLAllGather(int nRanks, const void* const* inputs, 
                                          uint32_t timeoutUs, nexrStream_t stream);
 
 /*
+ * nexrFlatAllReduce, nexrFlatReduceScatter, nexrFlatReduce — the RING all-reduce, reduce-scatter and reduce
+ * (runRing, reference src/device/all_reduce.h:12-84, reduce_scatter.h:12-52, reduce.h:12-50) of nRanks ranks
+ * that live on ONE GPU, each as one launch that writes exactly the bytes the ring's chain of reduce-copy steps
+ * writes: for all ten datatypes (not fp8), all five device ops and both operand orders. Where the nexrSym*
+ * calls fold owner first in fp32 with one rounding, these run the ring's own chain, one step and one rounding
+ * per rank, in registers: peer loads and stores only, no FIFO, no credit, no poll between workgroups, so a
+ * launch cannot stall on residency. Additions only: the ABI stays 0.3. n = nRanks (2..NEXR_SYM_MAX_RANKS),
+ * esz = the datatype's size.
+ *
+ * Rule for one element. The element has a start rank s (per collective, below).
+ *   v = in[s]. Under nexrDevPreMulSum it passes through the pre-op (times the scalar redOpArg encodes) and
+ *     then through the canonicalisation that a K = 1 reduce-copy with a pre-op applies (fp16 / bf16: every NaN
+ *     to 0x7fff). Without a pre-op it is a bit copy: NaN payloads survive (directSend / sendInput).
+ *   For j = 1..n-1, r = (s + j) mod n: v = one reduce-copy step of {in[r] through the pre-op, v}.
+ *     userFirst != 0 (SIMPLE): in[r] is the first operand (srcs[0] is the user input, prims_simple.h:238-242;
+ *     nexrReduceCopy's order). userFirst == 0 (LL, LL128): v is the first operand (prims_ll.h:251-258,
+ *     prims_ll128.h:214-219). The step's own fp16 / bf16 rounding and NaN canonicalisation follow EVERY step,
+ *     not the chain as a whole; nothing is contracted.
+ *   The nexrDevSumPostDiv post-op runs on the last step only (postOp of the chain's last rank).
+ *
+ * AllReduce. inputs[r] / outputs[r] hold nElts elements. parts[k] = {offset, count, chunkCount} in elements
+ * are the channels' views of the buffer (ncclCollCbdPart, src/include/device.h:946-970, with the channel's
+ * chunkCount of calcCollChunking, src/enqueue.cc:1993-2062); they tile [0, nElts) in ascending order. For
+ * element i of a part (runRingAllReduce, all_reduce.h:12-84):
+ *   j = i - offset, loop = n * chunkCount, L = floor(j / loop), rem = count - L * loop,
+ *   cc = rem < loop ? alignUp(divUp(rem, n), 16 / esz) : chunkCount, c = floor((j - L * loop) / cc),
+ *   s = (c + 1) mod n.
+ * The result goes to all n outputs. Every offset and chunkCount is a multiple of 16 / esz, so every chunk
+ * boundary lies a multiple of 16 bytes from element 0.
+ *
+ * ReduceScatter. inputs[r] holds n * nElts elements, outputs[r] holds nElts. Element e of chunk d reads
+ * inputs[*][d * nElts + e] with s = (d + 1) mod n (reduce_scatter.h:12-52: the chain ends at rank d); the
+ * result goes to outputs[d][e] only.
+ *
+ * Reduce. inputs[r] and output hold nElts elements. s = (root + 1) mod n (reduce.h:12-50); the result goes
+ * to output, the root's, only: nothing else is written.
+ *
+ * Semantics. nexrSemanticsFork runs signed Min / Max on the unsigned type, as every other call. Under
+ * nexrSemanticsShipped every reduce returns its first operand without pre-op or post-op, as in the SIMPLE
+ * group kernel: the result is a bit copy of in[(s + n - 1) mod n] with userFirst and of in[s] without.
+ *
+ * Aliasing. Any output may equal any input whole (the one lane that writes an element has read it from every
+ * input first); the reduce-scatter's outputs[r] may be chunk r of any input (inputs[t] + r * nElts * esz).
+ * Any other overlap is undefined. Pointers need element alignment only.
+ *
+ * Stream-ordered and one launch each; nothing of the caller's arrays is read after the call returns. Only an
+ * all-reduce with more than NEXR_FLAT_INLINE_PARTS parts takes a workspace: stream-ordered memory of the
+ * current device that short launches ahead of the one fill with the parts and that is freed behind it.
+ * nElts == 0 succeeds without a launch. nexrInvalidArgument, before any device call: null arrays or entries;
+ * nRanks outside 2..NEXR_SYM_MAX_RANKS; an fp8 or unknown datatype; an op that the datatype does not have
+ * (nexrDevSumPostDiv on a float; a signed one-byte divide by a divisor that truncates to 0); root outside
+ * 0..n-1; a pointer not aligned to esz; parts that do not tile [0, nElts) in ascending order or hold an empty
+ * part; a part offset or chunkCount that is zero (chunkCount) or not a multiple of 16 / esz; an overflowing
+ * product (nElts * esz, n * nElts * esz, n * chunkCount).
+ */
+typedef struct {
+  uint64_t offset;      /* first element of the channel's part */
+  uint64_t count;       /* its elements */
+  uint64_t chunkCount;  /* the channel's chunk in elements */
+} nexrFlatPart;
+#define NEXR_FLAT_INLINE_PARTS 120
+NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                        int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                        const nexrFlatPart* parts, int nParts, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
+                                     int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                     nexrStream_t stream);
+
+/*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
  * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.

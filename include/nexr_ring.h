@@ -195,6 +195,38 @@ NEXR_API nexrResult_t nexrRingAllGatherSymmetricLL(nexrRingComm_t comm, const vo
                                                    void* const* recvbuffs, size_t sendcount, int datatype,
                                                    int nBlocks);
 
+/* ncclAllReduce, ncclReduceScatter and ncclReduce of the RING, each as ONE launch with the ring's own bytes:
+ * nexrFlatAllReduce / nexrFlatReduceScatter / nexrFlatReduce (include/nexr.h: the chain of one reduce-copy step
+ * per rank, run in registers) over every rank's buffers. The argument lists are the plain calls' and so are
+ * the results, byte for byte, for every datatype and op the plain calls take: the op is encoded as theirs
+ * (Avg becomes PreMulSum or SumPostDiv), the all-reduce's chunks are this communicator's own (its channels'
+ * parts and chunk counts for its protocol and FIFO size), and a SIMPLE communicator folds the user input
+ * first where LL and LL128 fold the received partial first. Through the helper of the symmetric entries: the
+ * communicator's first stream and its wait, thread ranks on one GPU with device memory or nexrInvalidUsage,
+ * at most NEXR_SYM_MAX_RANKS ranks, one rank takes the one-rank path, a count of 0 succeeds; a reduce needs
+ * recvbuffs[root] only and writes nothing else. No connection and no step counter is touched and
+ * nexrRingCommGetQueued stays as it was, so flat and FIFO calls may alternate freely. In place as the plain
+ * calls define it. Chosen for the plain calls only under nexrRingCommSetFlat. Measured numbers: DESIGN §8.7
+ * (tools/flat_probe.py). */
+NEXR_API nexrResult_t nexrRingAllReduceFlat(nexrRingComm_t comm, const void* const* sendbuffs,
+                                            void* const* recvbuffs, size_t count, int datatype, int op);
+NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t comm, const void* const* sendbuffs,
+                                                void* const* recvbuffs, size_t recvcount, int datatype, int op);
+NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                         size_t count, int datatype, int op, int root);
+
+/* Opt-in, off by default: with on != 0, nexrRingAllReduce, nexrRingReduceScatter and nexrRingReduce on an
+ * eligible communicator run as the flat entries above, and nexrRingCommGetQueued reports 4 after such a call.
+ * Eligible: thread ranks, device memory, every rank on one GPU, at most NEXR_SYM_MAX_RANKS ranks and the
+ * library's own fn (SIMPLE), llFn (LL) or ll128Fn (LL128): a caller's function may compute anything. On any
+ * other communicator, and for the all-gather, the broadcast and nexrTreeAllReduce, the calls run exactly as
+ * without the option. The results are the same bytes either way, and the option may be toggled between
+ * collectives and combined with the group options (a routed call ignores them). With the option off nothing
+ * changes.
+ *
+ * nexrInvalidUsage for process-rank or host-memory communicators. */
+NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t comm, int on);
+
 /* The tree links of `rank` in this communicator's topology: *up (-1 at the root) and down[0..2]
  * (-1 when absent, children packed first as setTreeDown does). */
 NEXR_API nexrResult_t nexrTreeTopology(nexrRingComm_t comm, int rank, int* up, int* down);
@@ -218,7 +250,7 @@ NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t comm, int* word);
  * default 4). 0: host-sequenced (SIMPLE and LL128 without their group options, ranks on several GPUs, host
  * memory, NEXR_LL_ASYNC=0, or more rank streams on a GPU than it has hardware queues beside the default
  * stream's). 3: group launches on one stream (nexrRingCommSetLLGroup, below; LL and LL128;
- * nexrRingCommSetSimpleGroup for SIMPLE). */
+ * nexrRingCommSetSimpleGroup for SIMPLE). 4: one flat launch (nexrRingCommSetFlat, above). */
 NEXR_API nexrResult_t nexrRingCommGetQueued(nexrRingComm_t comm, int* queued);
 
 /* Opt-in: run the LL steps of every rank (and channel) of a ring collective in group launches on ONE

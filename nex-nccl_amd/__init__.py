@@ -91,6 +91,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrSimpleGroupDirectWorkspaceBytes", "nexrReduceCopySimpleStepsGroupDirect", "nexrSymAllReduce",
                "nexrSymReduceScatter", "nexrSymAllGather", "nexrSymLLWindowBytes", "nexrSymLLAllReduce",
                "nexrSymLLReduceScatter", "nexrSymLLAllGather",
+               "nexrFlatAllReduce", "nexrFlatReduceScatter", "nexrFlatReduce",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -104,6 +105,11 @@ class NexrError(RuntimeError):
         except ValueError:
             name = "Unknown"
         super().__init__(f"{what}: nexr result {self.code} ({name})" if what else f"nexr result {self.code} ({name})")
+
+
+class FlatPart(ctypes.Structure):
+    """nexrFlatPart: one channel's part of a flat all-reduce, in elements."""
+    _fields_ = [("offset", ctypes.c_uint64), ("count", ctypes.c_uint64), ("chunkCount", ctypes.c_uint64)]
 
 
 class DevRedOpFull(ctypes.Structure):
@@ -325,6 +331,12 @@ def lib() -> ctypes.CDLL:
     L.nexrSymReduceScatter.restype = i32
     L.nexrSymAllGather.argtypes = [i32, P(vp), P(vp), sz, vp]
     L.nexrSymAllGather.restype = i32
+    L.nexrFlatAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, i32, P(FlatPart), i32, vp]
+    L.nexrFlatAllReduce.restype = i32
+    L.nexrFlatReduceScatter.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, i32, vp]
+    L.nexrFlatReduceScatter.restype = i32
+    L.nexrFlatReduce.argtypes = [i32, P(vp), vp, i32, sz, i32, i32, u64, i32, vp]
+    L.nexrFlatReduce.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
     L.nexrSymLLWindowBytes.restype = i32
     L.nexrSymLLAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, P(vp), sz, i32, vp, ctypes.c_uint32, vp]
@@ -841,6 +853,49 @@ def sym_all_gather(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int, 
     rc = lib().nexrSymAllGather(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
                                 ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrSymAllGather")
+
+
+FLAT_INLINE_PARTS = 120  # NEXR_FLAT_INLINE_PARTS
+
+
+def flat_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int, dev_red_op: int,
+                    red_op_arg: int, user_first: bool, parts: Sequence[tuple], stream: int = 0) -> None:
+    """The ring all-reduce of len(inputs) ranks on one GPU in ONE launch with the ring's bytes
+    (``nexrFlatAllReduce``): every element runs the ring's chain, one reduce-copy step per rank from its start
+    rank on, in registers. ``parts`` are the channels' (offset, count, chunkCount) in elements, tiling
+    [0, n_elts) in ascending order; ``user_first`` is the SIMPLE operand order (the rank's input first), False
+    the LL / LL128 one. Every datatype but fp8 and every device op. In place allowed. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    arr = (FlatPart * max(1, len(parts)))(*[FlatPart(int(o), int(c), int(k)) for o, c, k in parts])
+    rc = lib().nexrFlatAllReduce(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                 int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0, arr,
+                                 len(parts), ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllReduce")
+
+
+def flat_reduce_scatter(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int, dev_red_op: int,
+                        red_op_arg: int, user_first: bool, stream: int = 0) -> None:
+    """The ring reduce-scatter in ONE launch with the ring's bytes (``nexrFlatReduceScatter``): inputs[r] holds
+    len(inputs) * ``n_elts`` elements, outputs[d] receives chunk d, whose chain starts at rank d + 1 and ends at
+    rank d. outputs[r] may be chunk r of any input. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatReduceScatter(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                     int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0,
+                                     ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatReduceScatter")
+
+
+def flat_reduce(inputs: Sequence[int], output: int, root: int, n_elts: int, datatype: int, dev_red_op: int,
+                red_op_arg: int, user_first: bool, stream: int = 0) -> None:
+    """The ring reduce in ONE launch with the ring's bytes (``nexrFlatReduce``): the chain starts at rank
+    ``root`` + 1 and ends at ``root``, whose ``output`` alone is written. Stream-ordered."""
+    rc = lib().nexrFlatReduce(len(inputs), _ptr_array(inputs), ctypes.c_void_p(int(output)) if output else None,
+                              int(root), int(n_elts), int(datatype), int(dev_red_op),
+                              int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0,
+                              ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatReduce")
 
 
 SYM_LL_HEADER_BYTES = 256  # NEXR_SYM_LL_HEADER_BYTES

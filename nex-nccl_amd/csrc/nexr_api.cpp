@@ -2275,6 +2275,147 @@ NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, vo
   return nexrSuccess;
 }
 
+// ---- nexrFlatAllReduce, nexrFlatReduceScatter, nexrFlatReduce -----------------------------------------------
+// The checks the three share, then what the semantics make of the call (as simpleStepsGroup hands them to
+// launch_simple_group: fork changes the dispatch type; shipped folds nothing, and what survives is the first
+// operand of the chain's last step).
+namespace {
+nexrResult_t flatPrepare(int nRanks, const void* const* inputs, int datatype, int devRedOp, uint64_t redOpArg,
+                         int userFirst, FlatParams* p, int* dt, int* op) {
+  if (!inputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
+    return nexrInvalidArgument;
+  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
+  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
+  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
+    uint32_t divisor = (uint32_t)(redOpArg >> 1);
+    if (divisor == 0) divisor = 1;
+    if ((int8_t)divisor == 0) return nexrInvalidArgument;
+  }
+  const uint64_t esz = typeSize(datatype);
+  memset((void*)p, 0, sizeof(*p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || ((uintptr_t)inputs[r] & (esz - 1))) return nexrInvalidArgument;
+    p->in[r] = (const char*)inputs[r];
+  }
+  int srcIsInput = 1, postOp = 1, firstWins = 0;
+  *dt = datatype;
+  *op = devRedOp;
+  llSemantics(dt, op, &srcIsInput, &postOp, &firstWins);
+  p->nRanks = nRanks;
+  p->redArg = redOpArg;
+  p->userFirst = userFirst ? 1 : 0;
+  p->nFold = firstWins ? 1 : nRanks;
+  p->shift = firstWins && userFirst ? nRanks - 1 : 0;
+  p->preOp = srcIsInput;
+  p->postOp = postOp;
+  return nexrSuccess;
+}
+
+// One-shot: a wave per 2048-byte piece of every region, four waves per workgroup; beyond the cap the kernel
+// strides.
+unsigned flatGrid(uint64_t regionBytes, int nRegions) {
+  const uint64_t items = (regionBytes + 2047) / 2048 * (uint64_t)nRegions;
+  return (unsigned)std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                        int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                        const nexrFlatPart* parts, int nParts, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  if (!outputs) return nexrInvalidArgument;
+  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess) return res;
+  const uint64_t esz = typeSize(datatype), epp = 16 / esz;
+  for (int r = 0; r < nRanks; r++) {
+    if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
+    p.out[r] = (char*)outputs[r];
+  }
+  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
+  if (nParts < 0 || (nParts > 0 && !parts)) return nexrInvalidArgument;
+  uint64_t at = 0;
+  for (int k = 0; k < nParts; k++) {  // ascending, gapless, from 0
+    const nexrFlatPart& q = parts[k];
+    if (q.offset != at || q.count == 0 || q.count > (uint64_t)nElts - at) return nexrInvalidArgument;
+    if (q.offset % epp || q.chunkCount == 0 || q.chunkCount % epp) return nexrInvalidArgument;
+    if (q.chunkCount > (uint64_t)-1 / (uint64_t)nRanks) return nexrInvalidArgument;
+    at += q.count;
+  }
+  if (at != (uint64_t)nElts) return nexrInvalidArgument;
+  if (nElts == 0) return nexrSuccess;
+  p.coll = kFlatAllReduce;
+  p.regionBytes = (uint64_t)nElts * esz;
+  p.nParts = nParts;
+  hipStream_t s = (hipStream_t)stream;
+  nexrFlatPart* ws = nullptr;
+  if (nParts <= kFlatInlineParts) {
+    memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatPart));
+  } else {  // the parts travel by value in short launches ahead of the one: nothing is read after return
+    NEXR_HIP(hipMallocAsync((void**)&ws, (size_t)nParts * sizeof(nexrFlatPart), s));
+    FlatPartsFill f;
+    for (int k = 0; k < nParts; k += kFlatInlineParts) {
+      f.dst = ws + k;
+      f.n = std::min(kFlatInlineParts, nParts - k);
+      f.pad = 0;
+      memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatPart));
+      const hipError_t e = launch_flat_parts(f, s);
+      if (e != hipSuccess) {
+        (void)hipFreeAsync(ws, s);
+        return hipFail(e);
+      }
+    }
+    p.ext = ws;
+  }
+  const hipError_t e = launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), s);
+  if (ws) (void)hipFreeAsync(ws, s);
+  NEXR_HIP(e);
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  if (!outputs) return nexrInvalidArgument;
+  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess) return res;
+  const uint64_t esz = typeSize(datatype);
+  for (int r = 0; r < nRanks; r++) {
+    if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
+    p.out[r] = (char*)outputs[r];
+  }
+  if (nElts > (size_t)-1 / esz / (size_t)nRanks) return nexrInvalidArgument;  // an input's nRanks * nElts * esz bytes
+  if (nElts == 0) return nexrSuccess;
+  p.coll = kFlatReduceScatter;
+  p.regionBytes = (uint64_t)nElts * esz;
+  NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
+                                     int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                     nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  if (!output) return nexrInvalidArgument;
+  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess) return res;
+  const uint64_t esz = typeSize(datatype);
+  if (root < 0 || root >= nRanks || ((uintptr_t)output & (esz - 1))) return nexrInvalidArgument;
+  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
+  if (nElts == 0) return nexrSuccess;
+  p.out[root] = (char*)output;
+  p.root = root;
+  p.coll = kFlatReduce;
+  p.regionBytes = (uint64_t)nElts * esz;
+  NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
 // ---- nexrSymLLAllReduce, nexrSymLLReduceScatter, nexrSymLLAllGather -----------------------------------------
 // Two things make a launch finish: its grid of nRanks * nBlocks teams is resident as a whole (the occupancy
 // check below), and every poll of its kernel is bounded (nexr_sym.hip). There is no dry run: a round needs

@@ -205,6 +205,9 @@ struct nexrRingComm {
   // channels (nexrRingCommGetDirect; counted on the top-level communicator).
   bool direct = false;
   std::atomic<uint64_t> directSlices{0}, fifoSlices{0};
+  // nexrRingCommSetFlat: the plain ring all-reduce, reduce-scatter and reduce run as one nexrFlat* launch
+  // where the communicator is eligible (flatRouted, nexr_ring.cpp); lastLLMode reports 4 after such a call.
+  bool flat = false;
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;

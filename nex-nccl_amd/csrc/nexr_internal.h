@@ -245,6 +245,35 @@ static_assert(sizeof(SymLLParams) <= 4096, "kernel argument block");
 hipError_t launch_sym_ll(int coll, int dt, const SymLLParams& p, hipStream_t s);
 hipError_t sym_ll_blocks_per_cu(int coll, int dt, int* blocks);
 
+// The ring all-reduce, reduce-scatter and reduce in one launch with the ring's bytes (nexrFlatAllReduce,
+// nexrFlatReduceScatter, nexrFlatReduce; nexr_flat.hip). A region is what a wave's pieces are cut from: the
+// all-reduce's and the reduce's whole buffer, one chunk of the reduce-scatter (chunk d of an input starts at
+// byte d * regionBytes). The all-reduce's channel parts ride in the kernel arguments, or, beyond
+// kFlatInlineParts of them, in a stream-ordered workspace (`ext`).
+enum { kFlatAllReduce = 0, kFlatReduceScatter = 1, kFlatReduce = 2 };
+constexpr int kFlatInlineParts = NEXR_FLAT_INLINE_PARTS;
+struct FlatParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];  // the reduce: out[root] only
+  uint64_t regionBytes;
+  uint64_t redArg;
+  const nexrFlatPart* ext;  // non-null: the parts are there, not in parts[]
+  int coll, nRanks;
+  int nFold;      // inputs that enter the chain: nRanks, or 1 under nexrSemanticsShipped
+  int shift;      // the folded inputs start at rank s + shift (0, or the chain's last rank under shipped SIMPLE)
+  int userFirst;  // SIMPLE: the rank's own input is a step's first operand; else the partial is
+  int preOp, postOp, root, nParts, pad;
+  nexrFlatPart parts[kFlatInlineParts];
+};
+static_assert(sizeof(FlatParams) <= 4000, "kernel argument block");
+struct FlatPartsFill {
+  nexrFlatPart* dst;
+  int n, pad;
+  nexrFlatPart parts[kFlatInlineParts];
+};
+hipError_t launch_flat(int dt, int op, const FlatParams& p, unsigned grid, hipStream_t s);
+hipError_t launch_flat_parts(const FlatPartsFill& f, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

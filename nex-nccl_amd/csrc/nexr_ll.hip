@@ -1195,3 +1195,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 #include "nexr_simple.hip"
 // The symmetric all-reduce in one launch: the same code object again.
 #include "nexr_sym.hip"
+// The ring collectives in one launch with the ring's bytes: the same code object again.
+#include "nexr_flat.hip"

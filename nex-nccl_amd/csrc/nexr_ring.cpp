@@ -1165,7 +1165,7 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
 // is touched. `count` is what the one-rank path copies.
 template <typename Launch>
 nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                           int datatype, Launch launch) {
+                           int datatype, Launch launch, const nexrDevRedOpFull* oneRankOp = nullptr) {
   const int n = c->cfg.nRanks;
   for (int i = 0; i < n; i++)
     if (count != 0 && (!sendbuffs[i] || !recvbuffs[i])) return nexrInvalidArgument;
@@ -1178,6 +1178,7 @@ nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* 
   if (count == 0) return nexrSuccess;
   if (n == 1) {
     nexrDevRedOpFull red;
+    if (oneRankOp) return oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, *oneRankOp, nexrTypeSize(datatype));
     const nexrResult_t r = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
     return r != nexrSuccess ? r : oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, nexrTypeSize(datatype));
   }
@@ -1233,6 +1234,70 @@ nexrResult_t symAllGather(nexrRingComm* c, const void* const* sendbuffs, void* c
   return symCollective(c, sendbuffs, recvbuffs, sendcount, datatype, [&](int n, nexrStream_t stream) {
     return nexrSymAllGather(n, sendbuffs, recvbuffs, sendcount * esz, stream);
   });
+}
+
+// The flat entries (nexrRingAllReduceFlat, nexrRingReduceScatterFlat, nexrRingReduceFlat): the ring collective
+// of the plain call as ONE nexrFlat* launch over every rank's buffers, on symCollective's checks and wait. The
+// op is encoded as for the ring (prepare: Avg becomes PreMulSum or SumPostDiv), the all-reduce's parts are
+// the plain call's own (channelParts and every channel's chunkElems for this communicator's protocol), and a
+// SIMPLE communicator folds the user input first. No connection and no step counter is touched, so flat and
+// FIFO calls may alternate.
+nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
+                            size_t count, int datatype, int op, int root) {
+  if (!c || c->peer) return nexrInvalidArgument;
+  size_t esz;
+  nexrDevRedOpFull red;
+  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  if (r != nexrSuccess) return r;
+  const int n = c->cfg.nRanks;
+  if (coll == kReduce && (root < 0 || root >= n)) return nexrInvalidArgument;
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  // a reduce needs the root's recvbuff only, as the plain call
+  std::vector<void*> outs(recvbuffs, recvbuffs + n);
+  if (coll == kReduce)
+    for (int i = 0; i < n; i++) outs[i] = recvbuffs[root];
+  const int userFirst = c->proto == nexrRingProtoSimple ? 1 : 0;
+  return symCollective(
+      c, sendbuffs, outs.data(), count, datatype,
+      [&](int nr, nexrStream_t stream) {
+        if (coll == kReduceScatter)
+          return nexrFlatReduceScatter(nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst,
+                                       stream);
+        if (coll == kReduce)
+          return nexrFlatReduce(nr, sendbuffs, recvbuffs[root], root, count, datatype, red.op, red.scalarArg,
+                                userFirst, stream);
+        std::vector<nexrFlatPart> parts;
+        for (const ChannelPart& part : channelParts(c, (int64_t)count, esz, /*ncclFuncAllReduce*/ 2))
+          parts.push_back({(uint64_t)part.offset, (uint64_t)part.count,
+                           (uint64_t)chunkElems(channelComm(c, part.channel), kGeomRing, esz, false, 0)});
+        return nexrFlatAllReduce(nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst,
+                                 parts.data(), (int)parts.size(), stream);
+      },
+      &red);
+}
+
+// nexrRingCommSetFlat: whether the plain ring all-reduce, reduce-scatter and reduce of this communicator run
+// flat. Thread ranks in device memory on one GPU with the library's own kernels for the protocol (a caller's
+// fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes.
+bool flatRouted(const nexrRingComm* c) {
+  if (!c || !c->flat || c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || c->streams.empty() ||
+      !c->streams[0] || c->cfg.nRanks > NEXR_SYM_MAX_RANKS || (int)c->devices.size() < c->cfg.nRanks)
+    return false;
+  const bool ownFn = c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
+                     : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
+                                                      : c->cfg.fn == defaultDeviceFn;
+  if (!ownFn) return false;
+  for (int d : c->devices)
+    if (d != c->devices[0]) return false;
+  return true;
+}
+
+nexrResult_t ringOrFlat(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
+                        size_t count, int datatype, int op, int root) {
+  if (!flatRouted(c)) return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root);
+  const nexrResult_t r = flatCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root);
+  if (r == nexrSuccess) c->lastLLMode = 4;
+  return r;
 }
 
 // The symmetric LL entries (nexrRingAllReduceSymmetricLL, nexrRingReduceScatterSymmetricLL,
@@ -1433,13 +1498,13 @@ NEXR_API nexrResult_t nexrRingCommCreate(nexrRingComm_t* out, const nexrRingConf
 NEXR_API nexrResult_t nexrRingAllReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op) {
   DeviceGuard dg(c && c->needHip);
-  return ringCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+  return ringOrFlat(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatter(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t recvcount, int datatype, int op) {
   DeviceGuard dg(c && c->needHip);
-  return ringCollective(c, kReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0);
+  return ringOrFlat(c, kReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllGather(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
@@ -1451,7 +1516,7 @@ NEXR_API nexrResult_t nexrRingAllGather(nexrRingComm_t c, const void* const* sen
 NEXR_API nexrResult_t nexrRingReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                      size_t count, int datatype, int op, int root) {
   DeviceGuard dg(c && c->needHip);
-  return ringCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+  return ringOrFlat(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
 }
 
 NEXR_API nexrResult_t nexrRingBroadcast(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
@@ -1484,6 +1549,31 @@ NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t c, const void* c
                                                  void* const* recvbuffs, size_t sendcount, int datatype) {
   DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
   return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
+}
+
+NEXR_API nexrResult_t nexrRingAllReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                            size_t count, int datatype, int op) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return flatCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+}
+
+NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t c, const void* const* sendbuffs,
+                                                void* const* recvbuffs, size_t recvcount, int datatype, int op) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return flatCollective(c, kReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0);
+}
+
+NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                         size_t count, int datatype, int op, int root) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return flatCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+}
+
+NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t c, int on) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer || c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
+  c->flat = on != 0;
+  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,

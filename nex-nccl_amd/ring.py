@@ -23,6 +23,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingReduceScatterSymmetric", "nexrRingAllGatherSymmetric",
                     "nexrRingAllReduceSymmetricLL", "nexrRingReduceScatterSymmetricLL",
                     "nexrRingAllGatherSymmetricLL",
+                    "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
                     "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
@@ -79,6 +80,10 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingAllReduceSymmetricLL.argtypes = [vp, arr, arr, sz, i32, i32, i32]
     L.nexrRingReduceScatterSymmetricLL.argtypes = [vp, arr, arr, sz, i32, i32, i32]
     L.nexrRingAllGatherSymmetricLL.argtypes = [vp, arr, arr, sz, i32, i32]
+    L.nexrRingAllReduceFlat.argtypes = [vp, arr, arr, sz, i32, i32]
+    L.nexrRingReduceScatterFlat.argtypes = [vp, arr, arr, sz, i32, i32]
+    L.nexrRingReduceFlat.argtypes = [vp, arr, arr, sz, i32, i32, i32]
+    L.nexrRingCommSetFlat.argtypes = [vp, i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
@@ -284,6 +289,38 @@ class RingComm:
         _check(self._L.nexrRingAllGatherSymmetricLL(self._h, s, r, int(sendcount), int(datatype), int(n_blocks)),
                "nexrRingAllGatherSymmetricLL")
 
+    def all_reduce_flat(self, sendbuffs, recvbuffs, count: int, datatype: int, op: int) -> None:
+        """The ring's ncclAllReduce as ONE launch with the ring's own bytes (nexrRingAllReduceFlat): the chain
+        of one reduce-copy step per rank runs in registers, over this communicator's own chunks, user input
+        first for SIMPLE and partial first for LL / LL128. Every datatype and op of all_reduce. Thread ranks,
+        device memory, every rank on one GPU (else InvalidUsage). Touches no connection: mixes with ring,
+        tree and group calls, queued() stays as it was."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllReduceFlat(self._h, s, r, int(count), int(datatype), int(op)),
+               "nexrRingAllReduceFlat")
+
+    def reduce_scatter_flat(self, sendbuffs, recvbuffs, recvcount: int, datatype: int, op: int) -> None:
+        """The ring's ncclReduceScatter as ONE launch with the ring's own bytes (nexrRingReduceScatterFlat):
+        chunk d is folded from rank d + 1 on and ends at rank d. Rules as all_reduce_flat."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingReduceScatterFlat(self._h, s, r, int(recvcount), int(datatype), int(op)),
+               "nexrRingReduceScatterFlat")
+
+    def reduce_flat(self, sendbuffs, recvbuffs, count: int, datatype: int, op: int, root: int) -> None:
+        """The ring's ncclReduce as ONE launch with the ring's own bytes (nexrRingReduceFlat): the chain starts
+        at root + 1 and ends at root; only recvbuffs[root] is needed and written. Rules as all_reduce_flat."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingReduceFlat(self._h, s, r, int(count), int(datatype), int(op), int(root)),
+               "nexrRingReduceFlat")
+
+    def set_flat(self, on: bool) -> None:
+        """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat): all_reduce,
+        reduce_scatter and reduce then run as their _flat forms where the communicator is eligible (thread
+        ranks, device memory, one GPU, the library's own kernels), with the same bytes, and queued() == 4
+        after such a call; every other call runs as without it. Between collectives; InvalidUsage for
+        process-rank or host-memory communicators."""
+        _check(self._L.nexrRingCommSetFlat(self._h, 1 if on else 0), "nexrRingCommSetFlat")
+
     def send_recv(self, sendbuffs, send_peers, recvbuffs, recv_peers, nbytes: int) -> None:
         """ncclSend/ncclRecv of every rank in one group: rank r sends nbytes of sendbuffs[r] to
         send_peers[r] and receives nbytes from recv_peers[r] into recvbuffs[r] (-1: none)."""
@@ -300,7 +337,8 @@ class RingComm:
         return "word" if w.value else "sync"
 
     def queued(self) -> int:
-        """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 3 group launches on
+        """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 4 one flat launch (set_flat),
+        3 group launches on
         one stream (set_ll_group; set_simple_group for SIMPLE), 2 runs on the device with device credits, 1 queued launches,
         0 host-sequenced (LL steps need every rank on one GPU and device memory for 1, 2 or 3; 1 and 2
         also a hardware queue per rank stream). While set_ll_group is on, a tree_all_reduce reports here
