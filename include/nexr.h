@@ -910,6 +910,67 @@ NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void
                                      nexrStream_t stream);
 
 /*
+ * nexrFlatTreeAllReduce, nexrFlatBroadcast — the TREE all-reduce (runTreeSplit, reference
+ * src/device/all_reduce.h:150-230) and the broadcast (broadcast.h:12-58) of nRanks ranks on ONE GPU, each as
+ * one launch that writes the bytes the FIFO collective writes. Datatypes, ops, operand orders, alignment,
+ * aliasing, semantics and stream order as nexrFlatAllReduce above; additions only, the ABI stays 0.3.
+ *
+ * Trees. trees[t][r] = {up, down[3]} are the links of rank r in tree t (nTrees 1 or 2: the double binary tree's
+ * two); -1 is no link, children are packed first. parts[k] = {offset, count, tree} in elements tile [0, nElts)
+ * in ascending order (the channels' parts); every offset is a multiple of 16 / esz, so no 16-byte pack holds
+ * elements of two parts. The chunking inside a part does not enter the result.
+ *
+ * Rule for one element of a part whose tree is t. Every rank r has a value(r), ONE reduce-copy step over its
+ * own input and its children's values in down[] order:
+ *   acc = in[r] through the pre-op (nexrDevPreMulSum: times the scalar; the rank's own input only).
+ *   For each child k in down[] order: acc = op(acc, value(k)) when userFirst != 0 (SIMPLE: srcs[0] is the user
+ *     input, a left fold), acc = op(value(k), acc) when userFirst == 0 (LL, LL128: the peer is the first
+ *     operand, prims_ll.h:251-258). Every op rounds to the datatype; the step ends with the fp16 / bf16 NaN
+ *     canonicalisation. Nothing is contracted.
+ *   A leaf's value is the K = 1 step: a bit copy without a pre-op (NaN payloads survive), the product and that
+ *     step's canonicalisation with one.
+ *   The root's step ends with the nexrDevSumPostDiv post-op; its value goes to all n outputs.
+ * Under nexrSemanticsShipped every reduce returns its first operand without pre-op or post-op: the result is a
+ * bit copy of the root's input with userFirst, and without it of the input of the leaf reached from the root
+ * through every rank's LAST child.
+ *
+ * How it runs. Each tree is compiled on the host into a program of one-byte instructions (LEAF r, JOIN r,
+ * PUSH, MERGE; at most 3n - 2) that the kernel interprets in registers: from the root, down[0]'s value first,
+ * then the rank's own input, then for every further child the accumulator is saved, the child evaluated and
+ * the two merged. A program may keep at most NEXR_FLAT_TREE_SLOTS values alive at once (the accumulator and the
+ * saved ones); every topology the ring library builds up to 64 ranks needs 6 at the most.
+ *
+ * nexrFlatBroadcast copies nBytes from input (the root's) to every outputs[r] whose address differs from it:
+ * a bit copy at any byte alignment. An output may equal the input whole; any other overlap is undefined.
+ *
+ * nElts == 0 / nBytes == 0 succeed without a launch. Only an all-reduce with more than
+ * NEXR_FLAT_TREE_INLINE_PARTS parts takes a (stream-ordered) workspace. nexrInvalidArgument, before any device
+ * call: everything nexrFlatAllReduce refuses for its buffers, datatype, op and sizes; nTrees outside 1..2 or a
+ * null tree; a part naming a missing tree; parts that do not tile [0, nElts) in ascending order, hold an empty
+ * part or begin off a multiple of 16 / esz; links that are not ONE spanning tree (exactly one root, every up
+ * matched by its parent's down and every down by its child's up, no cycle, no rank out of range, children
+ * packed first); a program that needs more than NEXR_FLAT_TREE_SLOTS live values.
+ */
+typedef struct {
+  int up;      /* the parent, -1 at the root */
+  int down[3]; /* the children in fold order, packed first, -1 for none */
+} nexrFlatTreeLinks;
+typedef struct {
+  uint64_t offset; /* first element of the channel's part */
+  uint64_t count;  /* its elements */
+  uint32_t tree;   /* index into trees */
+  uint32_t pad;    /* 0 */
+} nexrFlatTreePart;
+#define NEXR_FLAT_TREE_SLOTS 8
+#define NEXR_FLAT_TREE_INLINE_PARTS 96
+NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
+                                            const nexrFlatTreePart* parts, int nParts, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
+                                        nexrStream_t stream);
+
+/*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
  * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.

@@ -215,16 +215,39 @@ NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t comm, const void*
 NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
                                          size_t count, int datatype, int op, int root);
 
-/* Opt-in, off by default: with on != 0, nexrRingAllReduce, nexrRingReduceScatter and nexrRingReduce on an
- * eligible communicator run as the flat entries above, and nexrRingCommGetQueued reports 4 after such a call.
- * Eligible: thread ranks, device memory, every rank on one GPU, at most NEXR_SYM_MAX_RANKS ranks and the
- * library's own fn (SIMPLE), llFn (LL) or ll128Fn (LL128): a caller's function may compute anything. On any
- * other communicator, and for the all-gather, the broadcast and nexrTreeAllReduce, the calls run exactly as
- * without the option. The results are the same bytes either way, and the option may be toggled between
- * collectives and combined with the group options (a routed call ignores them). With the option off nothing
- * changes.
+/* The tree all-reduce, the broadcast and the all-gather as ONE launch each with the FIFO collective's own bytes,
+ * through the same helper as the three entries above (thread ranks on one GPU with device memory or
+ * nexrInvalidUsage, the communicator's first stream and its wait, one rank takes the one-rank path, a count of
+ * 0 succeeds; no connection, no step counter and not nexrRingCommGetQueued's report is touched). The argument
+ * lists are the plain calls'.
+ *   nexrTreeAllReduceFlat: nexrFlatTreeAllReduce (include/nexr.h: every rank's one step over its own input and
+ *     its children's values, interpreted in registers) with this communicator's channel parts, every
+ *     channel's own tree (the upper half of 2+ channels runs the other tree of the double binary tree) and
+ *     the protocol's operand order; the op is encoded as the plain call's.
+ *   nexrRingBroadcastFlat: nexrFlatBroadcast of sendbuffs[root]; only that send buffer is needed.
+ *   nexrRingAllGatherFlat: nexrSymAllGather under the flat name, whose bytes are the ring's already.
+ * Measured numbers: DESIGN §8.8 (tools/flat_tree_probe.py). */
+NEXR_API nexrResult_t nexrTreeAllReduceFlat(nexrRingComm_t comm, const void* const* sendbuffs,
+                                            void* const* recvbuffs, size_t count, int datatype, int op);
+NEXR_API nexrResult_t nexrRingBroadcastFlat(nexrRingComm_t comm, const void* const* sendbuffs,
+                                            void* const* recvbuffs, size_t count, int datatype, int root);
+NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* const* sendbuffs,
+                                            void* const* recvbuffs, size_t sendcount, int datatype);
+
+/* Opt-in, off by default: which plain calls on an eligible communicator run as their flat entries above. `on`
+ * is read as bits: NEXR_FLAT_RING (1) routes nexrRingAllReduce, nexrRingReduceScatter and nexrRingReduce;
+ * NEXR_FLAT_TREE (2) routes nexrTreeAllReduce; NEXR_FLAT_COPIES (4) routes nexrRingAllGather and
+ * nexrRingBroadcast. nexrRingCommGetQueued reports 4 after a routed call. Eligible: thread ranks, device
+ * memory, every rank on one GPU, at most NEXR_SYM_MAX_RANKS ranks and the library's own fn (SIMPLE), llFn (LL)
+ * or ll128Fn (LL128): a caller's function may compute anything. On any other communicator, and for the calls
+ * whose bit is not set, the calls run exactly as without the option. The results are the same bytes either way,
+ * and the option may be changed between collectives and combined with the group options (a routed call ignores
+ * them). With 0 nothing changes; with 1 exactly the three ring reductions are routed.
  *
- * nexrInvalidUsage for process-rank or host-memory communicators. */
+ * nexrInvalidArgument for any other bit; nexrInvalidUsage for process-rank or host-memory communicators. */
+#define NEXR_FLAT_RING 1
+#define NEXR_FLAT_TREE 2
+#define NEXR_FLAT_COPIES 4
 NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t comm, int on);
 
 /* The tree links of `rank` in this communicator's topology: *up (-1 at the root) and down[0..2]

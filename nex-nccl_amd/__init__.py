@@ -92,6 +92,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrSymReduceScatter", "nexrSymAllGather", "nexrSymLLWindowBytes", "nexrSymLLAllReduce",
                "nexrSymLLReduceScatter", "nexrSymLLAllGather",
                "nexrFlatAllReduce", "nexrFlatReduceScatter", "nexrFlatReduce",
+               "nexrFlatTreeAllReduce", "nexrFlatBroadcast",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -110,6 +111,17 @@ class NexrError(RuntimeError):
 class FlatPart(ctypes.Structure):
     """nexrFlatPart: one channel's part of a flat all-reduce, in elements."""
     _fields_ = [("offset", ctypes.c_uint64), ("count", ctypes.c_uint64), ("chunkCount", ctypes.c_uint64)]
+
+
+class FlatTreeLinks(ctypes.Structure):
+    """nexrFlatTreeLinks: one rank's links in a tree, -1 for none, children packed first."""
+    _fields_ = [("up", ctypes.c_int), ("down", ctypes.c_int * 3)]
+
+
+class FlatTreePart(ctypes.Structure):
+    """nexrFlatTreePart: one channel's part of a flat tree all-reduce, in elements, and its tree's index."""
+    _fields_ = [("offset", ctypes.c_uint64), ("count", ctypes.c_uint64), ("tree", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
 
 
 class DevRedOpFull(ctypes.Structure):
@@ -337,6 +349,11 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatReduceScatter.restype = i32
     L.nexrFlatReduce.argtypes = [i32, P(vp), vp, i32, sz, i32, i32, u64, i32, vp]
     L.nexrFlatReduce.restype = i32
+    L.nexrFlatTreeAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, i32, P(P(FlatTreeLinks)), i32,
+                                        P(FlatTreePart), i32, vp]
+    L.nexrFlatTreeAllReduce.restype = i32
+    L.nexrFlatBroadcast.argtypes = [i32, vp, P(vp), sz, vp]
+    L.nexrFlatBroadcast.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
     L.nexrSymLLWindowBytes.restype = i32
     L.nexrSymLLAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, P(vp), sz, i32, vp, ctypes.c_uint32, vp]
@@ -896,6 +913,51 @@ def flat_reduce(inputs: Sequence[int], output: int, root: int, n_elts: int, data
                               int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0,
                               ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatReduce")
+
+
+FLAT_TREE_SLOTS = 8          # NEXR_FLAT_TREE_SLOTS
+FLAT_TREE_INLINE_PARTS = 96  # NEXR_FLAT_TREE_INLINE_PARTS
+
+
+def flat_tree_links(trees: Sequence[Sequence[tuple]]):
+    """(array of nexrFlatTreeLinks pointers, keep-alive) for ``trees[t][r] = (up, [down...])``."""
+    rows = []
+    for links in trees:
+        row = (FlatTreeLinks * max(1, len(links)))()
+        for r, (up, down) in enumerate(links):
+            d = [int(x) for x in down] + [-1] * (3 - len(down))
+            row[r] = FlatTreeLinks(int(up), (ctypes.c_int * 3)(*d[:3]))
+        rows.append(row)
+    arr = (ctypes.POINTER(FlatTreeLinks) * max(1, len(rows)))(
+        *[ctypes.cast(row, ctypes.POINTER(FlatTreeLinks)) for row in rows])
+    return arr, rows
+
+
+def flat_tree_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int, dev_red_op: int,
+                         red_op_arg: int, user_first: bool, trees: Sequence[Sequence[tuple]], parts: Sequence[tuple],
+                         stream: int = 0) -> None:
+    """The tree all-reduce of len(inputs) ranks on one GPU in ONE launch with the FIFO tree's bytes
+    (``nexrFlatTreeAllReduce``): every rank's one reduce-copy step over its own input and its children's values
+    in down[] order, interpreted in registers. ``trees[t][r] = (up, [down...])`` (one or two trees), ``parts``
+    are the channels' (offset, count, tree) in elements, tiling [0, n_elts) in ascending order; ``user_first``
+    is the SIMPLE operand order, False the LL / LL128 one. In place allowed. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    tarr, _keep = flat_tree_links(trees)
+    arr = (FlatTreePart * max(1, len(parts)))(*[FlatTreePart(int(o), int(c), int(t), 0) for o, c, t in parts])
+    rc = lib().nexrFlatTreeAllReduce(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                     int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0,
+                                     tarr, len(trees), arr, len(parts),
+                                     ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatTreeAllReduce")
+
+
+def flat_broadcast(input: int, outputs: Sequence[int], n_bytes: int, stream: int = 0) -> None:
+    """The broadcast in ONE launch (``nexrFlatBroadcast``): ``n_bytes`` of ``input`` to every output whose address
+    differs from it, a bit copy at any byte alignment. Stream-ordered."""
+    rc = lib().nexrFlatBroadcast(len(outputs), ctypes.c_void_p(int(input)) if input else None, _ptr_array(outputs),
+                                 int(n_bytes), ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatBroadcast")
 
 
 SYM_LL_HEADER_BYTES = 256  # NEXR_SYM_LL_HEADER_BYTES

@@ -2416,6 +2416,189 @@ NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void
   return nexrSuccess;
 }
 
+// ---- nexrFlatTreeAllReduce, nexrFlatBroadcast ---------------------------------------------------------------
+namespace {
+// One tree's links as a program (include/nexr.h): from the root, down[0]'s value first, then the rank's own
+// input, then for every further child PUSH, the child, MERGE. `need` is the most values alive at once (the
+// accumulator and the saved ones). False: the links are not one spanning tree with packed children.
+bool flatTreeCompile(const nexrFlatTreeLinks* links, int n, std::vector<uint8_t>* code, int* need, int* root) {
+  int nRoots = 0, slots = 0;
+  *root = -1;
+  for (int r = 0; r < n; r++) {
+    const nexrFlatTreeLinks& l = links[r];
+    if (l.up < -1 || l.up >= n || l.up == r) return false;
+    if (l.up == -1) {
+      nRoots++;
+      *root = r;
+    } else {  // every up matched by its parent's down, once
+      const nexrFlatTreeLinks& p = links[l.up];
+      if ((p.down[0] == r) + (p.down[1] == r) + (p.down[2] == r) != 1) return false;
+    }
+    bool ended = false;
+    for (int k = 0; k < 3; k++) {
+      const int d = l.down[k];
+      if (d < -1 || d >= n) return false;
+      if (d == -1) {
+        ended = true;
+        continue;
+      }
+      if (ended || links[d].up != r) return false;  // packed first; every down matched by its child's up
+      slots++;
+    }
+  }
+  // one parent each and n - 1 child slots, every one its child's up: every rank but the root is some rank's
+  // child exactly once
+  if (nRoots != 1 || slots != n - 1) return false;
+  code->clear();
+  int depth = 0, most = 1;
+  // iterative walk: (rank, next child) frames; a rank has one parent, so what the root reaches is a tree
+  std::vector<std::pair<int, int>> stack{{*root, 0}};
+  int seen = 0;
+  while (!stack.empty()) {
+    const int r = stack.back().first, k = stack.back().second;
+    const nexrFlatTreeLinks& l = links[r];
+    const int nd = l.down[0] < 0 ? 0 : l.down[1] < 0 ? 1 : l.down[2] < 0 ? 2 : 3;
+    if (nd == 0) {
+      code->push_back((uint8_t)(kFlatTreeLeaf << 6 | r));
+      seen++;
+      stack.pop_back();
+      continue;
+    }
+    if (k == 1) {  // behind down[0]
+      code->push_back((uint8_t)(kFlatTreeJoin << 6 | r));
+      seen++;
+    } else if (k > 1) {  // behind a further child
+      code->push_back((uint8_t)(kFlatTreeMerge << 6));
+      depth--;
+    }
+    if (k == nd) {
+      stack.pop_back();
+      continue;
+    }
+    if (k >= 1) {
+      code->push_back((uint8_t)(kFlatTreePush << 6));
+      depth++;
+      most = std::max(most, depth + 1);
+    }
+    stack.back().second = k + 1;
+    stack.push_back({l.down[k], 0});
+  }
+  if (seen != n) return false;  // ranks the root does not reach: a cycle among them
+  *need = most;
+  return true;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
+                                            const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
+  FlatParams fp;  // the shared checks and what the semantics make of the call
+  int dt, op;
+  if (!outputs) return nexrInvalidArgument;
+  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &fp, &dt, &op);
+  if (res != nexrSuccess) return res;
+  const uint64_t esz = typeSize(datatype), epp = 16 / esz;
+  FlatTreeParams p;
+  memset((void*)&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
+    p.in[r] = fp.in[r];
+    p.out[r] = (char*)outputs[r];
+  }
+  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
+  if (!trees || nTrees < 1 || nTrees > 2) return nexrInvalidArgument;
+  if (nParts < 0 || (nParts > 0 && !parts)) return nexrInvalidArgument;
+  const bool firstWins = fp.nFold == 1;
+  for (int t = 0; t < nTrees; t++) {
+    if (!trees[t]) return nexrInvalidArgument;
+    std::vector<uint8_t> code;
+    int need = 0, root = -1;
+    if (!flatTreeCompile(trees[t], nRanks, &code, &need, &root)) return nexrInvalidArgument;
+    if (need > kFlatTreeSlots || code.size() > (size_t)kFlatTreeProgBytes) return nexrInvalidArgument;
+    if (firstWins) {  // every reduce returns its first operand: one rank's input survives
+      int r = root;
+      if (!userFirst)
+        while (trees[t][r].down[0] >= 0) {  // the peer is first, the last child's last
+          const nexrFlatTreeLinks& l = trees[t][r];
+          r = l.down[2] >= 0 ? l.down[2] : l.down[1] >= 0 ? l.down[1] : l.down[0];
+        }
+      code.assign(1, (uint8_t)(kFlatTreeLeaf << 6 | r));
+    }
+    uint8_t order[NEXR_SYM_MAX_RANKS] = {0};
+    int nIn = 0;
+    for (uint8_t ins : code)
+      if ((ins >> 6) <= kFlatTreeJoin) order[nIn++] = ins & 63;
+    FlatTreeProgram& g = p.prog[t];
+    memcpy(g.code, code.data(), code.size());
+    memcpy(g.order, order, sizeof(order));
+    g.nCode = (int)code.size();
+    g.nIn = nIn;
+  }
+  uint64_t at = 0;
+  for (int k = 0; k < nParts; k++) {  // ascending, gapless, from 0
+    const nexrFlatTreePart& q = parts[k];
+    if (q.offset != at || q.count == 0 || q.count > (uint64_t)nElts - at) return nexrInvalidArgument;
+    if (q.offset % epp || q.tree >= (uint32_t)nTrees) return nexrInvalidArgument;
+    at += q.count;
+  }
+  if (at != (uint64_t)nElts) return nexrInvalidArgument;
+  if (nElts == 0) return nexrSuccess;
+  p.nBytes = (uint64_t)nElts * esz;
+  p.redArg = fp.redArg;
+  p.nRanks = nRanks;
+  p.userFirst = fp.userFirst;
+  p.preOp = fp.preOp;
+  p.postOp = fp.postOp;
+  p.nParts = nParts;
+  hipStream_t s = (hipStream_t)stream;
+  nexrFlatTreePart* ws = nullptr;
+  if (nParts <= kFlatTreeInlineParts) {
+    memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatTreePart));
+  } else {  // the parts travel by value in short launches ahead of the one: nothing is read after return
+    NEXR_HIP(hipMallocAsync((void**)&ws, (size_t)nParts * sizeof(nexrFlatTreePart), s));
+    FlatTreePartsFill f;
+    for (int k = 0; k < nParts; k += kFlatTreeInlineParts) {
+      f.dst = ws + k;
+      f.n = std::min(kFlatTreeInlineParts, nParts - k);
+      f.pad = 0;
+      memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatTreePart));
+      const hipError_t e = launch_flat_tree_parts(f, s);
+      if (e != hipSuccess) {
+        (void)hipFreeAsync(ws, s);
+        return hipFail(e);
+      }
+    }
+    p.ext = ws;
+  }
+  const hipError_t e = launch_flat_tree(dt, op, p, flatGrid(p.nBytes, 1), s);
+  if (ws) (void)hipFreeAsync(ws, s);
+  NEXR_HIP(e);
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
+                                        nexrStream_t stream) {
+  if (!input || !outputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  FlatBcastParams p;
+  memset((void*)&p, 0, sizeof(p));
+  bool any = false;
+  for (int r = 0; r < nRanks; r++) {
+    if (!outputs[r]) return nexrInvalidArgument;
+    if (outputs[r] != input) {
+      p.out[r] = (char*)outputs[r];
+      any = true;
+    }
+  }
+  if (nBytes == 0 || !any) return nexrSuccess;
+  p.in = (const char*)input;
+  p.nBytes = nBytes;
+  p.nRanks = nRanks;
+  NEXR_HIP(launch_flat_bcast(p, flatGrid(nBytes, 1), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
 // ---- nexrSymLLAllReduce, nexrSymLLReduceScatter, nexrSymLLAllGather -----------------------------------------
 // Two things make a launch finish: its grid of nRanks * nBlocks teams is resident as a whole (the occupancy
 // check below), and every poll of its kernel is bounded (nexr_sym.hip). There is no dry run: a round needs

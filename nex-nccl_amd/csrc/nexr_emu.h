@@ -205,9 +205,10 @@ struct nexrRingComm {
   // channels (nexrRingCommGetDirect; counted on the top-level communicator).
   bool direct = false;
   std::atomic<uint64_t> directSlices{0}, fifoSlices{0};
-  // nexrRingCommSetFlat: the plain ring all-reduce, reduce-scatter and reduce run as one nexrFlat* launch
-  // where the communicator is eligible (flatRouted, nexr_ring.cpp); lastLLMode reports 4 after such a call.
-  bool flat = false;
+  // nexrRingCommSetFlat: the plain calls whose bit is set (NEXR_FLAT_RING: the ring all-reduce, reduce-scatter
+  // and reduce; NEXR_FLAT_TREE: the tree all-reduce; NEXR_FLAT_COPIES: all-gather and broadcast) run as one flat
+  // launch where the communicator is eligible (flatRouted, nexr_ring.cpp); lastLLMode reports 4 after such a call.
+  int flat = 0;
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;

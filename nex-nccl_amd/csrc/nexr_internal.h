@@ -274,6 +274,44 @@ struct FlatPartsFill {
 hipError_t launch_flat(int dt, int op, const FlatParams& p, unsigned grid, hipStream_t s);
 hipError_t launch_flat_parts(const FlatPartsFill& f, hipStream_t s);
 
+// The tree all-reduce and the broadcast in one launch (nexrFlatTreeAllReduce, nexrFlatBroadcast;
+// nexr_flat_tree.hip). A tree travels as a program of one-byte instructions, opcode << 6 | rank, and as the
+// ranks in the order the program consumes their inputs (what the kernel's loads run ahead on).
+enum { kFlatTreeLeaf = 0, kFlatTreeJoin = 1, kFlatTreePush = 2, kFlatTreeMerge = 3 };
+constexpr int kFlatTreeSlots = NEXR_FLAT_TREE_SLOTS;  // live values: the accumulator and the saved ones
+constexpr int kFlatTreeInlineParts = NEXR_FLAT_TREE_INLINE_PARTS;
+constexpr int kFlatTreeProgBytes = 3 * NEXR_SYM_MAX_RANKS;  // 3n - 2 instructions at the most
+struct FlatTreeProgram {
+  uint32_t code[kFlatTreeProgBytes / 4];    // bytes, packed little-endian: the kernel loads dwords
+  uint32_t order[NEXR_SYM_MAX_RANKS / 4];   // rank of the j-th LEAF / JOIN, packed likewise
+  int nCode, nIn;                           // nIn: n, or 1 under nexrSemanticsShipped
+};
+struct FlatTreeParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t nBytes;
+  uint64_t redArg;
+  const nexrFlatTreePart* ext;  // non-null: the parts are there, not in parts[]
+  int nRanks, userFirst, preOp, postOp, nParts, pad;
+  FlatTreeProgram prog[2];
+  nexrFlatTreePart parts[kFlatTreeInlineParts];
+};
+static_assert(sizeof(FlatTreeParams) <= 4000, "kernel argument block");
+struct FlatTreePartsFill {
+  nexrFlatTreePart* dst;
+  int n, pad;
+  nexrFlatTreePart parts[kFlatTreeInlineParts];
+};
+struct FlatBcastParams {
+  const char* in;
+  char* out[NEXR_SYM_MAX_RANKS];  // null: not written (its address is the input's)
+  uint64_t nBytes;
+  int nRanks, pad;
+};
+hipError_t launch_flat_tree(int dt, int op, const FlatTreeParams& p, unsigned grid, hipStream_t s);
+hipError_t launch_flat_tree_parts(const FlatTreePartsFill& f, hipStream_t s);
+hipError_t launch_flat_bcast(const FlatBcastParams& p, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -1197,3 +1197,4 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 #include "nexr_sym.hip"
 // The ring collectives in one launch with the ring's bytes: the same code object again.
 #include "nexr_flat.hip"
+#include "nexr_flat_tree.hip"

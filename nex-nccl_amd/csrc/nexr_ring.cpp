@@ -1276,11 +1276,67 @@ nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* s
       &red);
 }
 
+// nexrTreeAllReduceFlat: the tree all-reduce of the plain call as ONE nexrFlatTreeAllReduce launch. The parts are
+// the plain call's (channelParts), every part runs its own channel's tree (the upper half of 2+ channels has
+// the other tree of the double binary tree), and the operand order is the protocol's. The chunking inside a
+// part (chunkElems(..., kGeomPipe, ...)) does not enter the result.
+nexrResult_t flatTreeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                               int datatype, int op) {
+  if (!c || c->peer) return nexrInvalidArgument;
+  size_t esz;
+  nexrDevRedOpFull red;
+  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  if (r != nexrSuccess) return r;
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  const int userFirst = c->proto == nexrRingProtoSimple ? 1 : 0;
+  return symCollective(
+      c, sendbuffs, recvbuffs, count, datatype,
+      [&](int nr, nexrStream_t stream) {
+        std::vector<std::vector<nexrFlatTreeLinks>> trees;  // the distinct trees of the parts' channels
+        std::vector<int> treeIndex;                         // their cfg.treeIndex
+        std::vector<nexrFlatTreePart> parts;
+        for (const ChannelPart& part : channelParts(c, (int64_t)count, esz, /*ncclFuncAllReduce*/ 2)) {
+          const nexrRingComm* ck = channelComm(c, part.channel);
+          size_t t = 0;
+          while (t < treeIndex.size() && treeIndex[t] != ck->cfg.treeIndex) t++;
+          if (t == treeIndex.size()) {
+            treeIndex.push_back(ck->cfg.treeIndex);
+            trees.emplace_back();
+            for (const TreeLinks& l : ck->tree) trees.back().push_back({l.up, {l.down[0], l.down[1], l.down[2]}});
+          }
+          parts.push_back({(uint64_t)part.offset, (uint64_t)part.count, (uint32_t)t, 0u});
+        }
+        const nexrFlatTreeLinks* tp[2] = {trees.size() > 0 ? trees[0].data() : nullptr,
+                                          trees.size() > 1 ? trees[1].data() : nullptr};
+        return nexrFlatTreeAllReduce(nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst, tp,
+                                     (int)trees.size(), parts.data(), (int)parts.size(), stream);
+      },
+      &red);
+}
+
+// nexrRingBroadcastFlat: the broadcast as ONE nexrFlatBroadcast launch of the root's send buffer; only that
+// send buffer is needed, as in the plain call.
+nexrResult_t flatBroadcast(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                           int datatype, int root) {
+  if (!c || c->peer) return nexrInvalidArgument;
+  size_t esz;
+  nexrDevRedOpFull red;
+  nexrResult_t r = prepare(c, datatype, nexrSum, &esz, &red);  // ncclBroadcast: ncclSum
+  if (r != nexrSuccess) return r;
+  const int n = c->cfg.nRanks;
+  if (root < 0 || root >= n || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (count > (size_t)-1 / esz) return nexrInvalidArgument;
+  std::vector<const void*> ins(n, sendbuffs[root]);
+  return symCollective(c, ins.data(), recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
+    return nexrFlatBroadcast(nr, sendbuffs[root], recvbuffs, count * esz, stream);
+  });
+}
+
 // nexrRingCommSetFlat: whether the plain ring all-reduce, reduce-scatter and reduce of this communicator run
 // flat. Thread ranks in device memory on one GPU with the library's own kernels for the protocol (a caller's
 // fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes.
-bool flatRouted(const nexrRingComm* c) {
-  if (!c || !c->flat || c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || c->streams.empty() ||
+bool flatRouted(const nexrRingComm* c, int bit = NEXR_FLAT_RING) {
+  if (!c || !(c->flat & bit) || c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || c->streams.empty() ||
       !c->streams[0] || c->cfg.nRanks > NEXR_SYM_MAX_RANKS || (int)c->devices.size() < c->cfg.nRanks)
     return false;
   const bool ownFn = c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
@@ -1296,6 +1352,25 @@ nexrResult_t ringOrFlat(nexrRingComm* c, RingColl coll, const void* const* sendb
                         size_t count, int datatype, int op, int root) {
   if (!flatRouted(c)) return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root);
   const nexrResult_t r = flatCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root);
+  if (r == nexrSuccess) c->lastLLMode = 4;
+  return r;
+}
+
+// The same for the tree all-reduce (NEXR_FLAT_TREE) and for the all-gather and the broadcast (NEXR_FLAT_COPIES).
+nexrResult_t treeOrFlat(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                        int datatype, int op) {
+  if (!flatRouted(c, NEXR_FLAT_TREE)) return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+  const nexrResult_t r = flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+  if (r == nexrSuccess) c->lastLLMode = 4;
+  return r;
+}
+
+nexrResult_t copyOrFlat(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
+                        size_t count, int datatype, int root) {
+  if (!flatRouted(c, NEXR_FLAT_COPIES))
+    return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, nexrSum, root);
+  const nexrResult_t r = coll == kAllGather ? symAllGather(c, sendbuffs, recvbuffs, count, datatype)
+                                            : flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
   if (r == nexrSuccess) c->lastLLMode = 4;
   return r;
 }
@@ -1510,7 +1585,7 @@ NEXR_API nexrResult_t nexrRingReduceScatter(nexrRingComm_t c, const void* const*
 NEXR_API nexrResult_t nexrRingAllGather(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t sendcount, int datatype) {
   DeviceGuard dg(c && c->needHip);
-  return ringCollective(c, kAllGather, sendbuffs, recvbuffs, sendcount, datatype, nexrSum, 0);  // ncclAllGather: ncclSum
+  return copyOrFlat(c, kAllGather, sendbuffs, recvbuffs, sendcount, datatype, 0);  // ncclAllGather: ncclSum
 }
 
 NEXR_API nexrResult_t nexrRingReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
@@ -1522,13 +1597,13 @@ NEXR_API nexrResult_t nexrRingReduce(nexrRingComm_t c, const void* const* sendbu
 NEXR_API nexrResult_t nexrRingBroadcast(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int root) {
   DeviceGuard dg(c && c->needHip);
-  return ringCollective(c, kBroadcast, sendbuffs, recvbuffs, count, datatype, nexrSum, root);  // ncclBroadcast: ncclSum
+  return copyOrFlat(c, kBroadcast, sendbuffs, recvbuffs, count, datatype, root);  // ncclBroadcast: ncclSum
 }
 
 NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op) {
   DeviceGuard dg(c && c->needHip);
-  return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+  return treeOrFlat(c, sendbuffs, recvbuffs, count, datatype, op);
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
@@ -1572,8 +1647,27 @@ NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* se
 NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t c, int on) {
   if (!c) return nexrInvalidArgument;
   if (c->peer || c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
-  c->flat = on != 0;
+  if (on & ~(NEXR_FLAT_RING | NEXR_FLAT_TREE | NEXR_FLAT_COPIES)) return nexrInvalidArgument;
+  c->flat = on;
   return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrTreeAllReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                            size_t count, int datatype, int op) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+}
+
+NEXR_API nexrResult_t nexrRingBroadcastFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                            size_t count, int datatype, int root) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
+}
+
+NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                            size_t sendcount, int datatype) {
+  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,

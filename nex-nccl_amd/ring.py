@@ -24,6 +24,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllReduceSymmetricLL", "nexrRingReduceScatterSymmetricLL",
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
+                    "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat",
                     "nexrTreeTopology",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
@@ -40,6 +41,7 @@ DEVICE_MEMORY = 1
 PROTO_SIMPLE = 0
 PROTO_LL = 1
 PROTO_LL128 = 2
+FLAT_RING, FLAT_TREE, FLAT_COPIES = 1, 2, 4  # NEXR_FLAT_*: nexrRingCommSetFlat's bits
 
 REDUCE_COPY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
@@ -84,6 +86,9 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingReduceScatterFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingReduceFlat.argtypes = [vp, arr, arr, sz, i32, i32, i32]
     L.nexrRingCommSetFlat.argtypes = [vp, i32]
+    L.nexrTreeAllReduceFlat.argtypes = [vp, arr, arr, sz, i32, i32]
+    L.nexrRingBroadcastFlat.argtypes = [vp, arr, arr, sz, i32, i32]
+    L.nexrRingAllGatherFlat.argtypes = [vp, arr, arr, sz, i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
@@ -313,13 +318,36 @@ class RingComm:
         _check(self._L.nexrRingReduceFlat(self._h, s, r, int(count), int(datatype), int(op), int(root)),
                "nexrRingReduceFlat")
 
-    def set_flat(self, on: bool) -> None:
-        """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat): all_reduce,
-        reduce_scatter and reduce then run as their _flat forms where the communicator is eligible (thread
-        ranks, device memory, one GPU, the library's own kernels), with the same bytes, and queued() == 4
-        after such a call; every other call runs as without it. Between collectives; InvalidUsage for
-        process-rank or host-memory communicators."""
-        _check(self._L.nexrRingCommSetFlat(self._h, 1 if on else 0), "nexrRingCommSetFlat")
+    def tree_all_reduce_flat(self, sendbuffs, recvbuffs, count: int, datatype: int, op: int) -> None:
+        """The tree's ncclAllReduce as ONE launch with the FIFO tree's own bytes (nexrTreeAllReduceFlat): every
+        rank's one step over its own input and its children's values, interpreted in registers over this
+        communicator's channel parts and every channel's own tree. Rules as all_reduce_flat."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrTreeAllReduceFlat(self._h, s, r, int(count), int(datatype), int(op)),
+               "nexrTreeAllReduceFlat")
+
+    def broadcast_flat(self, sendbuffs, recvbuffs, count: int, datatype: int, root: int) -> None:
+        """ncclBroadcast as ONE launch (nexrRingBroadcastFlat): a bit copy of sendbuffs[root] to every recvbuff
+        that is not that buffer itself; only the root's sendbuff is needed. Rules as all_reduce_flat."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingBroadcastFlat(self._h, s, r, int(count), int(datatype), int(root)),
+               "nexrRingBroadcastFlat")
+
+    def all_gather_flat(self, sendbuffs, recvbuffs, sendcount: int, datatype: int) -> None:
+        """ncclAllGather as ONE launch (nexrRingAllGatherFlat): all_gather_symmetric under the flat name, whose
+        bytes are the ring's."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllGatherFlat(self._h, s, r, int(sendcount), int(datatype)), "nexrRingAllGatherFlat")
+
+    def set_flat(self, on: bool, tree: bool = False, copies: bool = False) -> None:
+        """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat). `on` (FLAT_RING):
+        all_reduce, reduce_scatter and reduce; `tree` (FLAT_TREE): tree_all_reduce; `copies` (FLAT_COPIES):
+        all_gather and broadcast. The chosen calls then run as their _flat forms where the communicator is
+        eligible (thread ranks, device memory, one GPU, the library's own kernels), with the same bytes, and
+        queued() == 4 after such a call; every other call runs as without it. Between collectives;
+        InvalidUsage for process-rank or host-memory communicators."""
+        bits = (FLAT_RING if on else 0) | (FLAT_TREE if tree else 0) | (FLAT_COPIES if copies else 0)
+        _check(self._L.nexrRingCommSetFlat(self._h, bits), "nexrRingCommSetFlat")
 
     def send_recv(self, sendbuffs, send_peers, recvbuffs, recv_peers, nbytes: int) -> None:
         """ncclSend/ncclRecv of every rank in one group: rank r sends nbytes of sendbuffs[r] to
