@@ -971,6 +971,57 @@ NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* con
                                         nexrStream_t stream);
 
 /*
+ * nexrFlatHostAllReduce, nexrFlatHostReduceScatter, nexrFlatHostReduce, nexrFlatHostTreeAllReduce,
+ * nexrFlatHostBroadcast, nexrFlatHostAllGather — the flat collectives over HOST memory: the arguments, the
+ * per-element rules, the bytes, the aliasing rules and the argument checks (nexrInvalidArgument before any
+ * device call) of nexrFlatAllReduce, nexrFlatReduceScatter, nexrFlatReduce, nexrFlatTreeAllReduce,
+ * nexrFlatBroadcast and nexrSymAllGather, with every buffer in host memory. The call returns when the outputs
+ * are complete, as nexrReduceCopyHost does. Additions only: the ABI stays 0.3.
+ *
+ * Every distinct (address, length) among the buffers is classified once, as nexrReduceCopyHost classifies a
+ * buffer: the registration cache (nexrHostRegister, nexrHostMemAlloc) without a runtime call, else the
+ * runtime's pointer query, trusted only when the whole buffer lies inside the pinned range it reports; a
+ * buffer that begins inside a pinned range and runs past its end is staged and copied in pieces.
+ * NEXR_HOST_ZERO_COPY=0 stages everything. With every buffer pinned the call is ONE launch that reads and
+ * writes the user buffers in place over the link, its grid capped at NEXR_HOST_GRID (32) workgroups. Otherwise
+ * pageable inputs are copied into device memory before the launch and pageable outputs out of it behind the
+ * launch; pinned buffers are still accessed in place; outputs that receive the same bytes (the all-reduces,
+ * the broadcast, the all-gather) share one staged output. The ring and the tree all-reduce, the reduce and the
+ * broadcast run calls of more than NEXR_FLAT_HOST_CHUNK_BYTES (read once per process, 32 MiB, cut to a
+ * multiple of 2048) as a two-slot window pipeline: window w is copied in and launched while window w - 1 is
+ * copied out on a second stream. The reduce-scatter and the all-gather stage whole.
+ *
+ * nexrGetFlatHostStats — diagnostics (process-wide, every thread) since the last reset: calls that reached
+ * the classification; zeroCopyCalls: those with every buffer pinned; stagedBuffers: device slots that staged
+ * calls used (one per distinct pageable input, one per distinct pageable output, or one for all pageable
+ * outputs where they share); registeredHits / pointerQueries: distinct buffers classified from the
+ * registration cache / by a runtime query; windows: launches (one per window; a zero-copy call is one).
+ * reset != 0 zeroes the counters after reading them.
+ */
+typedef struct {
+  uint64_t calls, zeroCopyCalls, stagedBuffers, registeredHits, pointerQueries, windows;
+} nexrFlatHostStats;
+NEXR_API nexrResult_t nexrFlatHostAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, const nexrFlatPart* parts, int nParts,
+                                            nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatHostReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                                size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                                int userFirst, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatHostReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
+                                         int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                         nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatHostTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                                size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                                int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
+                                                const nexrFlatTreePart* parts, int nParts, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatHostBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
+                                            nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatHostAllGather(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nBytes, nexrStream_t stream);
+NEXR_API nexrResult_t nexrGetFlatHostStats(nexrFlatHostStats* stats, int reset);
+
+/*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
  * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.

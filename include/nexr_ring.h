@@ -207,7 +207,17 @@ NEXR_API nexrResult_t nexrRingAllGatherSymmetricLL(nexrRingComm_t comm, const vo
  * recvbuffs[root] only and writes nothing else. No connection and no step counter is touched and
  * nexrRingCommGetQueued stays as it was, so flat and FIFO calls may alternate freely. In place as the plain
  * calls define it. Chosen for the plain calls only under nexrRingCommSetFlat. Measured numbers: DESIGN §8.7
- * (tools/flat_probe.py). */
+ * (tools/flat_probe.py).
+ *
+ * Host memory. These entries, the three below and nexrRingCommSetFlat also take a HOST-memory communicator with
+ * thread ranks, the SIMPLE protocol (the user input is a step's first operand), at most NEXR_SYM_MAX_RANKS
+ * ranks and the library's own fn: the same parts, chunk counts, trees and op encoding go to the nexrFlatHost*
+ * form of the entry (include/nexr.h), on the first rank's device and stream; pinned (registered, allocated)
+ * user buffers are read and written in place over the link, pageable ones are staged, and the call returns
+ * with the outputs complete. A host-memory communicator with a caller's fn or with LL or LL128 is
+ * nexrInvalidUsage as before, and so is a process-rank communicator, from every one of these entries (the three
+ * entries here and nexrTreeAllReduceFlat / nexrRingBroadcastFlat used to answer nexrInvalidArgument for one,
+ * against this comment and against nexrRingCommSetFlat and nexrRingAllGatherFlat). Measured numbers: DESIGN §8.9 (tools/flat_host_probe.py). */
 NEXR_API nexrResult_t nexrRingAllReduceFlat(nexrRingComm_t comm, const void* const* sendbuffs,
                                             void* const* recvbuffs, size_t count, int datatype, int op);
 NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t comm, const void* const* sendbuffs,
@@ -239,12 +249,14 @@ NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* con
  * NEXR_FLAT_TREE (2) routes nexrTreeAllReduce; NEXR_FLAT_COPIES (4) routes nexrRingAllGather and
  * nexrRingBroadcast. nexrRingCommGetQueued reports 4 after a routed call. Eligible: thread ranks, device
  * memory, every rank on one GPU, at most NEXR_SYM_MAX_RANKS ranks and the library's own fn (SIMPLE), llFn (LL)
- * or ll128Fn (LL128): a caller's function may compute anything. On any other communicator, and for the calls
+ * or ll128Fn (LL128): a caller's function may compute anything; or thread ranks in HOST memory with SIMPLE and
+ * the library's own fn (the host forms, see nexrRingAllReduceFlat above). On any other communicator, and for the calls
  * whose bit is not set, the calls run exactly as without the option. The results are the same bytes either way,
  * and the option may be changed between collectives and combined with the group options (a routed call ignores
  * them). With 0 nothing changes; with 1 exactly the three ring reductions are routed.
  *
- * nexrInvalidArgument for any other bit; nexrInvalidUsage for process-rank or host-memory communicators. */
+ * nexrInvalidArgument for any other bit; nexrInvalidUsage for process-rank communicators and for host-memory
+ * communicators with a caller's fn, LL or LL128. */
 #define NEXR_FLAT_RING 1
 #define NEXR_FLAT_TREE 2
 #define NEXR_FLAT_COPIES 4

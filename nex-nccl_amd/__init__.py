@@ -93,6 +93,8 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrSymLLReduceScatter", "nexrSymLLAllGather",
                "nexrFlatAllReduce", "nexrFlatReduceScatter", "nexrFlatReduce",
                "nexrFlatTreeAllReduce", "nexrFlatBroadcast",
+               "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
+               "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -143,6 +145,12 @@ class HostPathStats(ctypes.Structure):
     """Mirror of nexrHostPathStats (include/nexr.h): nexrGetHostPathStats' counters."""
     _fields_ = [(f, ctypes.c_uint64) for f in ("calls", "zeroCopyCalls", "registeredHits", "pointerQueries",
                                                "classifyNs", "copyNs", "launchNs", "waitNs")]
+
+
+class FlatHostStats(ctypes.Structure):
+    """Mirror of nexrFlatHostStats (include/nexr.h): nexrGetFlatHostStats' counters."""
+    _fields_ = [(f, ctypes.c_uint64) for f in ("calls", "zeroCopyCalls", "stagedBuffers", "registeredHits",
+                                               "pointerQueries", "windows")]
 
 
 MAX_BATCH_WORKS = 14  # NEXR_MAX_BATCH_WORKS
@@ -354,6 +362,15 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatTreeAllReduce.restype = i32
     L.nexrFlatBroadcast.argtypes = [i32, vp, P(vp), sz, vp]
     L.nexrFlatBroadcast.restype = i32
+    for host, dev in (("nexrFlatHostAllReduce", L.nexrFlatAllReduce),
+                      ("nexrFlatHostReduceScatter", L.nexrFlatReduceScatter), ("nexrFlatHostReduce", L.nexrFlatReduce),
+                      ("nexrFlatHostTreeAllReduce", L.nexrFlatTreeAllReduce),
+                      ("nexrFlatHostBroadcast", L.nexrFlatBroadcast), ("nexrFlatHostAllGather", L.nexrSymAllGather)):
+        f = getattr(L, host)   # the device entry's argument list
+        f.argtypes = dev.argtypes
+        f.restype = i32
+    L.nexrGetFlatHostStats.argtypes = [P(FlatHostStats), i32]
+    L.nexrGetFlatHostStats.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
     L.nexrSymLLWindowBytes.restype = i32
     L.nexrSymLLAllReduce.argtypes = [i32, P(vp), P(vp), sz, i32, i32, u64, P(vp), sz, i32, vp, ctypes.c_uint32, vp]
@@ -958,6 +975,86 @@ def flat_broadcast(input: int, outputs: Sequence[int], n_bytes: int, stream: int
     rc = lib().nexrFlatBroadcast(len(outputs), ctypes.c_void_p(int(input)) if input else None, _ptr_array(outputs),
                                  int(n_bytes), ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatBroadcast")
+
+
+# ---- the flat collectives over host memory (nexrFlatHost*): the device forms' arguments, host addresses -------------
+def _stream_arg(stream: int):
+    return ctypes.c_void_p(int(stream)) if stream else None
+
+
+def flat_host_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int, dev_red_op: int,
+                         red_op_arg: int, user_first: bool, parts: Sequence[tuple], stream: int = 0) -> None:
+    """``flat_all_reduce`` over HOST buffers (``nexrFlatHostAllReduce``): pinned buffers are read and written in
+    place over the link in one launch, pageable ones are staged (a window pipeline beyond
+    NEXR_FLAT_HOST_CHUNK_BYTES). Returns when the outputs are complete."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    arr = (FlatPart * max(1, len(parts)))(*[FlatPart(int(o), int(c), int(k)) for o, c, k in parts])
+    rc = lib().nexrFlatHostAllReduce(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts), int(datatype),
+                                     int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0,
+                                     arr, len(parts), _stream_arg(stream))
+    _check(rc, "nexrFlatHostAllReduce")
+
+
+def flat_host_reduce_scatter(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                             dev_red_op: int, red_op_arg: int, user_first: bool, stream: int = 0) -> None:
+    """``flat_reduce_scatter`` over HOST buffers (``nexrFlatHostReduceScatter``); pageable buffers are staged
+    whole. Returns when the outputs are complete."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatHostReduceScatter(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts),
+                                         int(datatype), int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                         1 if user_first else 0, _stream_arg(stream))
+    _check(rc, "nexrFlatHostReduceScatter")
+
+
+def flat_host_reduce(inputs: Sequence[int], output: int, root: int, n_elts: int, datatype: int, dev_red_op: int,
+                     red_op_arg: int, user_first: bool, stream: int = 0) -> None:
+    """``flat_reduce`` over HOST buffers (``nexrFlatHostReduce``). Returns when the output is complete."""
+    rc = lib().nexrFlatHostReduce(len(inputs), _ptr_array(inputs), ctypes.c_void_p(int(output)) if output else None,
+                                  int(root), int(n_elts), int(datatype), int(dev_red_op),
+                                  int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0, _stream_arg(stream))
+    _check(rc, "nexrFlatHostReduce")
+
+
+def flat_host_tree_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                              dev_red_op: int, red_op_arg: int, user_first: bool, trees: Sequence[Sequence[tuple]],
+                              parts: Sequence[tuple], stream: int = 0) -> None:
+    """``flat_tree_all_reduce`` over HOST buffers (``nexrFlatHostTreeAllReduce``). Returns when the outputs are
+    complete."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    tarr, _keep = flat_tree_links(trees)
+    arr = (FlatTreePart * max(1, len(parts)))(*[FlatTreePart(int(o), int(c), int(t), 0) for o, c, t in parts])
+    rc = lib().nexrFlatHostTreeAllReduce(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts),
+                                         int(datatype), int(dev_red_op), int(red_op_arg) & 0xFFFFFFFFFFFFFFFF,
+                                         1 if user_first else 0, tarr, len(trees), arr, len(parts), _stream_arg(stream))
+    _check(rc, "nexrFlatHostTreeAllReduce")
+
+
+def flat_host_broadcast(input: int, outputs: Sequence[int], n_bytes: int, stream: int = 0) -> None:
+    """``flat_broadcast`` over HOST buffers (``nexrFlatHostBroadcast``). Returns when the outputs are complete."""
+    rc = lib().nexrFlatHostBroadcast(len(outputs), ctypes.c_void_p(int(input)) if input else None,
+                                     _ptr_array(outputs), int(n_bytes), _stream_arg(stream))
+    _check(rc, "nexrFlatHostBroadcast")
+
+
+def flat_host_all_gather(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int, stream: int = 0) -> None:
+    """``sym_all_gather``'s bytes over HOST buffers (``nexrFlatHostAllGather``): outputs[s][r * n_bytes + b] =
+    inputs[r][b]; pageable buffers are staged whole. Returns when the outputs are complete."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatHostAllGather(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
+                                     _stream_arg(stream))
+    _check(rc, "nexrFlatHostAllGather")
+
+
+def flat_host_stats(reset: bool = False) -> dict:
+    """nexrGetFlatHostStats: how the nexrFlatHost* calls since the last reset classified and staged their buffers
+    (process-wide)."""
+    st = FlatHostStats()
+    _check(lib().nexrGetFlatHostStats(ctypes.byref(st), 1 if reset else 0), "nexrGetFlatHostStats")
+    return {f: int(getattr(st, f)) for f, _ in FlatHostStats._fields_}
 
 
 SYM_LL_HEADER_BYTES = 256  # NEXR_SYM_LL_HEADER_BYTES

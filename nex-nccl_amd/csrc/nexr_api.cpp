@@ -11,6 +11,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
@@ -2315,17 +2316,21 @@ nexrResult_t flatPrepare(int nRanks, const void* const* inputs, int datatype, in
 
 // One-shot: a wave per 2048-byte piece of every region, four waves per workgroup; beyond the cap the kernel
 // strides.
-unsigned flatGrid(uint64_t regionBytes, int nRegions) {
+unsigned flatGrid(uint64_t regionBytes, int nRegions, uint64_t maxGrid = 0) {
   const uint64_t items = (regionBytes + 2047) / 2048 * (uint64_t)nRegions;
-  return (unsigned)std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+  const uint64_t grid = std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+  return (unsigned)(maxGrid > 0 && grid > maxGrid ? maxGrid : grid);  // maxGrid: the host forms' cap (hostGrid)
 }
 }  // namespace
 
-NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
-                                        int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
-                                        const nexrFlatPart* parts, int nParts, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
+// The checks of nexrFlatAllReduce, and the launch's parameters over the pointers as given (no device call).
+namespace {
+nexrResult_t flatAllReduceCheck(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                const nexrFlatPart* parts, int nParts, FlatParams* pp, int* dtp, int* opp) {
+  FlatParams& p = *pp;
+  int& dt = *dtp;
+  int& op = *opp;
   if (!outputs) return nexrInvalidArgument;
   nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
   if (res != nexrSuccess) return res;
@@ -2345,11 +2350,16 @@ NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, v
     at += q.count;
   }
   if (at != (uint64_t)nElts) return nexrInvalidArgument;
-  if (nElts == 0) return nexrSuccess;
   p.coll = kFlatAllReduce;
-  p.regionBytes = (uint64_t)nElts * esz;
+  p.regionBytes = p.winEnd = (uint64_t)nElts * esz;
   p.nParts = nParts;
-  hipStream_t s = (hipStream_t)stream;
+  p.nOut = nRanks;
+  return nexrSuccess;
+}
+
+// One launch of a checked all-reduce over the window that p holds; gridCap > 0 caps the grid.
+nexrResult_t flatAllReduceLaunch(FlatParams& p, int dt, int op, const nexrFlatPart* parts, int nParts,
+                                 uint64_t gridCapWgs, hipStream_t s) {
   nexrFlatPart* ws = nullptr;
   if (nParts <= kFlatInlineParts) {
     memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatPart));
@@ -2369,17 +2379,31 @@ NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, v
     }
     p.ext = ws;
   }
-  const hipError_t e = launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), s);
+  const hipError_t e = launch_flat(dt, op, p, flatGrid(p.winEnd - p.winBeg, 1, gridCapWgs), s);
   if (ws) (void)hipFreeAsync(ws, s);
   NEXR_HIP(e);
   return nexrSuccess;
 }
+}  // namespace
 
-NEXR_API nexrResult_t nexrFlatReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
-                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                            int userFirst, nexrStream_t stream) {
+NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                        int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                        const nexrFlatPart* parts, int nParts, nexrStream_t stream) {
   FlatParams p;
   int dt, op;
+  const nexrResult_t res = flatAllReduceCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
+                                              parts, nParts, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
+  return flatAllReduceLaunch(p, dt, op, parts, nParts, 0, (hipStream_t)stream);
+}
+
+namespace {
+nexrResult_t flatReduceScatterCheck(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
+                                    int datatype, int devRedOp, uint64_t redOpArg, int userFirst, FlatParams* pp,
+                                    int* dtp, int* opp) {
+  FlatParams& p = *pp;
+  int& dt = *dtp;
+  int& op = *opp;
   if (!outputs) return nexrInvalidArgument;
   nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
   if (res != nexrSuccess) return res;
@@ -2389,29 +2413,53 @@ NEXR_API nexrResult_t nexrFlatReduceScatter(int nRanks, const void* const* input
     p.out[r] = (char*)outputs[r];
   }
   if (nElts > (size_t)-1 / esz / (size_t)nRanks) return nexrInvalidArgument;  // an input's nRanks * nElts * esz bytes
-  if (nElts == 0) return nexrSuccess;
   p.coll = kFlatReduceScatter;
-  p.regionBytes = (uint64_t)nElts * esz;
+  p.regionBytes = p.winEnd = (uint64_t)nElts * esz;
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  const nexrResult_t res =
+      flatReduceScatterCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
   NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks), (hipStream_t)stream));
   return nexrSuccess;
 }
 
-NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
-                                     int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
-                                     nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
+namespace {
+nexrResult_t flatReduceCheck(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
+                             int datatype, int devRedOp, uint64_t redOpArg, int userFirst, FlatParams* pp, int* dtp,
+                             int* opp) {
+  FlatParams& p = *pp;
+  int& dt = *dtp;
+  int& op = *opp;
   if (!output) return nexrInvalidArgument;
   nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
   if (res != nexrSuccess) return res;
   const uint64_t esz = typeSize(datatype);
   if (root < 0 || root >= nRanks || ((uintptr_t)output & (esz - 1))) return nexrInvalidArgument;
   if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
-  if (nElts == 0) return nexrSuccess;
   p.out[root] = (char*)output;
   p.root = root;
   p.coll = kFlatReduce;
-  p.regionBytes = (uint64_t)nElts * esz;
+  p.regionBytes = p.winEnd = (uint64_t)nElts * esz;
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
+                                     int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                     nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  const nexrResult_t res =
+      flatReduceCheck(nRanks, inputs, output, root, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
   NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), (hipStream_t)stream));
   return nexrSuccess;
 }
@@ -2489,17 +2537,19 @@ bool flatTreeCompile(const nexrFlatTreeLinks* links, int n, std::vector<uint8_t>
 }
 }  // namespace
 
-NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
-                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                            int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
-                                            const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
+namespace {
+nexrResult_t flatTreeCheck(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts, int datatype,
+                           int devRedOp, uint64_t redOpArg, int userFirst, const nexrFlatTreeLinks* const* trees,
+                           int nTrees, const nexrFlatTreePart* parts, int nParts, FlatTreeParams* pp, int* dtp,
+                           int* opp) {
+  FlatTreeParams& p = *pp;
+  int& dt = *dtp;
+  int& op = *opp;
   FlatParams fp;  // the shared checks and what the semantics make of the call
-  int dt, op;
   if (!outputs) return nexrInvalidArgument;
   nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &fp, &dt, &op);
   if (res != nexrSuccess) return res;
   const uint64_t esz = typeSize(datatype), epp = 16 / esz;
-  FlatTreeParams p;
   memset((void*)&p, 0, sizeof(p));
   for (int r = 0; r < nRanks; r++) {
     if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
@@ -2543,15 +2593,19 @@ NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* input
     at += q.count;
   }
   if (at != (uint64_t)nElts) return nexrInvalidArgument;
-  if (nElts == 0) return nexrSuccess;
-  p.nBytes = (uint64_t)nElts * esz;
+  p.nBytes = p.winEnd = (uint64_t)nElts * esz;
   p.redArg = fp.redArg;
-  p.nRanks = nRanks;
+  p.nRanks = p.nOut = nRanks;
   p.userFirst = fp.userFirst;
   p.preOp = fp.preOp;
   p.postOp = fp.postOp;
   p.nParts = nParts;
-  hipStream_t s = (hipStream_t)stream;
+  return nexrSuccess;
+}
+
+// One launch of a checked tree all-reduce over the window that p holds; gridCapWgs > 0 caps the grid.
+nexrResult_t flatTreeLaunch(FlatTreeParams& p, int dt, int op, const nexrFlatTreePart* parts, int nParts,
+                            uint64_t gridCapWgs, hipStream_t s) {
   nexrFlatTreePart* ws = nullptr;
   if (nParts <= kFlatTreeInlineParts) {
     memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatTreePart));
@@ -2571,10 +2625,23 @@ NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* input
     }
     p.ext = ws;
   }
-  const hipError_t e = launch_flat_tree(dt, op, p, flatGrid(p.nBytes, 1), s);
+  const hipError_t e = launch_flat_tree(dt, op, p, flatGrid(p.winEnd - p.winBeg, 1, gridCapWgs), s);
   if (ws) (void)hipFreeAsync(ws, s);
   NEXR_HIP(e);
   return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
+                                            const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
+  FlatTreeParams p;
+  int dt, op;
+  const nexrResult_t res = flatTreeCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
+                                         trees, nTrees, parts, nParts, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
+  return flatTreeLaunch(p, dt, op, parts, nParts, 0, (hipStream_t)stream);
 }
 
 NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
@@ -2593,9 +2660,407 @@ NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* con
   }
   if (nBytes == 0 || !any) return nexrSuccess;
   p.in = (const char*)input;
-  p.nBytes = nBytes;
+  p.nBytes = p.winEnd = nBytes;
   p.nRanks = nRanks;
   NEXR_HIP(launch_flat_bcast(p, flatGrid(nBytes, 1), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+// ---- nexrFlatHost*: the flat entries over host memory -------------------------------------------------------
+// The device entries' checks, then one helper for all six (flatHostRun). Every DISTINCT (address, length) among
+// the call's buffers is classified once, as nexrReduceCopyHost classifies a buffer: the registration cache
+// (regLookup, no HIP call), else the runtime's pointer query, trusted only when the whole buffer lies inside
+// the pinned range it reports; a buffer that begins inside such a range and runs past its end is `cut`: never
+// read in place, and copied only in pieces (hostCopyPieces). NEXR_HOST_ZERO_COPY=0 stages everything.
+//   - Every buffer pinned: one launch over the device-mapped addresses, the grid capped at hostGrid().
+//   - Otherwise a pageable input is copied into a device slot before the launch and a pageable output out of one
+//     behind it; pinned buffers are still read and written in place. A host address always maps to the same
+//     device address (pinned) or, as an input, to the same slot, so an input that appears twice is copied once.
+//     Outputs that receive the same bytes (the all-reduces, the broadcast, the all-gather) share ONE staged
+//     output, copied out once per distinct pageable output address. Every copy-in of a launch's bytes precedes
+//     the launch and every copy-out follows it, and a lane stores a position only after it has read it from every
+//     input, so the device entries' aliasing rules hold for host addresses as they stand.
+//   - Calls whose inputs and outputs are one region (ring and tree all-reduce, reduce, broadcast) and that hold
+//     more than one chunk (NEXR_FLAT_HOST_CHUNK_BYTES, 32 MiB, cut to a multiple of the 2048-byte piece) run as
+//     a two-slot window pipeline on a pooled staging ring (stageFor): window w is copied in and launched on the
+//     caller's stream while window w - 1 is copied out on the ring's stream. A staged window holds only its own
+//     bytes, so its pointer is biased by -winBeg. The reduce-scatter and the all-gather stage whole: their
+//     chunks are strided through the inputs and the outputs.
+namespace {
+std::atomic<uint64_t> gFhCalls{0}, gFhZeroCopy{0}, gFhStaged{0}, gFhRegHits{0}, gFhQueries{0}, gFhWindows{0};
+
+struct FlatHostIo {
+  int nIn = 0, nOut = 0;
+  const void* in[NEXR_SYM_MAX_RANKS];  // host inputs, slot by slot
+  void* out[NEXR_SYM_MAX_RANKS];       // host outputs, slot by slot; null: the slot has none
+  size_t inBytes = 0, outBytes = 0;
+  bool sharedOut = false;  // every output receives the same bytes: one staged output serves the pageable ones
+  bool compact = false;    // the launch takes the distinct device outputs as a list, not slot by slot
+  bool windowed = false;   // inputs and outputs are one region and the launch takes a byte window of it
+};
+// (device inputs by slot, device outputs by slot or as the compact list, their number, winBeg, winEnd, the
+// grid's cap or 0, stream)
+using FlatHostLaunch = std::function<nexrResult_t(const char* const*, char* const*, int, uint64_t, uint64_t,
+                                                  uint64_t, hipStream_t)>;
+
+struct FlatHostBuf {
+  uintptr_t host;
+  size_t bytes;
+  bool pin, cut;
+  char* dev;    // pinned: the device address of the buffer
+  int stageIn;  // pageable, used as an input: its slot among the staged inputs, else -1
+  int stageOut; // pageable, used as an output: its slot among the staged outputs, else -1
+};
+
+// 32 MiB: with pageable buffers fewer windows were faster at every point measured (a 64 MiB all-reduce at 2 ranks:
+// 6.18 ms in 4 MiB windows, 5.61 in 8, 5.21 in 16, 5.05 in 32, 5.02 whole; profiles/r19e_flat_host_chunk_sweep_64mib.json),
+// so the chunk is what bounds the staging ring's memory, set where the loss to staging whole is 0.5 %.
+size_t flatHostChunk() {
+  static const long v = envLong("NEXR_FLAT_HOST_CHUNK_BYTES", 32l << 20);
+  const size_t c = (size_t)(v > 2048 ? v : 2048);
+  return c / 2048 * 2048;
+}
+
+int flatHostClassify(std::vector<FlatHostBuf>& bufs, const void* hp, size_t bytes, bool zeroCopy) {
+  for (size_t i = 0; i < bufs.size(); i++)
+    if (bufs[i].host == (uintptr_t)hp && bufs[i].bytes == bytes) return (int)i;
+  FlatHostBuf b{(uintptr_t)hp, bytes, false, false, nullptr, -1, -1};
+  void* dev = nullptr;
+  if (!zeroCopy) {
+    b.cut = true;  // what the runtime knows of the range is not asked: every copy goes in pieces
+  } else if (regLookup(hp, bytes, &dev)) {
+    b.pin = true;
+    gFhRegHits.fetch_add(1, std::memory_order_relaxed);
+  } else {
+    gFhQueries.fetch_add(1, std::memory_order_relaxed);
+    hipPointerAttribute_t a;
+    b.pin = hipPointerGetAttributes(&a, hp) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer != nullptr;
+    if (b.pin) {
+      dev = a.devicePointer;
+      uintptr_t beg = 0;
+      size_t size = 0;
+      if (hipPointerGetAttribute(&beg, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, (hipDeviceptr_t)hp) != hipSuccess ||
+          hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, (hipDeviceptr_t)hp) != hipSuccess ||
+          (uintptr_t)hp < beg || (uintptr_t)hp + bytes > beg + size) {
+        b.pin = false;  // the device mapping ends before the buffer does
+        b.cut = true;
+      }
+    }
+    (void)hipGetLastError();  // pageable memory reports an error: not a failure of this call
+  }
+  b.dev = b.pin ? (char*)dev : nullptr;
+  bufs.push_back(b);
+  return (int)bufs.size() - 1;
+}
+
+nexrResult_t flatHostRun(const FlatHostIo& io, hipStream_t s, const FlatHostLaunch& launch) {
+  static const long zeroCopy = envLong("NEXR_HOST_ZERO_COPY", 1);
+  gFhCalls.fetch_add(1, std::memory_order_relaxed);
+  std::vector<FlatHostBuf> bufs;
+  int inIx[NEXR_SYM_MAX_RANKS], outIx[NEXR_SYM_MAX_RANKS];
+  int nStageIn = 0, nStageOut = 0, nPinned = 0;
+  for (int r = 0; r < io.nIn; r++) {
+    inIx[r] = flatHostClassify(bufs, io.in[r], io.inBytes, zeroCopy != 0);
+    FlatHostBuf& b = bufs[inIx[r]];
+    if (!b.pin && b.stageIn < 0) b.stageIn = nStageIn++;
+  }
+  for (int r = 0; r < io.nOut; r++) {
+    outIx[r] = -1;
+    if (!io.out[r]) continue;
+    outIx[r] = flatHostClassify(bufs, io.out[r], io.outBytes, zeroCopy != 0);
+    FlatHostBuf& b = bufs[outIx[r]];
+    if (!b.pin && b.stageOut < 0) b.stageOut = io.sharedOut ? 0 : nStageOut++;
+    if (!b.pin && io.sharedOut) nStageOut = 1;
+  }
+  for (const FlatHostBuf& b : bufs) nPinned += b.pin ? 1 : 0;
+  const char* devIn[NEXR_SYM_MAX_RANKS];
+  char* devOut[NEXR_SYM_MAX_RANKS];
+  if (nStageIn + nStageOut == 0) {  // zero-copy: the kernel reads and writes the user buffers over the link
+    gFhZeroCopy.fetch_add(1, std::memory_order_relaxed);
+    gFhWindows.fetch_add(1, std::memory_order_relaxed);
+    for (int r = 0; r < io.nIn; r++) devIn[r] = bufs[inIx[r]].dev;
+    int m = 0;
+    for (int r = 0; r < io.nOut; r++) {
+      char* d = outIx[r] < 0 ? nullptr : bufs[outIx[r]].dev;
+      if (!io.compact) {
+        devOut[m++] = d;
+      } else if (d && std::find(devOut, devOut + m, d) == devOut + m) {
+        devOut[m++] = d;
+      }
+    }
+    const nexrResult_t res = launch(devIn, devOut, m, 0, io.windowed ? io.inBytes : 0, hostGrid(), s);
+    if (res != nexrSuccess) return res;
+    NEXR_HIP(hipStreamSynchronize(s));
+    return nexrSuccess;
+  }
+  gFhStaged.fetch_add((uint64_t)(nStageIn + nStageOut), std::memory_order_relaxed);
+  const size_t region = io.inBytes;
+  const size_t chunk = io.windowed ? std::min(flatHostChunk(), (region + 2047) / 2048 * 2048) : 0;
+  const size_t inStride = ((io.windowed ? chunk : io.inBytes) + 255) & ~(size_t)255;
+  const size_t outStride = ((io.windowed ? chunk : io.outBytes) + 255) & ~(size_t)255;
+  const size_t nWindows = io.windowed ? (region + chunk - 1) / chunk : 1;
+  // A ring is two slots. A call of one window (every reduce-scatter and all-gather among them) uses the ring's
+  // memory as ONE slot, so it asks for half its bytes a slot.
+  const size_t slotNeed = inStride * (size_t)nStageIn + outStride * (size_t)nStageOut;
+  StageLease lease;
+  nexrResult_t res = stageFor(nWindows > 1 ? slotNeed : (slotNeed + 1) / 2, s, &lease);
+  if (res != nexrSuccess) return res;
+  HostStage* st = lease.st;
+  gFhWindows.fetch_add(nWindows, std::memory_order_relaxed);
+  for (size_t w = 0; w < nWindows; w++) {
+    const int slot = (int)(w & 1);
+    const uint64_t wb = io.windowed ? (uint64_t)w * chunk : 0;
+    const uint64_t we = io.windowed ? std::min<uint64_t>(wb + chunk, region) : 0;
+    const size_t inLen = io.windowed ? (size_t)(we - wb) : io.inBytes;
+    const size_t outLen = io.windowed ? (size_t)(we - wb) : io.outBytes;
+    char* inBase = st->buf + (nWindows > 1 ? (size_t)slot * st->slotBytes : 0);
+    char* outBase = inBase + inStride * (size_t)nStageIn;
+    if (w >= 2) NEXR_HIP(hipStreamWaitEvent(s, st->outDone[slot], 0));  // slot drained by window w - 2's copies out
+    for (const FlatHostBuf& b : bufs) {
+      if (b.stageIn < 0) continue;
+      char* d = inBase + inStride * (size_t)b.stageIn;
+      if (b.cut)
+        NEXR_HIP(hostCopyPieces(d, (char*)b.host + wb, inLen, true, s));
+      else
+        NEXR_HIP(hipMemcpyAsync(d, (const char*)b.host + wb, inLen, hipMemcpyHostToDevice, s));
+    }
+    // a staged window holds only its own bytes: the kernel addresses `pointer + region offset`
+    for (int r = 0; r < io.nIn; r++) {
+      const FlatHostBuf& b = bufs[inIx[r]];
+      devIn[r] = b.pin ? b.dev : inBase + inStride * (size_t)b.stageIn - wb;
+    }
+    int m = 0;
+    for (int r = 0; r < io.nOut; r++) {
+      char* d = nullptr;
+      if (outIx[r] >= 0) {
+        const FlatHostBuf& b = bufs[outIx[r]];
+        d = b.pin ? b.dev : outBase + outStride * (size_t)b.stageOut - wb;
+      }
+      if (!io.compact) {
+        devOut[m++] = d;
+      } else if (d && std::find(devOut, devOut + m, d) == devOut + m) {
+        devOut[m++] = d;
+      }
+    }
+    res = launch(devIn, devOut, m, wb, we, nPinned > 0 ? hostGrid() : 0, s);
+    if (res != nexrSuccess) return res;
+    if (nStageOut == 0) continue;
+    NEXR_HIP(hipEventRecord(st->kernelDone[slot], s));
+    NEXR_HIP(hipStreamWaitEvent(st->out, st->kernelDone[slot], 0));
+    for (const FlatHostBuf& b : bufs) {
+      if (b.stageOut < 0) continue;
+      char* d = outBase + outStride * (size_t)b.stageOut;
+      if (b.cut)
+        NEXR_HIP(hostCopyPieces(d, (char*)b.host + wb, outLen, false, st->out));
+      else
+        NEXR_HIP(hipMemcpyAsync((char*)b.host + wb, d, outLen, hipMemcpyDeviceToHost, st->out));
+    }
+    NEXR_HIP(hipEventRecord(st->outDone[slot], st->out));
+  }
+  NEXR_HIP(hipStreamSynchronize(st->out));
+  NEXR_HIP(hipStreamSynchronize(s));
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatHostAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                            int userFirst, const nexrFlatPart* parts, int nParts,
+                                            nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  const nexrResult_t res = flatAllReduceCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
+                                              parts, nParts, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
+  FlatHostIo io;
+  io.nIn = io.nOut = nRanks;
+  for (int r = 0; r < nRanks; r++) {
+    io.in[r] = inputs[r];
+    io.out[r] = outputs[r];
+  }
+  io.inBytes = io.outBytes = (size_t)p.regionBytes;
+  io.sharedOut = io.compact = io.windowed = true;
+  return flatHostRun(io, (hipStream_t)stream,
+                     [&](const char* const* in, char* const* out, int nOut, uint64_t wb, uint64_t we, uint64_t cap,
+                         hipStream_t s) {
+                       for (int r = 0; r < nRanks; r++) {
+                         p.in[r] = in[r];
+                         p.out[r] = r < nOut ? out[r] : nullptr;
+                       }
+                       p.nOut = nOut;
+                       p.winBeg = wb;
+                       p.winEnd = we;
+                       return flatAllReduceLaunch(p, dt, op, parts, nParts, cap, s);
+                     });
+}
+
+NEXR_API nexrResult_t nexrFlatHostReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
+                                                size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                                int userFirst, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  const nexrResult_t res =
+      flatReduceScatterCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
+  FlatHostIo io;
+  io.nIn = io.nOut = nRanks;
+  for (int r = 0; r < nRanks; r++) {
+    io.in[r] = inputs[r];
+    io.out[r] = outputs[r];
+  }
+  io.outBytes = (size_t)p.regionBytes;
+  io.inBytes = io.outBytes * (size_t)nRanks;
+  return flatHostRun(io, (hipStream_t)stream,
+                     [&](const char* const* in, char* const* out, int, uint64_t, uint64_t, uint64_t cap,
+                         hipStream_t s) {
+                       for (int r = 0; r < nRanks; r++) {
+                         p.in[r] = in[r];
+                         p.out[r] = out[r];
+                       }
+                       NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks, cap), s));
+                       return nexrSuccess;
+                     });
+}
+
+NEXR_API nexrResult_t nexrFlatHostReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
+                                         int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
+                                         nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  const nexrResult_t res =
+      flatReduceCheck(nRanks, inputs, output, root, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
+  FlatHostIo io;
+  io.nIn = nRanks;
+  io.nOut = 1;
+  for (int r = 0; r < nRanks; r++) io.in[r] = inputs[r];
+  io.out[0] = output;
+  io.inBytes = io.outBytes = (size_t)p.regionBytes;
+  io.windowed = true;
+  return flatHostRun(io, (hipStream_t)stream,
+                     [&](const char* const* in, char* const* out, int, uint64_t wb, uint64_t we, uint64_t cap,
+                         hipStream_t s) {
+                       for (int r = 0; r < nRanks; r++) p.in[r] = in[r];
+                       p.out[root] = out[0];
+                       p.winBeg = wb;
+                       p.winEnd = we;
+                       NEXR_HIP(launch_flat(dt, op, p, flatGrid(we - wb, 1, cap), s));
+                       return nexrSuccess;
+                     });
+}
+
+NEXR_API nexrResult_t nexrFlatHostTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
+                                                size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
+                                                int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
+                                                const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
+  FlatTreeParams p;
+  int dt, op;
+  const nexrResult_t res = flatTreeCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
+                                         trees, nTrees, parts, nParts, &p, &dt, &op);
+  if (res != nexrSuccess || nElts == 0) return res;
+  FlatHostIo io;
+  io.nIn = io.nOut = nRanks;
+  for (int r = 0; r < nRanks; r++) {
+    io.in[r] = inputs[r];
+    io.out[r] = outputs[r];
+  }
+  io.inBytes = io.outBytes = (size_t)p.nBytes;
+  io.sharedOut = io.compact = io.windowed = true;
+  return flatHostRun(io, (hipStream_t)stream,
+                     [&](const char* const* in, char* const* out, int nOut, uint64_t wb, uint64_t we, uint64_t cap,
+                         hipStream_t s) {
+                       for (int r = 0; r < nRanks; r++) {
+                         p.in[r] = in[r];
+                         p.out[r] = r < nOut ? out[r] : nullptr;
+                       }
+                       p.nOut = nOut;
+                       p.winBeg = wb;
+                       p.winEnd = we;
+                       return flatTreeLaunch(p, dt, op, parts, nParts, cap, s);
+                     });
+}
+
+NEXR_API nexrResult_t nexrFlatHostBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
+                                            nexrStream_t stream) {
+  if (!input || !outputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  FlatHostIo io;
+  bool any = false;
+  for (int r = 0; r < nRanks; r++) {
+    if (!outputs[r]) return nexrInvalidArgument;
+    io.out[r] = outputs[r] != input ? outputs[r] : nullptr;
+    any = any || io.out[r];
+  }
+  if (nBytes == 0 || !any) return nexrSuccess;
+  io.nIn = 1;
+  io.nOut = nRanks;
+  io.in[0] = input;
+  io.inBytes = io.outBytes = nBytes;
+  io.sharedOut = io.compact = io.windowed = true;
+  return flatHostRun(io, (hipStream_t)stream,
+                     [&](const char* const* in, char* const* out, int nOut, uint64_t wb, uint64_t we, uint64_t cap,
+                         hipStream_t s) {
+                       FlatBcastParams p;
+                       memset((void*)&p, 0, sizeof(p));
+                       for (int r = 0; r < nOut; r++) p.out[r] = out[r];
+                       p.in = in[0];
+                       p.nBytes = nBytes;
+                       p.winBeg = wb;
+                       p.winEnd = we;
+                       p.nRanks = nOut;
+                       NEXR_HIP(launch_flat_bcast(p, flatGrid(we - wb, 1, cap), s));
+                       return nexrSuccess;
+                     });
+}
+
+NEXR_API nexrResult_t nexrFlatHostAllGather(int nRanks, const void* const* inputs, void* const* outputs,
+                                            size_t nBytes, nexrStream_t stream) {
+  if (!inputs || !outputs) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (nBytes > (size_t)-1 / (size_t)nRanks) return nexrInvalidArgument;  // an output's nRanks * nBytes bytes
+  FlatHostIo io;
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
+    io.in[r] = inputs[r];
+    io.out[r] = outputs[r];
+  }
+  if (nBytes == 0) return nexrSuccess;
+  io.nIn = io.nOut = nRanks;
+  io.inBytes = nBytes;
+  io.outBytes = nBytes * (size_t)nRanks;
+  io.sharedOut = true;
+  return flatHostRun(io, (hipStream_t)stream,
+                     [&](const char* const* in, char* const* out, int, uint64_t, uint64_t, uint64_t cap,
+                         hipStream_t s) {
+                       SymAgParams p;
+                       memset(&p, 0, sizeof(p));
+                       for (int r = 0; r < nRanks; r++) {
+                         p.in[r] = in[r];
+                         p.out[r] = out[r];
+                         // Pageable outputs all name the one staged output, which the kernel therefore
+                         // stores once per pageable rank (the same bytes, in device memory: up to n times
+                         // the device writes, none over the link). The reference's inPlace, per rank: a
+                         // staged buffer never lies inside another
+                         if ((uintptr_t)in[r] == (uintptr_t)out[r] + (uintptr_t)r * nBytes) p.inPlace |= 1ull << r;
+                       }
+                       p.nBytes = nBytes;
+                       p.nRanks = nRanks;
+                       unsigned grid = symChunkGrid(nBytes, 1, nRanks);
+                       if (cap > 0 && grid > cap) grid = (unsigned)cap;
+                       NEXR_HIP(launch_sym_all_gather(p, grid, s));
+                       return nexrSuccess;
+                     });
+}
+
+NEXR_API nexrResult_t nexrGetFlatHostStats(nexrFlatHostStats* stats, int reset) {
+  if (stats == nullptr) return nexrInvalidArgument;
+  auto take = [&](std::atomic<uint64_t>& a) { return reset ? a.exchange(0) : a.load(); };
+  stats->calls = take(gFhCalls);
+  stats->zeroCopyCalls = take(gFhZeroCopy);
+  stats->stagedBuffers = take(gFhStaged);
+  stats->registeredHits = take(gFhRegHits);
+  stats->pointerQueries = take(gFhQueries);
+  stats->windows = take(gFhWindows);
   return nexrSuccess;
 }
 

@@ -26,6 +26,14 @@
 // phase differs by rank), so every pack access is the unaligned-capable form; the region's last bytes below a
 // pack go one element per lane. Offsets are 64-bit. No LDS, no cross-lane traffic, plain cache policy. A lane
 // reads its bytes from every input before it stores them, so an output may be an input.
+//
+// The window. A launch covers the bytes [winBeg, winEnd) of every region (winBeg a multiple of the piece; 0 and
+// regionBytes: the whole region, the device entries' launch). Only the enumeration of the pieces knows it: a
+// piece keeps its number from the region's byte 0, so a position, its chunk, its start rank and the sub-pack tail
+// at the region's end are what they are in a whole launch, and `pointer + region offset` addresses every buffer
+// (the host entries pass a staged window's buffer biased by -winBeg, nexr_api.cpp). The all-reduce stores the
+// first nOut entries of out[] (n, or fewer where outputs share a staged buffer). Both are wave-uniform kernel
+// arguments: no instance's VGPRs, scratch or occupancy changed with them (docs/HISTORY.md, round 19).
 
 namespace nexr {
 
@@ -164,17 +172,20 @@ __device__ __forceinline__ void flat_run(const FlatParams& P) {
   const uint32_t n = (uint32_t)P.nRanks, coll = (uint32_t)P.coll;
   const uint32_t nRegions = coll == kFlatReduceScatter ? n : 1u;
   const uint64_t regBytes = P.regionBytes;
-  const uint64_t pieces = (regBytes + kFlatPiece - 1) / kFlatPiece;  // the last one may be short
+  // this launch's pieces of every region: those of the window [winBeg, winEnd), numbered from the region's byte
+  // 0 (positions are the region's, whatever the window); the last one may be short
+  const uint64_t winEnd = P.winEnd, piece0 = P.winBeg / kFlatPiece;
+  const uint64_t pieces = (winEnd + kFlatPiece - 1) / kFlatPiece - piece0;
   const uint64_t nItems = pieces * nRegions;
   const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
   const uint32_t shift = (uint32_t)P.shift;
-  const uint32_t nOut = coll == kFlatAllReduce ? n : 1u;
+  const uint32_t nOut = coll == kFlatAllReduce ? (uint32_t)P.nOut : 1u;
   for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < nItems; it += nWaves) {
     uint64_t k = it;
     uint32_t d = 0;
     if (nRegions > 1) sym_split(it, nRegions, &k, &d);  // region fastest: few waves still touch every chunk
-    const uint64_t pBeg = k * kFlatPiece;
-    const uint64_t pEnd = pBeg + kFlatPiece < regBytes ? pBeg + kFlatPiece : regBytes;
+    const uint64_t pBeg = (piece0 + k) * kFlatPiece;
+    const uint64_t pEnd = pBeg + kFlatPiece < winEnd ? pBeg + kFlatPiece : winEnd;
     const uint64_t inBase = (uint64_t)d * regBytes;  // chunk d of every input
     const uint64_t mine = pBeg + lane * 16u;         // this lane's first pack, from the region's byte 0
     uint64_t cur = pBeg;

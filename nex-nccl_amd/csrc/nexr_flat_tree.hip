@@ -22,7 +22,9 @@
 // (DESIGN §8.8 has the numbers against lane-private LDS slots). User pointers are element-aligned only, so
 // every pack access is the unaligned-capable form; the buffer's last bytes below a pack go one element per
 // lane. Offsets are 64-bit, the cache policy is plain. A lane reads its bytes from every input before it
-// stores them, so an output may be an input.
+// stores them, so an output may be an input. A launch covers the byte window [winBeg, winEnd) of the buffer and
+// stores out[0 .. nOut), as nexr_flat.hip's: pieces keep their numbers from byte 0, so parts, trees and the tail
+// are those of a whole launch.
 
 namespace nexr {
 
@@ -187,13 +189,16 @@ __device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
   constexpr uint32_t esz = 16 / Ty<D>::EPP;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t n = (uint32_t)P.nRanks;
+  const uint32_t nOut = (uint32_t)P.nOut;  // the outputs that are stored: the first nOut of out[]
   const uint64_t nBytes = P.nBytes;
-  const uint64_t pieces = (nBytes + kFlatPiece - 1) / kFlatPiece;  // the last one may be short
+  // this launch's pieces: those of the window [winBeg, winEnd), numbered from the buffer's byte 0 (positions are
+  // the buffer's, whatever the window); the last one may be short
+  const uint64_t winEnd = P.winEnd;
+  const uint64_t pieces = (winEnd + kFlatPiece - 1) / kFlatPiece;
   const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
-  for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < pieces; it += nWaves) {
+  for (uint64_t it = P.winBeg / kFlatPiece + (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < pieces; it += nWaves) {
     const uint64_t pBeg = it * kFlatPiece;
-    const uint64_t pEnd = pBeg + kFlatPiece < nBytes ? pBeg + kFlatPiece : nBytes;
+    const uint64_t pEnd = pBeg + kFlatPiece < winEnd ? pBeg + kFlatPiece : winEnd;
     const uint64_t mine = pBeg + lane * 16u;  // this lane's first pack
     uint64_t cur = pBeg;
     while (cur < pEnd) {  // one pass per part that the piece touches: one, but for a piece with a boundary
@@ -210,7 +215,7 @@ __device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
           valid[u] = o >= cur && o + 16u <= end;  // whole packs of [cur, end)
         }
         flat_tree_fold<D, OP, IsMin, 2, kFlatPiece / 2, false>(P, t, mine, valid, out);
-        for (uint32_t r = 0; r < n; r++) {
+        for (uint32_t r = 0; r < nOut; r++) {
           char* w = P.out[r] + mine;
 #pragma unroll
           for (int u = 0; u < 2; u++)
@@ -223,7 +228,7 @@ __device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
         bool valid[1] = {lane < tail};
         u32x4 out[1];
         flat_tree_fold<D, OP, IsMin, 1, 0, true>(P, t, o, valid, out);
-        for (uint32_t r = 0; r < n; r++)
+        for (uint32_t r = 0; r < nOut; r++)
           if (valid[0]) flat_st_elem<esz>(P.out[r] + o, out[0]);
       }
       cur = end;
@@ -254,11 +259,12 @@ __global__ __launch_bounds__(kBlock) void flat_bcast_kernel(FlatBcastParams P) {
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t n = (uint32_t)P.nRanks;
   const uint64_t nBytes = P.nBytes;
-  const uint64_t pieces = (nBytes + kFlatPiece - 1) / kFlatPiece;
+  const uint64_t winEnd = P.winEnd;  // the window's pieces, numbered from the buffer's byte 0
+  const uint64_t pieces = (winEnd + kFlatPiece - 1) / kFlatPiece;
   const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
-  for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < pieces; it += nWaves) {
+  for (uint64_t it = P.winBeg / kFlatPiece + (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < pieces; it += nWaves) {
     const uint64_t pBeg = it * kFlatPiece;
-    const uint64_t pEnd = pBeg + kFlatPiece < nBytes ? pBeg + kFlatPiece : nBytes;
+    const uint64_t pEnd = pBeg + kFlatPiece < winEnd ? pBeg + kFlatPiece : winEnd;
     const uint64_t mine = pBeg + lane * 16u;
     bool valid[2];
     u32x4 v[2];

@@ -249,7 +249,10 @@ hipError_t sym_ll_blocks_per_cu(int coll, int dt, int* blocks);
 // nexrFlatReduceScatter, nexrFlatReduce; nexr_flat.hip). A region is what a wave's pieces are cut from: the
 // all-reduce's and the reduce's whole buffer, one chunk of the reduce-scatter (chunk d of an input starts at
 // byte d * regionBytes). The all-reduce's channel parts ride in the kernel arguments, or, beyond
-// kFlatInlineParts of them, in a stream-ordered workspace (`ext`).
+// kFlatInlineParts of them, in a stream-ordered workspace (`ext`). A launch covers the byte window
+// [winBeg, winEnd) of every region (winBeg a multiple of the 2048-byte piece; 0 and regionBytes: the whole
+// region). Positions stay global: a pointer addresses `ptr + region offset` whatever the window, so a buffer
+// that holds only the window's bytes is passed biased by -winBeg (the host entries' staged windows).
 enum { kFlatAllReduce = 0, kFlatReduceScatter = 1, kFlatReduce = 2 };
 constexpr int kFlatInlineParts = NEXR_FLAT_INLINE_PARTS;
 struct FlatParams {
@@ -257,12 +260,14 @@ struct FlatParams {
   char* out[NEXR_SYM_MAX_RANKS];  // the reduce: out[root] only
   uint64_t regionBytes;
   uint64_t redArg;
+  uint64_t winBeg, winEnd;  // the bytes of every region that this launch covers
   const nexrFlatPart* ext;  // non-null: the parts are there, not in parts[]
   int coll, nRanks;
   int nFold;      // inputs that enter the chain: nRanks, or 1 under nexrSemanticsShipped
   int shift;      // the folded inputs start at rank s + shift (0, or the chain's last rank under shipped SIMPLE)
   int userFirst;  // SIMPLE: the rank's own input is a step's first operand; else the partial is
-  int preOp, postOp, root, nParts, pad;
+  int preOp, postOp, root, nParts;
+  int nOut;  // the all-reduce stores out[0 .. nOut): nRanks, or fewer where outputs share a buffer
   nexrFlatPart parts[kFlatInlineParts];
 };
 static_assert(sizeof(FlatParams) <= 4000, "kernel argument block");
@@ -291,8 +296,10 @@ struct FlatTreeParams {
   char* out[NEXR_SYM_MAX_RANKS];
   uint64_t nBytes;
   uint64_t redArg;
+  uint64_t winBeg, winEnd;      // the bytes this launch covers, as FlatParams'
   const nexrFlatTreePart* ext;  // non-null: the parts are there, not in parts[]
-  int nRanks, userFirst, preOp, postOp, nParts, pad;
+  int nRanks, userFirst, preOp, postOp, nParts;
+  int nOut;  // out[0 .. nOut) are stored
   FlatTreeProgram prog[2];
   nexrFlatTreePart parts[kFlatTreeInlineParts];
 };
@@ -306,6 +313,7 @@ struct FlatBcastParams {
   const char* in;
   char* out[NEXR_SYM_MAX_RANKS];  // null: not written (its address is the input's)
   uint64_t nBytes;
+  uint64_t winBeg, winEnd;  // the bytes this launch covers, as FlatParams'
   int nRanks, pad;
 };
 hipError_t launch_flat_tree(int dt, int op, const FlatTreeParams& p, unsigned grid, hipStream_t s);

@@ -1163,16 +1163,26 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
 // every collective ends with (the completion word where the communicator uses it, as runGroup;
 // hipStreamSynchronize otherwise). No connection, no step counter and no report of the last collective's mode
 // is touched. `count` is what the one-rank path copies.
+// The host-memory communicators that the flat entries take (flatHost): thread ranks, SIMPLE (so the user input
+// is a step's first operand), the library's own reduce-copy (a caller's fn computes what it likes). Their one
+// launch goes on the first rank's device and stream, whatever GPUs the ranks' FIFO steps use.
+bool flatHostEligible(const nexrRingComm* c) {
+  return c && !c->peer && c->cfg.memMode == nexrRingHostMemory && c->proto == nexrRingProtoSimple &&
+         c->cfg.fn == defaultHostFn && c->cfg.nRanks <= NEXR_SYM_MAX_RANKS;
+}
+
 template <typename Launch>
 nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                           int datatype, Launch launch, const nexrDevRedOpFull* oneRankOp = nullptr) {
+                           int datatype, Launch launch, const nexrDevRedOpFull* oneRankOp = nullptr,
+                           bool flatHost = false) {
   const int n = c->cfg.nRanks;
   for (int i = 0; i < n; i++)
     if (count != 0 && (!sendbuffs[i] || !recvbuffs[i])) return nexrInvalidArgument;
-  if (c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || (int)c->devices.size() < n ||
+  const bool host = flatHost && flatHostEligible(c);
+  if (c->peer || c->broken || (c->cfg.memMode != nexrRingDeviceMemory && !host) || (int)c->devices.size() < n ||
       c->streams.empty() || !c->streams[0])
     return nexrInvalidUsage;
-  for (int i = 0; i < n; i++)
+  for (int i = 0; i < n && !host; i++)
     if (c->devices[i] != c->devices[0]) return nexrInvalidUsage;
   if (n > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
   if (count == 0) return nexrSuccess;
@@ -1185,7 +1195,7 @@ nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* 
   if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
   hipStream_t stream = c->streams[0];
   nexrResult_t r = launch(n, (nexrStream_t)stream);
-  if (r != nexrSuccess) return r;
+  if (r != nexrSuccess || host) return r;  // a host form returns with its outputs complete
   uint32_t* done = c->stepWaitWord && !c->done.empty() ? c->done[0] : nullptr;
   if (done) {
     const int timeoutMs = c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000;
@@ -1244,7 +1254,8 @@ nexrResult_t symAllGather(nexrRingComm* c, const void* const* sendbuffs, void* c
 // FIFO calls may alternate.
 nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
                             size_t count, int datatype, int op, int root) {
-  if (!c || c->peer) return nexrInvalidArgument;
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;  // process ranks: as nexrRingCommSetFlat and symCollective answer
   size_t esz;
   nexrDevRedOpFull red;
   nexrResult_t r = prepare(c, datatype, op, &esz, &red);
@@ -1257,23 +1268,25 @@ nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* s
   if (coll == kReduce)
     for (int i = 0; i < n; i++) outs[i] = recvbuffs[root];
   const int userFirst = c->proto == nexrRingProtoSimple ? 1 : 0;
+  const bool host = flatHostEligible(c);  // host memory: the same launch through the nexrFlatHost* forms
   return symCollective(
       c, sendbuffs, outs.data(), count, datatype,
       [&](int nr, nexrStream_t stream) {
         if (coll == kReduceScatter)
-          return nexrFlatReduceScatter(nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst,
-                                       stream);
+          return (host ? nexrFlatHostReduceScatter : nexrFlatReduceScatter)(nr, sendbuffs, recvbuffs, count, datatype,
+                                                                            red.op, red.scalarArg, userFirst, stream);
         if (coll == kReduce)
-          return nexrFlatReduce(nr, sendbuffs, recvbuffs[root], root, count, datatype, red.op, red.scalarArg,
-                                userFirst, stream);
+          return (host ? nexrFlatHostReduce : nexrFlatReduce)(nr, sendbuffs, recvbuffs[root], root, count, datatype,
+                                                              red.op, red.scalarArg, userFirst, stream);
         std::vector<nexrFlatPart> parts;
         for (const ChannelPart& part : channelParts(c, (int64_t)count, esz, /*ncclFuncAllReduce*/ 2))
           parts.push_back({(uint64_t)part.offset, (uint64_t)part.count,
                            (uint64_t)chunkElems(channelComm(c, part.channel), kGeomRing, esz, false, 0)});
-        return nexrFlatAllReduce(nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst,
-                                 parts.data(), (int)parts.size(), stream);
+        return (host ? nexrFlatHostAllReduce : nexrFlatAllReduce)(nr, sendbuffs, recvbuffs, count, datatype, red.op,
+                                                                  red.scalarArg, userFirst, parts.data(),
+                                                                  (int)parts.size(), stream);
       },
-      &red);
+      &red, true);
 }
 
 // nexrTreeAllReduceFlat: the tree all-reduce of the plain call as ONE nexrFlatTreeAllReduce launch. The parts are
@@ -1282,7 +1295,8 @@ nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* s
 // part (chunkElems(..., kGeomPipe, ...)) does not enter the result.
 nexrResult_t flatTreeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
                                int datatype, int op) {
-  if (!c || c->peer) return nexrInvalidArgument;
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;  // process ranks: as nexrRingCommSetFlat and symCollective answer
   size_t esz;
   nexrDevRedOpFull red;
   nexrResult_t r = prepare(c, datatype, op, &esz, &red);
@@ -1308,17 +1322,19 @@ nexrResult_t flatTreeAllReduce(nexrRingComm* c, const void* const* sendbuffs, vo
         }
         const nexrFlatTreeLinks* tp[2] = {trees.size() > 0 ? trees[0].data() : nullptr,
                                           trees.size() > 1 ? trees[1].data() : nullptr};
-        return nexrFlatTreeAllReduce(nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst, tp,
-                                     (int)trees.size(), parts.data(), (int)parts.size(), stream);
+        return (flatHostEligible(c) ? nexrFlatHostTreeAllReduce : nexrFlatTreeAllReduce)(
+            nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst, tp, (int)trees.size(),
+            parts.data(), (int)parts.size(), stream);
       },
-      &red);
+      &red, true);
 }
 
 // nexrRingBroadcastFlat: the broadcast as ONE nexrFlatBroadcast launch of the root's send buffer; only that
 // send buffer is needed, as in the plain call.
 nexrResult_t flatBroadcast(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
                            int datatype, int root) {
-  if (!c || c->peer) return nexrInvalidArgument;
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;  // process ranks: as nexrRingCommSetFlat and symCollective answer
   size_t esz;
   nexrDevRedOpFull red;
   nexrResult_t r = prepare(c, datatype, nexrSum, &esz, &red);  // ncclBroadcast: ncclSum
@@ -1327,18 +1343,40 @@ nexrResult_t flatBroadcast(nexrRingComm* c, const void* const* sendbuffs, void* 
   if (root < 0 || root >= n || !sendbuffs || !recvbuffs) return nexrInvalidArgument;
   if (count > (size_t)-1 / esz) return nexrInvalidArgument;
   std::vector<const void*> ins(n, sendbuffs[root]);
-  return symCollective(c, ins.data(), recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
-    return nexrFlatBroadcast(nr, sendbuffs[root], recvbuffs, count * esz, stream);
-  });
+  return symCollective(
+      c, ins.data(), recvbuffs, count, datatype,
+      [&](int nr, nexrStream_t stream) {
+        return (flatHostEligible(c) ? nexrFlatHostBroadcast : nexrFlatBroadcast)(nr, sendbuffs[root], recvbuffs,
+                                                                                 count * esz, stream);
+      },
+      nullptr, true);
+}
+
+// nexrRingAllGatherFlat: symAllGather, and on a host-memory communicator (flatHostEligible) its host form.
+nexrResult_t flatAllGather(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t sendcount,
+                           int datatype) {
+  if (!flatHostEligible(c)) return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  const size_t esz = nexrTypeSize(datatype);
+  if (esz == 0 || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
+  if (sendcount > (size_t)-1 / esz) return nexrInvalidArgument;
+  return symCollective(
+      c, sendbuffs, recvbuffs, sendcount, datatype,
+      [&](int n, nexrStream_t stream) {
+        return nexrFlatHostAllGather(n, sendbuffs, recvbuffs, sendcount * esz, stream);
+      },
+      nullptr, true);
 }
 
 // nexrRingCommSetFlat: whether the plain ring all-reduce, reduce-scatter and reduce of this communicator run
 // flat. Thread ranks in device memory on one GPU with the library's own kernels for the protocol (a caller's
-// fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes.
+// fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes; or thread ranks in
+// host memory that flatHostEligible takes.
 bool flatRouted(const nexrRingComm* c, int bit = NEXR_FLAT_RING) {
-  if (!c || !(c->flat & bit) || c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || c->streams.empty() ||
-      !c->streams[0] || c->cfg.nRanks > NEXR_SYM_MAX_RANKS || (int)c->devices.size() < c->cfg.nRanks)
+  if (!c || !(c->flat & bit) || c->peer || c->broken || c->streams.empty() || !c->streams[0] ||
+      c->cfg.nRanks > NEXR_SYM_MAX_RANKS || (int)c->devices.size() < c->cfg.nRanks)
     return false;
+  if (c->cfg.memMode != nexrRingDeviceMemory) return flatHostEligible(c);  // host memory: one launch on devices[0]
   const bool ownFn = c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
                      : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
                                                       : c->cfg.fn == defaultDeviceFn;
@@ -1369,7 +1407,7 @@ nexrResult_t copyOrFlat(nexrRingComm* c, RingColl coll, const void* const* sendb
                         size_t count, int datatype, int root) {
   if (!flatRouted(c, NEXR_FLAT_COPIES))
     return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, nexrSum, root);
-  const nexrResult_t r = coll == kAllGather ? symAllGather(c, sendbuffs, recvbuffs, count, datatype)
+  const nexrResult_t r = coll == kAllGather ? flatAllGather(c, sendbuffs, recvbuffs, count, datatype)
                                             : flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
   if (r == nexrSuccess) c->lastLLMode = 4;
   return r;
@@ -1628,25 +1666,25 @@ NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t c, const void* c
 
 NEXR_API nexrResult_t nexrRingAllReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t count, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
   return flatCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t c, const void* const* sendbuffs,
                                                 void* const* recvbuffs, size_t recvcount, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
   return flatCollective(c, kReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                          size_t count, int datatype, int op, int root) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
   return flatCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
 }
 
 NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t c, int on) {
   if (!c) return nexrInvalidArgument;
-  if (c->peer || c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
+  if (c->peer || (c->cfg.memMode != nexrRingDeviceMemory && !flatHostEligible(c))) return nexrInvalidUsage;
   if (on & ~(NEXR_FLAT_RING | NEXR_FLAT_TREE | NEXR_FLAT_COPIES)) return nexrInvalidArgument;
   c->flat = on;
   return nexrSuccess;
@@ -1654,20 +1692,20 @@ NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t c, int on) {
 
 NEXR_API nexrResult_t nexrTreeAllReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t count, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
   return flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
 }
 
 NEXR_API nexrResult_t nexrRingBroadcastFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t count, int datatype, int root) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
+  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
   return flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
 }
 
 NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t sendcount, int datatype) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
+  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
+  return flatAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,

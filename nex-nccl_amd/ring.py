@@ -298,8 +298,10 @@ class RingComm:
         """The ring's ncclAllReduce as ONE launch with the ring's own bytes (nexrRingAllReduceFlat): the chain
         of one reduce-copy step per rank runs in registers, over this communicator's own chunks, user input
         first for SIMPLE and partial first for LL / LL128. Every datatype and op of all_reduce. Thread ranks,
-        device memory, every rank on one GPU (else InvalidUsage). Touches no connection: mixes with ring,
-        tree and group calls, queued() stays as it was."""
+        device memory, every rank on one GPU; or thread ranks in host memory with SIMPLE and the library's own
+        reduce-copy, which run the host form (nexrFlatHostAllReduce: pinned buffers in place over the link,
+        pageable ones staged; ``flat_host_stats()`` of the package reports how). Else InvalidUsage. Touches no
+        connection: mixes with ring, tree and group calls, queued() stays as it was."""
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrRingAllReduceFlat(self._h, s, r, int(count), int(datatype), int(op)),
                "nexrRingAllReduceFlat")
@@ -343,9 +345,10 @@ class RingComm:
         """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat). `on` (FLAT_RING):
         all_reduce, reduce_scatter and reduce; `tree` (FLAT_TREE): tree_all_reduce; `copies` (FLAT_COPIES):
         all_gather and broadcast. The chosen calls then run as their _flat forms where the communicator is
-        eligible (thread ranks, device memory, one GPU, the library's own kernels), with the same bytes, and
-        queued() == 4 after such a call; every other call runs as without it. Between collectives;
-        InvalidUsage for process-rank or host-memory communicators."""
+        eligible (thread ranks, device memory, one GPU, the library's own kernels; or thread ranks in host
+        memory with SIMPLE and the library's own reduce-copy), with the same bytes, and queued() == 4 after such
+        a call; every other call runs as without it. Between collectives; InvalidUsage for process-rank
+        communicators and for host-memory communicators with a caller's fn, LL or LL128."""
         bits = (FLAT_RING if on else 0) | (FLAT_TREE if tree else 0) | (FLAT_COPIES if copies else 0)
         _check(self._L.nexrRingCommSetFlat(self._h, bits), "nexrRingCommSetFlat")
 
