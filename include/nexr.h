@@ -255,7 +255,9 @@ NEXR_API nexrResult_t nexrGetHostPathStats(nexrHostPathStats* stats, int reset);
 /*
  * nexrHostToDevRedOp — replaces hostToDevRedOp (reference src/enqueue.cc:2185-2278) for the
  * built-in ops: encodes (op, datatype, nRanks) into the device op and its 64-bit argument
- * (Min/Max xormask, Avg: integer nRanks<<1|signed or float 1/nRanks bit pattern).
+ * (Min/Max xormask, Avg: integer nRanks<<1|signed or float 1/nRanks bit pattern). A user-created op
+ * (its `default:` row, :2266-2275) is nexrInvalidArgument here: such ops belong to a communicator and are
+ * resolved by the ring library's table (nexrRingRedOpCreatePreMulSum, include/nexr_ring.h).
  */
 NEXR_API nexrResult_t nexrHostToDevRedOp(nexrDevRedOpFull* opFull, int op, int datatype, int nRanks);
 
@@ -969,6 +971,46 @@ NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* input
                                             const nexrFlatTreePart* parts, int nParts, nexrStream_t stream);
 NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
                                         nexrStream_t stream);
+
+/*
+ * nexrFlatAllReducePreMul, nexrFlatReduceScatterPreMul, nexrFlatReducePreMul, nexrFlatTreeAllReducePreMul —
+ * nexrFlatAllReduce, nexrFlatReduceScatter, nexrFlatReduce and nexrFlatTreeAllReduce under nexrDevPreMulSum with
+ * a scalar PER RANK: what a user-created PreMulSum op needs (ncclRedOpCreatePreMulSum, reference
+ * src/enqueue.cc:2447-2487; include/nexr_ring.h has the op table). The per-element rules are the ones stated
+ * above for nexrDevPreMulSum with "times the scalar" read as "times scalars[r] for rank r's input": indexed by the
+ * RANK whose input it is, whatever that rank's place in the chain or in the tree's program. Additions only: the
+ * ABI stays 0.3.
+ *
+ * scalars[r], r < nRanks: the raw bits of one element of `datatype` (the low bytes), or, with scalarsArePtrs !=
+ * 0, the device address of that element (element-aligned, readable on the current device). A device-resident
+ * scalar is read by the kernel itself, with no host read and no synchronisation: it holds whatever the stream
+ * wrote before the launch, and a replay of a captured graph sees the value current at the replay.
+ *
+ * Everything else is the plain entry's: the argument checks (plus nexrInvalidArgument for a null `scalars`, and
+ * with scalarsArePtrs for a null or misaligned entry), aliasing, alignment, stream order, graph capture, the
+ * parts, the trees, the semantics modes. Under nexrSemanticsShipped the pre-op returns its input, so the result
+ * is the plain entry's bit copy and does not depend on the scalars (they are not read). The kernels are separate
+ * instances, one per datatype; their argument block holds the n scalars in the room of inline parts, so an
+ * all-reduce takes the stream-ordered workspace beyond NEXR_FLAT_PREMUL_INLINE_PARTS parts and a tree all-reduce
+ * beyond NEXR_FLAT_TREE_PREMUL_INLINE_PARTS (the ring library's most is 64, one per channel).
+ */
+#define NEXR_FLAT_PREMUL_INLINE_PARTS 96
+#define NEXR_FLAT_TREE_PREMUL_INLINE_PARTS 64
+NEXR_API nexrResult_t nexrFlatAllReducePreMul(int nRanks, const void* const* inputs, void* const* outputs,
+                                              size_t nElts, int datatype, const uint64_t* scalars,
+                                              int scalarsArePtrs, int userFirst, const nexrFlatPart* parts,
+                                              int nParts, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatReduceScatterPreMul(int nRanks, const void* const* inputs, void* const* outputs,
+                                                  size_t nElts, int datatype, const uint64_t* scalars,
+                                                  int scalarsArePtrs, int userFirst, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatReducePreMul(int nRanks, const void* const* inputs, void* output, int root,
+                                           size_t nElts, int datatype, const uint64_t* scalars, int scalarsArePtrs,
+                                           int userFirst, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatTreeAllReducePreMul(int nRanks, const void* const* inputs, void* const* outputs,
+                                                  size_t nElts, int datatype, const uint64_t* scalars,
+                                                  int scalarsArePtrs, int userFirst,
+                                                  const nexrFlatTreeLinks* const* trees, int nTrees,
+                                                  const nexrFlatTreePart* parts, int nParts, nexrStream_t stream);
 
 /*
  * nexrFlatHostAllReduce, nexrFlatHostReduceScatter, nexrFlatHostReduce, nexrFlatHostTreeAllReduce,

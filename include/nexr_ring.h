@@ -90,7 +90,8 @@ typedef struct nexrRingComm* nexrRingComm_t;
 NEXR_API nexrResult_t nexrRingCommCreate(nexrRingComm_t* comm, const nexrRingConfig* config);
 
 /* ncclAllReduce over all emulated ranks at once: sendbuffs[r] / recvbuffs[r] are rank r's buffers
- * (host or device memory per memMode; in-place allowed). op is an ncclRedOp_t built-in. */
+ * (host or device memory per memMode; in-place allowed). op is an ncclRedOp_t built-in or a handle of
+ * nexrRingRedOpCreatePreMulSum (below). */
 NEXR_API nexrResult_t nexrRingAllReduce(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op);
 
@@ -261,6 +262,54 @@ NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* con
 #define NEXR_FLAT_TREE 2
 #define NEXR_FLAT_COPIES 4
 NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t comm, int on);
+
+/* User-created reduction ops: ncclRedOpCreatePreMulSum / ncclRedOpDestroy (reference src/nccl.h.in:305-325,
+ * src/enqueue.cc:2447-2518) and the `default:` row of hostToDevRedOp (:2266-2275). Under the op every rank's own
+ * input is multiplied by that rank's own scalar (rounded to the datatype) before the sum; nothing else is scaled.
+ *
+ * A thread-rank communicator holds all n ranks, so scalars[r] is rank r's scalar (the reference's ranks each call
+ * create with their own). nexrScalarHostImmediate: scalars[r] points to one element of `datatype` in host memory,
+ * copied at creation. nexrScalarDevice: scalars[r] is kept and dereferenced during every collective that uses the
+ * op (element-aligned; any memory the HIP runtime knows, device memory included; on a communicator that never
+ * touches HIP, because every step is a caller's function, the host's own memory). A device-resident scalar is
+ * read once per call and rank at the start of the call, by a copy ordered behind the rank's stream; the calls
+ * are blocking, so that is while the collective runs, and the next call sees a value rewritten in between.
+ *
+ * *op is nexrNumOps + ix. The table is the reference's (:2453-2471, :2508-2515): its capacity doubles from 4 and
+ * the free list is last-in first-out, so a destroyed handle is the next one handed out. Destroying an op does not
+ * wait for anything: the calls are blocking, so no collective is using it.
+ *
+ * nexrInvalidArgument, before any device call: destroying a built-in op; a handle that is out of range, already
+ * destroyed or never issued, in destroy or in a collective (:2491-2512, argcheck.cc:66); a collective whose
+ * datatype is not the op's (:2269-2273); fp8 or an unknown datatype or residence; a null `scalars` or a null
+ * entry. nexrInvalidUsage from create on a process-rank communicator (not built; its collectives therefore know
+ * no handle).
+ *
+ * Which entries take a handle wherever they take a built-in op: nexrRingAllReduce, nexrRingReduceScatter,
+ * nexrRingReduce, nexrTreeAllReduce, their ...Flat forms, and the one-rank path of each. Which keep refusing one
+ * with nexrInvalidArgument, exactly as they refuse op 5 without this: the symmetric entries (Sum only), the
+ * nexrPeerRing* entries, and the extras library's resident and send/recv entries (include/nexr_extras.h).
+ *
+ * How a call with a user op runs. Every rank's Primitives carries its own rank's scalar, which is all the
+ * host-sequenced SIMPLE / LL / LL128 steps (host or device memory), the queued LL launches and the per-rank LL
+ * runs on the device need: their pre-op applies to the rank's own input only. The launches that carry ONE
+ * redOpArg for all ranks (the group launches of nexrRingCommSetLLGroup / nexrRingCommSetSimpleGroup and the flat
+ * launches) serve a user op when all n scalars are bit-equal once read, and the call then runs exactly as
+ * ncclAvg's PreMulSum does. With differing scalars:
+ *   - a group option falls back to the mode the call would have run without it, one more case of the fall-back
+ *     lists of nexrRingCommSetLLGroup and nexrRingCommSetSimpleGroup; nexrRingCommGetQueued reports what ran;
+ *   - on a device-memory communicator the ...Flat entries, and the plain calls under nexrRingCommSetFlat, run
+ *     the launches with a scalar per rank (nexrFlatAllReducePreMul, nexrFlatReduceScatterPreMul,
+ *     nexrFlatReducePreMul, nexrFlatTreeAllReducePreMul, include/nexr.h): one launch, the same bytes, 4 reported;
+ *   - a host-memory communicator has no such launch: under nexrRingCommSetFlat the call runs host-sequenced, as
+ *     without the option, and reports 0; its explicit ...Flat entries return nexrInvalidUsage.
+ * A device-resident scalar on those device-memory flat calls is not read by the host at all: the kernel reads it
+ * (also when all n turn out equal), so what the communicator's first stream, or anything ordered before the
+ * call, wrote last is what counts. */
+typedef enum { nexrScalarDevice = 0, nexrScalarHostImmediate = 1 } nexrScalarResidence_t; /* = ncclScalarResidence_t */
+NEXR_API nexrResult_t nexrRingRedOpCreatePreMulSum(nexrRingComm_t comm, int* op, const void* const* scalars,
+                                                   int datatype, int residence);
+NEXR_API nexrResult_t nexrRingRedOpDestroy(nexrRingComm_t comm, int op);
 
 /* The tree links of `rank` in this communicator's topology: *up (-1 at the root) and down[0..2]
  * (-1 when absent, children packed first as setTreeDown does). */

@@ -93,6 +93,8 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrSymLLReduceScatter", "nexrSymLLAllGather",
                "nexrFlatAllReduce", "nexrFlatReduceScatter", "nexrFlatReduce",
                "nexrFlatTreeAllReduce", "nexrFlatBroadcast",
+               "nexrFlatAllReducePreMul", "nexrFlatReduceScatterPreMul", "nexrFlatReducePreMul",
+               "nexrFlatTreeAllReducePreMul",
                "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
                "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
@@ -362,6 +364,14 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatTreeAllReduce.restype = i32
     L.nexrFlatBroadcast.argtypes = [i32, vp, P(vp), sz, vp]
     L.nexrFlatBroadcast.restype = i32
+    L.nexrFlatAllReducePreMul.argtypes = [i32, P(vp), P(vp), sz, i32, P(u64), i32, i32, P(FlatPart), i32, vp]
+    L.nexrFlatReduceScatterPreMul.argtypes = [i32, P(vp), P(vp), sz, i32, P(u64), i32, i32, vp]
+    L.nexrFlatReducePreMul.argtypes = [i32, P(vp), vp, i32, sz, i32, P(u64), i32, i32, vp]
+    L.nexrFlatTreeAllReducePreMul.argtypes = [i32, P(vp), P(vp), sz, i32, P(u64), i32, i32, P(P(FlatTreeLinks)), i32,
+                                              P(FlatTreePart), i32, vp]
+    for name in ("nexrFlatAllReducePreMul", "nexrFlatReduceScatterPreMul", "nexrFlatReducePreMul",
+                 "nexrFlatTreeAllReducePreMul"):
+        getattr(L, name).restype = i32
     for host, dev in (("nexrFlatHostAllReduce", L.nexrFlatAllReduce),
                       ("nexrFlatHostReduceScatter", L.nexrFlatReduceScatter), ("nexrFlatHostReduce", L.nexrFlatReduce),
                       ("nexrFlatHostTreeAllReduce", L.nexrFlatTreeAllReduce),
@@ -967,6 +977,71 @@ def flat_tree_all_reduce(inputs: Sequence[int], outputs: Sequence[int], n_elts: 
                                      tarr, len(trees), arr, len(parts),
                                      ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatTreeAllReduce")
+
+
+FLAT_PREMUL_INLINE_PARTS = 96       # NEXR_FLAT_PREMUL_INLINE_PARTS
+FLAT_TREE_PREMUL_INLINE_PARTS = 64  # NEXR_FLAT_TREE_PREMUL_INLINE_PARTS
+
+
+def _scalar_array(scalars: Optional[Sequence[int]]):
+    if scalars is None:
+        return None
+    return (ctypes.c_uint64 * max(1, len(scalars)))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in scalars])
+
+
+def flat_all_reduce_premul(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                           scalars: Optional[Sequence[int]], scalars_are_ptrs: bool, user_first: bool,
+                           parts: Sequence[tuple], stream: int = 0) -> None:
+    """``flat_all_reduce`` under PreMulSum with a scalar per rank (``nexrFlatAllReducePreMul``): rank r's input is
+    multiplied by ``scalars[r]``, the raw bits of one element, or with ``scalars_are_ptrs`` the device address
+    the kernel reads it from (no host read: a copy queued on the stream before the launch is seen)."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    arr = (FlatPart * max(1, len(parts)))(*[FlatPart(int(o), int(c), int(k)) for o, c, k in parts])
+    rc = lib().nexrFlatAllReducePreMul(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts),
+                                       int(datatype), _scalar_array(scalars), 1 if scalars_are_ptrs else 0,
+                                       1 if user_first else 0, arr, len(parts),
+                                       ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllReducePreMul")
+
+
+def flat_reduce_scatter_premul(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                               scalars: Optional[Sequence[int]], scalars_are_ptrs: bool, user_first: bool,
+                               stream: int = 0) -> None:
+    """``flat_reduce_scatter`` with a scalar per rank (``nexrFlatReduceScatterPreMul``), as flat_all_reduce_premul."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatReduceScatterPreMul(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts),
+                                           int(datatype), _scalar_array(scalars), 1 if scalars_are_ptrs else 0,
+                                           1 if user_first else 0, ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatReduceScatterPreMul")
+
+
+def flat_reduce_premul(inputs: Sequence[int], output: int, root: int, n_elts: int, datatype: int,
+                       scalars: Optional[Sequence[int]], scalars_are_ptrs: bool, user_first: bool,
+                       stream: int = 0) -> None:
+    """``flat_reduce`` with a scalar per rank (``nexrFlatReducePreMul``), as flat_all_reduce_premul."""
+    rc = lib().nexrFlatReducePreMul(len(inputs), _ptr_array(inputs), ctypes.c_void_p(int(output)) if output else None,
+                                    int(root), int(n_elts), int(datatype), _scalar_array(scalars),
+                                    1 if scalars_are_ptrs else 0, 1 if user_first else 0,
+                                    ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatReducePreMul")
+
+
+def flat_tree_all_reduce_premul(inputs: Sequence[int], outputs: Sequence[int], n_elts: int, datatype: int,
+                                scalars: Optional[Sequence[int]], scalars_are_ptrs: bool, user_first: bool,
+                                trees: Sequence[Sequence[tuple]], parts: Sequence[tuple], stream: int = 0) -> None:
+    """``flat_tree_all_reduce`` with a scalar per rank (``nexrFlatTreeAllReducePreMul``), as
+    flat_all_reduce_premul."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    tarr, _keep = flat_tree_links(trees)
+    arr = (FlatTreePart * max(1, len(parts)))(*[FlatTreePart(int(o), int(c), int(t), 0) for o, c, t in parts])
+    rc = lib().nexrFlatTreeAllReducePreMul(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_elts),
+                                           int(datatype), _scalar_array(scalars), 1 if scalars_are_ptrs else 0,
+                                           1 if user_first else 0, tarr, len(trees), arr, len(parts),
+                                           ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatTreeAllReducePreMul")
 
 
 def flat_broadcast(input: int, outputs: Sequence[int], n_bytes: int, stream: int = 0) -> None:

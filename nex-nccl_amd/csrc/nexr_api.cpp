@@ -2357,26 +2357,35 @@ nexrResult_t flatAllReduceCheck(int nRanks, const void* const* inputs, void* con
   return nexrSuccess;
 }
 
+// A part list too long for a launch's arguments, in a stream-ordered workspace: the parts travel by value in
+// short launches ahead of the one, so nothing is read after return. The caller frees *ws behind its launch.
+nexrResult_t flatPartsWorkspace(const nexrFlatPart* parts, int nParts, hipStream_t s, nexrFlatPart** ws) {
+  NEXR_HIP(hipMallocAsync((void**)ws, (size_t)nParts * sizeof(nexrFlatPart), s));
+  FlatPartsFill f;
+  for (int k = 0; k < nParts; k += kFlatInlineParts) {
+    f.dst = *ws + k;
+    f.n = std::min(kFlatInlineParts, nParts - k);
+    f.pad = 0;
+    memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatPart));
+    const hipError_t e = launch_flat_parts(f, s);
+    if (e != hipSuccess) {
+      (void)hipFreeAsync(*ws, s);
+      *ws = nullptr;
+      return hipFail(e);
+    }
+  }
+  return nexrSuccess;
+}
+
 // One launch of a checked all-reduce over the window that p holds; gridCap > 0 caps the grid.
 nexrResult_t flatAllReduceLaunch(FlatParams& p, int dt, int op, const nexrFlatPart* parts, int nParts,
                                  uint64_t gridCapWgs, hipStream_t s) {
   nexrFlatPart* ws = nullptr;
   if (nParts <= kFlatInlineParts) {
     memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatPart));
-  } else {  // the parts travel by value in short launches ahead of the one: nothing is read after return
-    NEXR_HIP(hipMallocAsync((void**)&ws, (size_t)nParts * sizeof(nexrFlatPart), s));
-    FlatPartsFill f;
-    for (int k = 0; k < nParts; k += kFlatInlineParts) {
-      f.dst = ws + k;
-      f.n = std::min(kFlatInlineParts, nParts - k);
-      f.pad = 0;
-      memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatPart));
-      const hipError_t e = launch_flat_parts(f, s);
-      if (e != hipSuccess) {
-        (void)hipFreeAsync(ws, s);
-        return hipFail(e);
-      }
-    }
+  } else {
+    const nexrResult_t res = flatPartsWorkspace(parts, nParts, s, &ws);
+    if (res != nexrSuccess) return res;
     p.ext = ws;
   }
   const hipError_t e = launch_flat(dt, op, p, flatGrid(p.winEnd - p.winBeg, 1, gridCapWgs), s);
@@ -2603,26 +2612,34 @@ nexrResult_t flatTreeCheck(int nRanks, const void* const* inputs, void* const* o
   return nexrSuccess;
 }
 
+// flatPartsWorkspace for a tree's parts.
+nexrResult_t flatTreePartsWorkspace(const nexrFlatTreePart* parts, int nParts, hipStream_t s, nexrFlatTreePart** ws) {
+  NEXR_HIP(hipMallocAsync((void**)ws, (size_t)nParts * sizeof(nexrFlatTreePart), s));
+  FlatTreePartsFill f;
+  for (int k = 0; k < nParts; k += kFlatTreeInlineParts) {
+    f.dst = *ws + k;
+    f.n = std::min(kFlatTreeInlineParts, nParts - k);
+    f.pad = 0;
+    memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatTreePart));
+    const hipError_t e = launch_flat_tree_parts(f, s);
+    if (e != hipSuccess) {
+      (void)hipFreeAsync(*ws, s);
+      *ws = nullptr;
+      return hipFail(e);
+    }
+  }
+  return nexrSuccess;
+}
+
 // One launch of a checked tree all-reduce over the window that p holds; gridCapWgs > 0 caps the grid.
 nexrResult_t flatTreeLaunch(FlatTreeParams& p, int dt, int op, const nexrFlatTreePart* parts, int nParts,
                             uint64_t gridCapWgs, hipStream_t s) {
   nexrFlatTreePart* ws = nullptr;
   if (nParts <= kFlatTreeInlineParts) {
     memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatTreePart));
-  } else {  // the parts travel by value in short launches ahead of the one: nothing is read after return
-    NEXR_HIP(hipMallocAsync((void**)&ws, (size_t)nParts * sizeof(nexrFlatTreePart), s));
-    FlatTreePartsFill f;
-    for (int k = 0; k < nParts; k += kFlatTreeInlineParts) {
-      f.dst = ws + k;
-      f.n = std::min(kFlatTreeInlineParts, nParts - k);
-      f.pad = 0;
-      memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatTreePart));
-      const hipError_t e = launch_flat_tree_parts(f, s);
-      if (e != hipSuccess) {
-        (void)hipFreeAsync(ws, s);
-        return hipFail(e);
-      }
-    }
+  } else {
+    const nexrResult_t res = flatTreePartsWorkspace(parts, nParts, s, &ws);
+    if (res != nexrSuccess) return res;
     p.ext = ws;
   }
   const hipError_t e = launch_flat_tree(dt, op, p, flatGrid(p.winEnd - p.winBeg, 1, gridCapWgs), s);
@@ -2642,6 +2659,151 @@ NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* input
                                          trees, nTrees, parts, nParts, &p, &dt, &op);
   if (res != nexrSuccess || nElts == 0) return res;
   return flatTreeLaunch(p, dt, op, parts, nParts, 0, (hipStream_t)stream);
+}
+
+// ---- nexrFlat*PreMul: PreMulSum with a scalar per rank --------------------------------------------------------
+// The plain entry's checks run with nexrDevPreMulSum and make the plain launch's parameters; the scalars are
+// checked; then the fields move into the per-rank kernels' block. Under nexrSemanticsShipped the checks turn the
+// op into a bit copy without a pre-op: that is the plain kernel's launch, and no scalar is read.
+namespace {
+nexrResult_t flatScalarsCheck(int nRanks, const uint64_t* scalars, int arePtrs, int datatype) {
+  if (!scalars) return nexrInvalidArgument;
+  const uint64_t esz = typeSize(datatype);
+  for (int r = 0; arePtrs && r < nRanks; r++)
+    if (!scalars[r] || (scalars[r] & (esz - 1))) return nexrInvalidArgument;
+  return nexrSuccess;
+}
+
+void flatPreMulFrom(const FlatParams& p, const uint64_t* scalars, int arePtrs, FlatPreMulParams* q) {
+  memset((void*)q, 0, sizeof(*q));
+  memcpy(q->in, p.in, sizeof(q->in));
+  memcpy(q->out, p.out, sizeof(q->out));
+  memcpy(q->scalars, scalars, (size_t)p.nRanks * sizeof(uint64_t));
+  q->regionBytes = p.regionBytes;
+  q->winBeg = p.winBeg;
+  q->winEnd = p.winEnd;
+  q->coll = p.coll;
+  q->nRanks = p.nRanks;
+  q->nFold = p.nFold;
+  q->shift = p.shift;
+  q->userFirst = p.userFirst;
+  q->preOp = p.preOp;
+  q->postOp = p.postOp;
+  q->root = p.root;
+  q->nParts = p.nParts;
+  q->nOut = p.nOut;
+  q->scalarsArePtrs = arePtrs ? 1 : 0;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatAllReducePreMul(int nRanks, const void* const* inputs, void* const* outputs,
+                                              size_t nElts, int datatype, const uint64_t* scalars,
+                                              int scalarsArePtrs, int userFirst, const nexrFlatPart* parts,
+                                              int nParts, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  nexrResult_t res = flatAllReduceCheck(nRanks, inputs, outputs, nElts, datatype, nexrDevPreMulSum, 0, userFirst, parts,
+                                        nParts, &p, &dt, &op);
+  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
+  if (res != nexrSuccess || nElts == 0) return res;
+  hipStream_t s = (hipStream_t)stream;
+  if (op != nexrDevPreMulSum) return flatAllReduceLaunch(p, dt, op, parts, nParts, 0, s);
+  FlatPreMulParams q;
+  flatPreMulFrom(p, scalars, scalarsArePtrs, &q);
+  nexrFlatPart* ws = nullptr;
+  if (nParts <= kFlatPreMulInlineParts) {
+    memcpy(q.parts, parts, (size_t)nParts * sizeof(nexrFlatPart));
+  } else {
+    res = flatPartsWorkspace(parts, nParts, s, &ws);
+    if (res != nexrSuccess) return res;
+    q.ext = ws;
+  }
+  const hipError_t e = launch_flat_premul(dt, q, flatGrid(q.regionBytes, 1), s);
+  if (ws) (void)hipFreeAsync(ws, s);
+  NEXR_HIP(e);
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatReduceScatterPreMul(int nRanks, const void* const* inputs, void* const* outputs,
+                                                  size_t nElts, int datatype, const uint64_t* scalars,
+                                                  int scalarsArePtrs, int userFirst, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  nexrResult_t res = flatReduceScatterCheck(nRanks, inputs, outputs, nElts, datatype, nexrDevPreMulSum, 0, userFirst,
+                                            &p, &dt, &op);
+  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
+  if (res != nexrSuccess || nElts == 0) return res;
+  if (op != nexrDevPreMulSum) {
+    NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks), (hipStream_t)stream));
+    return nexrSuccess;
+  }
+  FlatPreMulParams q;
+  flatPreMulFrom(p, scalars, scalarsArePtrs, &q);
+  NEXR_HIP(launch_flat_premul(dt, q, flatGrid(q.regionBytes, nRanks), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatReducePreMul(int nRanks, const void* const* inputs, void* output, int root,
+                                           size_t nElts, int datatype, const uint64_t* scalars, int scalarsArePtrs,
+                                           int userFirst, nexrStream_t stream) {
+  FlatParams p;
+  int dt, op;
+  nexrResult_t res = flatReduceCheck(nRanks, inputs, output, root, nElts, datatype, nexrDevPreMulSum, 0, userFirst, &p,
+                                     &dt, &op);
+  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
+  if (res != nexrSuccess || nElts == 0) return res;
+  if (op != nexrDevPreMulSum) {
+    NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), (hipStream_t)stream));
+    return nexrSuccess;
+  }
+  FlatPreMulParams q;
+  flatPreMulFrom(p, scalars, scalarsArePtrs, &q);
+  NEXR_HIP(launch_flat_premul(dt, q, flatGrid(q.regionBytes, 1), (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatTreeAllReducePreMul(int nRanks, const void* const* inputs, void* const* outputs,
+                                                  size_t nElts, int datatype, const uint64_t* scalars,
+                                                  int scalarsArePtrs, int userFirst,
+                                                  const nexrFlatTreeLinks* const* trees, int nTrees,
+                                                  const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
+  FlatTreeParams p;
+  int dt, op;
+  nexrResult_t res = flatTreeCheck(nRanks, inputs, outputs, nElts, datatype, nexrDevPreMulSum, 0, userFirst, trees,
+                                   nTrees, parts, nParts, &p, &dt, &op);
+  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
+  if (res != nexrSuccess || nElts == 0) return res;
+  hipStream_t s = (hipStream_t)stream;
+  if (op != nexrDevPreMulSum) return flatTreeLaunch(p, dt, op, parts, nParts, 0, s);
+  FlatTreePreMulParams q;
+  memset((void*)&q, 0, sizeof(q));
+  memcpy(q.in, p.in, sizeof(q.in));
+  memcpy(q.out, p.out, sizeof(q.out));
+  memcpy(q.scalars, scalars, (size_t)nRanks * sizeof(uint64_t));
+  q.nBytes = p.nBytes;
+  q.winBeg = p.winBeg;
+  q.winEnd = p.winEnd;
+  q.nRanks = p.nRanks;
+  q.userFirst = p.userFirst;
+  q.preOp = p.preOp;
+  q.postOp = p.postOp;
+  q.nParts = p.nParts;
+  q.nOut = p.nOut;
+  q.scalarsArePtrs = scalarsArePtrs ? 1 : 0;
+  q.prog[0] = p.prog[0];
+  q.prog[1] = p.prog[1];
+  nexrFlatTreePart* ws = nullptr;
+  if (nParts <= kFlatTreePreMulInlineParts) {
+    memcpy(q.parts, parts, (size_t)nParts * sizeof(nexrFlatTreePart));
+  } else {
+    res = flatTreePartsWorkspace(parts, nParts, s, &ws);
+    if (res != nexrSuccess) return res;
+    q.ext = ws;
+  }
+  const hipError_t e = launch_flat_tree_premul(dt, q, flatGrid(q.nBytes, 1), s);
+  if (ws) (void)hipFreeAsync(ws, s);
+  NEXR_HIP(e);
+  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,

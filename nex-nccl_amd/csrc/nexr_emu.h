@@ -209,6 +209,19 @@ struct nexrRingComm {
   // and reduce; NEXR_FLAT_TREE: the tree all-reduce; NEXR_FLAT_COPIES: all-gather and broadcast) run as one flat
   // launch where the communicator is eligible (flatRouted, nexr_ring.cpp); lastLLMode reports 4 after such a call.
   int flat = 0;
+  // User-created reduction ops (nexrRingRedOpCreatePreMulSum): the reference's comm->userRedOps table
+  // (enqueue.cc:2453-2471, :2508-2515). Handle nexrNumOps + ix; the capacity (userRedOps.size()) doubles from 4;
+  // free entries are chained through freeNext from userRedOpFreeHead, last destroyed first, and an allocated
+  // entry has freeNext == -1. scalars[r] is rank r's: the raw bits of one element of `datatype`, or with isPtr the
+  // address the scalar is read from during every collective that uses the op.
+  struct UserRedOp {
+    int freeNext = 0;
+    int datatype = 0;
+    bool isPtr = false;
+    std::vector<uint64_t> scalars;
+  };
+  std::vector<UserRedOp> userRedOps;
+  int userRedOpFreeHead = 0;
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;

@@ -68,11 +68,32 @@ __device__ __forceinline__ uint64_t flat_div(uint64_t a, uint64_t b) {
   return ((a | b) >> 32) ? a / b : (uint64_t)((uint32_t)a / (uint32_t)b);
 }
 
+// With a scalar per rank: the scalar of each rank in flight, imm its bits or where they are, lo / hi the element
+// loaded from there (hi: 8-byte types). Nothing at all in the launches with one factor.
+template <bool kPerRank>
+struct FlatScalars {};
+template <>
+struct FlatScalars<true> {
+  uint64_t imm[kSymPeers];
+  uint32_t lo[kSymPeers], hi[kSymPeers];
+};
+template <class PT>
+__device__ __forceinline__ bool flat_scalars_from_mem(const PT& P, bool pre) {
+  if constexpr (PT::kPerRank) return pre && P.scalarsArePtrs != 0;
+  else return false;
+}
+
 // The chain of one lane's kPacks positions (kStride bytes apart, from byte `off` of every input), started at
 // rank `first`: the loads of up to kSymPeers ranks, then their steps. kElem: a position is one element, not
 // a 16-byte pack. A lane whose position is not valid[] loads nothing and folds zeros, which it does not store.
-template <int D, int OP, bool IsMin, int kPacks, int kStride, bool kElem>
-__device__ __forceinline__ void flat_fold(const FlatParams& P, uint32_t first, uint64_t off,
+// PT: the launch's parameters. With PT::kPerRank (FlatPreMulParams: a user-created PreMulSum op) the pre-op's
+// factor is the one of the RANK whose packs are being loaded, P.scalars[r], not one factor for the chain: it is
+// fetched in the load phase beside that rank's packs, a scalar load of the kernel argument for an immediate, or,
+// for a device-resident scalar (element-aligned only), one load of the element at a wave-uniform address by
+// every lane, made a scalar by readfirstlane where the step multiplies. The kernel reads such a scalar itself:
+// whatever the stream wrote before the launch is what it sees.
+template <class PT, int D, int OP, bool IsMin, int kPacks, int kStride, bool kElem>
+__device__ __forceinline__ void flat_fold(const PT& P, uint32_t first, uint64_t off,
                                           const bool (&valid)[kPacks], u32x4 (&out)[kPacks]) {
   using T = Ty<D>;
   using V = typename T::V;
@@ -83,15 +104,26 @@ __device__ __forceinline__ void flat_fold(const FlatParams& P, uint32_t first, u
   V factor = bc<V>((u32x4)0u);
   if constexpr (OP == nexrDevPreMulSum) {
     pre = P.preOp != 0;
-    factor = T::splat(P.redArg);
+    if constexpr (!PT::kPerRank) factor = T::splat(P.redArg);
   }
+  const bool fromMem = flat_scalars_from_mem(P, pre);
   V acc[kPacks];
   uint32_t r = first;
   for (uint32_t base = 0; base < nFold; base += kSymPeers) {  // wave-uniform, as everything but valid[]
     u32x4 v[kSymPeers][kPacks];
+    FlatScalars<PT::kPerRank> sc;  // PT::kPerRank: the scalars of the ranks whose packs are in flight
 #pragma unroll
     for (int j = 0; j < kSymPeers; j++) {
       if (base + j < nFold) {
+        if constexpr (PT::kPerRank) {
+          sc.imm[j] = P.scalars[r];
+          sc.lo[j] = sc.hi[j] = 0u;
+          if (fromMem) {  // every lane, the same address
+            const u32x4 e = flat_ld_elem<esz>((const char*)(uintptr_t)sc.imm[j]);
+            sc.lo[j] = e.x;
+            if constexpr (esz == 8) sc.hi[j] = e.y;
+          }
+        }
         const char* p = P.in[r] + off;  // scalar load of the pointer
 #pragma unroll
         for (int u = 0; u < kPacks; u++) {
@@ -110,6 +142,16 @@ __device__ __forceinline__ void flat_fold(const FlatParams& P, uint32_t first, u
 #pragma unroll
         for (int u = 0; u < kPacks; u++) {
           V x = bc<V>(v[j][u]);
+          if constexpr (PT::kPerRank) {
+            if (u == 0 && pre) {
+              uint64_t bits = sc.imm[j];
+              if (fromMem) {
+                bits = __builtin_amdgcn_readfirstlane(sc.lo[j]);
+                if constexpr (esz == 8) bits |= (uint64_t)__builtin_amdgcn_readfirstlane(sc.hi[j]) << 32;
+              }
+              factor = T::splat(bits);
+            }
+          }
           if constexpr (OP == nexrDevPreMulSum) {
             if (pre) x = T::mul(x, factor);  // Apply_PreOp on the rank's own input
           }
@@ -140,8 +182,8 @@ __device__ __forceinline__ void flat_fold(const FlatParams& P, uint32_t first, u
 // chunk ends. runRingAllReduce (nexr_ring.cpp; all_reduce.h:12-84) for the part {offset, count, chunkCount}
 // that holds i: loops of n * chunkCount elements, the last one in chunks of alignUp(divUp(rem, n), 16 / esz),
 // chunk c of a loop started by rank c + 1.
-__device__ __forceinline__ void flat_chunk(const FlatParams& P, uint64_t i, uint32_t epp, uint32_t* s,
-                                           uint64_t* end) {
+template <class PT>
+__device__ __forceinline__ void flat_chunk(const PT& P, uint64_t i, uint32_t epp, uint32_t* s, uint64_t* end) {
   const uint32_t n = (uint32_t)P.nRanks;
   uint32_t lo = 0, hi = (uint32_t)P.nParts - 1;  // the parts tile [0, nElts) in ascending order
   while (lo < hi) {
@@ -164,8 +206,8 @@ __device__ __forceinline__ void flat_chunk(const FlatParams& P, uint64_t i, uint
   *end = offset + L * loop + (chunkEnd < rem ? chunkEnd : rem);
 }
 
-template <int D, int OP, bool IsMin>
-__device__ __forceinline__ void flat_run(const FlatParams& P) {
+template <class PT, int D, int OP, bool IsMin>
+__device__ __forceinline__ void flat_run(const PT& P) {
   constexpr uint32_t esz = 16 / Ty<D>::EPP;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -211,7 +253,7 @@ __device__ __forceinline__ void flat_run(const FlatParams& P) {
           const uint64_t o = mine + (uint64_t)u * (kFlatPiece / 2);
           valid[u] = o >= cur && o + 16u <= end;  // whole packs of [cur, end)
         }
-        flat_fold<D, OP, IsMin, 2, kFlatPiece / 2, false>(P, first, inBase + mine, valid, out);
+        flat_fold<PT, D, OP, IsMin, 2, kFlatPiece / 2, false>(P, first, inBase + mine, valid, out);
         uint32_t r = outFirst;
         for (uint32_t q = 0; q < nOut; q++) {
           char* w = P.out[r] + mine;
@@ -226,7 +268,7 @@ __device__ __forceinline__ void flat_run(const FlatParams& P) {
         const uint64_t o = (regBytes & ~(uint64_t)15) + lane * esz;
         bool valid[1] = {lane < tail};
         u32x4 out[1];
-        flat_fold<D, OP, IsMin, 1, 0, true>(P, first, inBase + o, valid, out);
+        flat_fold<PT, D, OP, IsMin, 1, 0, true>(P, first, inBase + o, valid, out);
         uint32_t r = outFirst;
         for (uint32_t q = 0; q < nOut; q++) {
           if (valid[0]) flat_st_elem<esz>(P.out[r] + o, out[0]);
@@ -241,11 +283,19 @@ __device__ __forceinline__ void flat_run(const FlatParams& P) {
 template <int D, int OP>
 __global__ __launch_bounds__(kBlock) void flat_kernel(FlatParams P) {
   if constexpr (OP == nexrDevMinMax) {
-    if ((P.redArg & 1) == 0) flat_run<D, OP, true>(P);
-    else flat_run<D, OP, false>(P);
+    if ((P.redArg & 1) == 0) flat_run<FlatParams, D, OP, true>(P);
+    else flat_run<FlatParams, D, OP, false>(P);
   } else {
-    flat_run<D, OP, false>(P);
+    flat_run<FlatParams, D, OP, false>(P);
   }
+}
+
+// nexrFlatAllReducePreMul, nexrFlatReduceScatterPreMul, nexrFlatReducePreMul: the same run under PreMulSum with a
+// factor per rank (flat_fold's PT::kPerRank). Kernels of their own, one per datatype: the instances above are at
+// their SGPR limit and stay as they are.
+template <int D>
+__global__ __launch_bounds__(kBlock) void flat_premul_kernel(FlatPreMulParams P) {
+  flat_run<FlatPreMulParams, D, nexrDevPreMulSum, false>(P);
 }
 
 // Parts beyond the kernel arguments: a launch of this copies up to kFlatInlineParts of them, passed by value,
@@ -289,6 +339,25 @@ hipError_t launch_flat(int dt, int op, const FlatParams& p, unsigned grid, hipSt
   const void* fn = flat_fn(dt, op);
   if (!fn) return hipErrorInvalidValue;
   void* args[] = {const_cast<FlatParams*>(&p)};
+  return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, s);
+}
+
+hipError_t launch_flat_premul(int dt, const FlatPreMulParams& p, unsigned grid, hipStream_t s) {
+  const void* fn = nullptr;
+  switch (dt) {
+    case nexrInt8: fn = (const void*)&flat_premul_kernel<nexrInt8>; break;
+    case nexrUint8: fn = (const void*)&flat_premul_kernel<nexrUint8>; break;
+    case nexrInt32: fn = (const void*)&flat_premul_kernel<nexrInt32>; break;
+    case nexrUint32: fn = (const void*)&flat_premul_kernel<nexrUint32>; break;
+    case nexrInt64: fn = (const void*)&flat_premul_kernel<nexrInt64>; break;
+    case nexrUint64: fn = (const void*)&flat_premul_kernel<nexrUint64>; break;
+    case nexrFloat16: fn = (const void*)&flat_premul_kernel<nexrFloat16>; break;
+    case nexrFloat32: fn = (const void*)&flat_premul_kernel<nexrFloat32>; break;
+    case nexrFloat64: fn = (const void*)&flat_premul_kernel<nexrFloat64>; break;
+    case nexrBfloat16: fn = (const void*)&flat_premul_kernel<nexrBfloat16>; break;
+  }
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {const_cast<FlatPreMulParams*>(&p)};
   return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, s);
 }
 

@@ -171,8 +171,118 @@ __device__ __forceinline__ void flat_tree_fold(const FlatTreeParams& P, uint32_t
   }
 }
 
+// flat_tree_fold for the launches with a scalar per rank (FlatTreePreMulParams; OP is nexrDevPreMulSum): the same
+// program over the same loads, but the pre-op's factor is P.scalars[rank] of the rank whose input the LEAF / JOIN
+// consumes, fetched beside that rank's packs as nexr_flat.hip's flat_fold fetches it. A function of its own, so
+// that flat_tree_fold and every instance built from it stay as they are.
+template <class PT, int D, int kPacks, int kStride, bool kElem>
+__device__ __forceinline__ void flat_tree_fold_per_rank(const PT& P, uint32_t t, uint64_t off,
+                                                        const bool (&valid)[kPacks], u32x4 (&out)[kPacks]) {
+  constexpr int OP = nexrDevPreMulSum;
+  using T = Ty<D>;
+  using V = typename T::V;
+  constexpr int esz = 16 / T::EPP;
+  const FlatTreeProgram& G = P.prog[t];
+  const uint32_t nCode = (uint32_t)G.nCode, nIn = (uint32_t)G.nIn;
+  const bool userFirst = P.userFirst != 0;
+  const bool pre = P.preOp != 0;  // 0 under nexrSemanticsShipped only, which launches the plain kernels
+  const bool fromMem = pre && P.scalarsArePtrs != 0;
+  V factor = bc<V>((u32x4)0u);
+  V acc[kPacks];
+#pragma unroll
+  for (int u = 0; u < kPacks; u++) acc[u] = bc<V>((u32x4)0u);
+  FlatTreeSaved<kPacks> saved;
+  uint32_t sp = 0, pc = 0;  // wave-uniform, as everything but valid[]
+  // PUSH, or MERGE: one more source of the step of the rank whose accumulator was saved
+  auto stack_op = [&](uint32_t ins) {
+    if ((ins >> 6) == kFlatTreePush) {
+      u32x4 bits[kPacks];
+#pragma unroll
+      for (int u = 0; u < kPacks; u++) bits[u] = bc<u32x4>(acc[u]);
+      if (sp < (uint32_t)kFlatTreeSlots - 1) saved.put(sp, bits);
+      sp++;
+    } else {
+      sp = sp ? sp - 1 : 0;
+      u32x4 bits[kPacks];
+#pragma unroll
+      for (int u = 0; u < kPacks; u++) bits[u] = (u32x4)0u;
+      saved.get(sp, bits);
+#pragma unroll
+      for (int u = 0; u < kPacks; u++) {
+        const V top = bc<V>(bits[u]);
+        const V a = userFirst ? top : acc[u], b = userFirst ? acc[u] : top;
+        acc[u] = reduce_step<D, OP, false>(a, b);
+        if constexpr (T::kCanon) acc[u] = T::canon(acc[u]);
+      }
+    }
+  };
+  for (uint32_t base = 0; base < nIn; base += kSymPeers) {
+    u32x4 v[kSymPeers][kPacks];
+    FlatScalars<true> sc;  // the scalars of the ranks whose packs are in flight
+#pragma unroll
+    for (int j = 0; j < kSymPeers; j++) {
+      if (base + j < nIn) {
+        const uint32_t rank = flat_tree_byte(G.order, base + j) & 63u;
+        sc.imm[j] = P.scalars[rank];  // by RANK, whatever its place in the program
+        sc.lo[j] = sc.hi[j] = 0u;
+        if (fromMem) {  // every lane, the same address
+          const u32x4 e = flat_ld_elem<esz>((const char*)(uintptr_t)sc.imm[j]);
+          sc.lo[j] = e.x;
+          if constexpr (esz == 8) sc.hi[j] = e.y;
+        }
+        const char* p = P.in[rank] + off;  // scalar load of the pointer
+#pragma unroll
+        for (int u = 0; u < kPacks; u++) {
+          v[j][u] = (u32x4)0u;
+          if (valid[u]) {
+            if constexpr (kElem) v[j][u] = flat_ld_elem<esz>(p + u * kStride);
+            else v[j][u] = *(g_cu32x4_a1*)(p + u * kStride);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSymPeers; j++) {
+      if (base + j < nIn) {
+        uint32_t ins = flat_tree_byte(G.code, pc++);
+        while ((ins >> 6) >= kFlatTreePush && pc < nCode) {  // what stands before this input's consumer
+          stack_op(ins);
+          ins = flat_tree_byte(G.code, pc++);
+        }
+#pragma unroll
+        for (int u = 0; u < kPacks; u++) {
+          V x = bc<V>(v[j][u]);
+          if (u == 0 && pre) {
+            uint64_t bits = sc.imm[j];
+            if (fromMem) {
+              bits = __builtin_amdgcn_readfirstlane(sc.lo[j]);
+              if constexpr (esz == 8) bits |= (uint64_t)__builtin_amdgcn_readfirstlane(sc.hi[j]) << 32;
+            }
+            factor = T::splat(bits);
+          }
+          if (pre) x = T::mul(x, factor);  // Apply_PreOp on the rank's own input, by that rank's factor
+          if ((ins >> 6) == kFlatTreeLeaf) {  // the K = 1 step of a leaf: a bit copy without a pre-op
+            acc[u] = x;
+            if constexpr (T::kCanon) {
+              if (pre) acc[u] = T::canon(acc[u]);
+            }
+          } else {  // JOIN: the rank's own input and its first child's value
+            const V a = userFirst ? x : acc[u], b = userFirst ? acc[u] : x;
+            acc[u] = reduce_step<D, OP, false>(a, b);
+            if constexpr (T::kCanon) acc[u] = T::canon(acc[u]);
+          }
+        }
+      }
+    }
+  }
+  while (pc < nCode) stack_op(flat_tree_byte(G.code, pc++));  // the merges behind the last input
+#pragma unroll
+  for (int u = 0; u < kPacks; u++) out[u] = bc<u32x4>(acc[u]);
+}
+
 // The part of element i (wave-uniform): its tree and the element where the part ends.
-__device__ __forceinline__ void flat_tree_part(const FlatTreeParams& P, uint64_t i, uint32_t* t, uint64_t* end) {
+template <class PT>
+__device__ __forceinline__ void flat_tree_part(const PT& P, uint64_t i, uint32_t* t, uint64_t* end) {
   uint32_t lo = 0, hi = (uint32_t)P.nParts - 1;  // the parts tile [0, nElts) in ascending order
   while (lo < hi) {
     const uint32_t mid = (lo + hi) / 2;
@@ -184,8 +294,8 @@ __device__ __forceinline__ void flat_tree_part(const FlatTreeParams& P, uint64_t
   *end = P.ext ? P.ext[lo].offset + P.ext[lo].count : P.parts[lo].offset + P.parts[lo].count;
 }
 
-template <int D, int OP, bool IsMin>
-__device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
+template <class PT, int D, int OP, bool IsMin>
+__device__ __forceinline__ void flat_tree_run(const PT& P) {
   constexpr uint32_t esz = 16 / Ty<D>::EPP;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -214,7 +324,8 @@ __device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
           const uint64_t o = mine + (uint64_t)u * (kFlatPiece / 2);
           valid[u] = o >= cur && o + 16u <= end;  // whole packs of [cur, end)
         }
-        flat_tree_fold<D, OP, IsMin, 2, kFlatPiece / 2, false>(P, t, mine, valid, out);
+        if constexpr (PT::kPerRank) flat_tree_fold_per_rank<PT, D, 2, kFlatPiece / 2, false>(P, t, mine, valid, out);
+        else flat_tree_fold<D, OP, IsMin, 2, kFlatPiece / 2, false>(P, t, mine, valid, out);
         for (uint32_t r = 0; r < nOut; r++) {
           char* w = P.out[r] + mine;
 #pragma unroll
@@ -227,7 +338,8 @@ __device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
         const uint64_t o = (nBytes & ~(uint64_t)15) + lane * esz;
         bool valid[1] = {lane < tail};
         u32x4 out[1];
-        flat_tree_fold<D, OP, IsMin, 1, 0, true>(P, t, o, valid, out);
+        if constexpr (PT::kPerRank) flat_tree_fold_per_rank<PT, D, 1, 0, true>(P, t, o, valid, out);
+        else flat_tree_fold<D, OP, IsMin, 1, 0, true>(P, t, o, valid, out);
         for (uint32_t r = 0; r < nOut; r++)
           if (valid[0]) flat_st_elem<esz>(P.out[r] + o, out[0]);
       }
@@ -239,11 +351,18 @@ __device__ __forceinline__ void flat_tree_run(const FlatTreeParams& P) {
 template <int D, int OP>
 __global__ __launch_bounds__(kBlock) void flat_tree_kernel(FlatTreeParams P) {
   if constexpr (OP == nexrDevMinMax) {
-    if ((P.redArg & 1) == 0) flat_tree_run<D, OP, true>(P);
-    else flat_tree_run<D, OP, false>(P);
+    if ((P.redArg & 1) == 0) flat_tree_run<FlatTreeParams, D, OP, true>(P);
+    else flat_tree_run<FlatTreeParams, D, OP, false>(P);
   } else {
-    flat_tree_run<D, OP, false>(P);
+    flat_tree_run<FlatTreeParams, D, OP, false>(P);
   }
+}
+
+// nexrFlatTreeAllReducePreMul: the same run under PreMulSum with a factor per rank, kernels of their own (one per
+// datatype) whose argument block trades inline parts for the n scalars.
+template <int D>
+__global__ __launch_bounds__(kBlock) void flat_tree_premul_kernel(FlatTreePreMulParams P) {
+  flat_tree_run<FlatTreePreMulParams, D, nexrDevPreMulSum, false>(P);
 }
 
 // Parts beyond the kernel arguments, as flat_parts_kernel.
@@ -325,6 +444,25 @@ hipError_t launch_flat_tree(int dt, int op, const FlatTreeParams& p, unsigned gr
   const void* fn = flat_tree_fn(dt, op);
   if (!fn) return hipErrorInvalidValue;
   void* args[] = {const_cast<FlatTreeParams*>(&p)};
+  return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, s);
+}
+
+hipError_t launch_flat_tree_premul(int dt, const FlatTreePreMulParams& p, unsigned grid, hipStream_t s) {
+  const void* fn = nullptr;
+  switch (dt) {
+    case nexrInt8: fn = (const void*)&flat_tree_premul_kernel<nexrInt8>; break;
+    case nexrUint8: fn = (const void*)&flat_tree_premul_kernel<nexrUint8>; break;
+    case nexrInt32: fn = (const void*)&flat_tree_premul_kernel<nexrInt32>; break;
+    case nexrUint32: fn = (const void*)&flat_tree_premul_kernel<nexrUint32>; break;
+    case nexrInt64: fn = (const void*)&flat_tree_premul_kernel<nexrInt64>; break;
+    case nexrUint64: fn = (const void*)&flat_tree_premul_kernel<nexrUint64>; break;
+    case nexrFloat16: fn = (const void*)&flat_tree_premul_kernel<nexrFloat16>; break;
+    case nexrFloat32: fn = (const void*)&flat_tree_premul_kernel<nexrFloat32>; break;
+    case nexrFloat64: fn = (const void*)&flat_tree_premul_kernel<nexrFloat64>; break;
+    case nexrBfloat16: fn = (const void*)&flat_tree_premul_kernel<nexrBfloat16>; break;
+  }
+  if (!fn) return hipErrorInvalidValue;
+  void* args[] = {const_cast<FlatTreePreMulParams*>(&p)};
   return hipLaunchKernel(fn, dim3(grid), dim3(kBlock), args, 0, s);
 }
 

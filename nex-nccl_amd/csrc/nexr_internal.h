@@ -256,6 +256,7 @@ hipError_t sym_ll_blocks_per_cu(int coll, int dt, int* blocks);
 enum { kFlatAllReduce = 0, kFlatReduceScatter = 1, kFlatReduce = 2 };
 constexpr int kFlatInlineParts = NEXR_FLAT_INLINE_PARTS;
 struct FlatParams {
+  static constexpr bool kPerRank = false;  // one pre-op factor for the call: redArg
   const char* in[NEXR_SYM_MAX_RANKS];
   char* out[NEXR_SYM_MAX_RANKS];  // the reduce: out[root] only
   uint64_t regionBytes;
@@ -271,6 +272,28 @@ struct FlatParams {
   nexrFlatPart parts[kFlatInlineParts];
 };
 static_assert(sizeof(FlatParams) <= 4000, "kernel argument block");
+// nexrFlatAllReducePreMul / nexrFlatReduceScatterPreMul / nexrFlatReducePreMul: FlatParams' fields by the same
+// names (the kernel code is one template over both), PreMulSum implied, and rank r's pre-op scalar in scalars[r]:
+// the raw bits of one element, or with scalarsArePtrs the device address the kernel reads it from. The n scalars
+// take the room of inline parts: kFlatPreMulInlineParts of them ride in the arguments, longer lists in `ext`.
+constexpr int kFlatPreMulInlineParts = NEXR_FLAT_PREMUL_INLINE_PARTS;
+struct FlatPreMulParams {
+  static constexpr bool kPerRank = true;
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t scalars[NEXR_SYM_MAX_RANKS];
+  uint64_t regionBytes;
+  uint64_t winBeg, winEnd;
+  const nexrFlatPart* ext;
+  int coll, nRanks;
+  int nFold, shift, userFirst;
+  int preOp, postOp, root, nParts;
+  int nOut;
+  int scalarsArePtrs, pad;
+  nexrFlatPart parts[kFlatPreMulInlineParts];
+};
+static_assert(sizeof(FlatPreMulParams) <= 4000, "kernel argument block");
+hipError_t launch_flat_premul(int dt, const FlatPreMulParams& p, unsigned grid, hipStream_t s);
 struct FlatPartsFill {
   nexrFlatPart* dst;
   int n, pad;
@@ -292,6 +315,7 @@ struct FlatTreeProgram {
   int nCode, nIn;                           // nIn: n, or 1 under nexrSemanticsShipped
 };
 struct FlatTreeParams {
+  static constexpr bool kPerRank = false;  // one pre-op factor for the call: redArg
   const char* in[NEXR_SYM_MAX_RANKS];
   char* out[NEXR_SYM_MAX_RANKS];
   uint64_t nBytes;
@@ -304,6 +328,26 @@ struct FlatTreeParams {
   nexrFlatTreePart parts[kFlatTreeInlineParts];
 };
 static_assert(sizeof(FlatTreeParams) <= 4000, "kernel argument block");
+// nexrFlatTreeAllReducePreMul: FlatTreeParams' fields by the same names, PreMulSum implied, and the scalars as
+// FlatPreMulParams carries them. FlatTreeParams is 3,904 bytes with 96 inline parts: 64 more 8-byte entries fit
+// only with fewer of those, kFlatTreePreMulInlineParts; longer lists go to `ext` as they do already.
+constexpr int kFlatTreePreMulInlineParts = NEXR_FLAT_TREE_PREMUL_INLINE_PARTS;
+struct FlatTreePreMulParams {
+  static constexpr bool kPerRank = true;
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t scalars[NEXR_SYM_MAX_RANKS];
+  uint64_t nBytes;
+  uint64_t winBeg, winEnd;
+  const nexrFlatTreePart* ext;
+  int nRanks, userFirst, preOp, postOp, nParts;
+  int nOut;
+  int scalarsArePtrs, pad;
+  FlatTreeProgram prog[2];
+  nexrFlatTreePart parts[kFlatTreePreMulInlineParts];
+};
+static_assert(sizeof(FlatTreePreMulParams) <= 4000, "kernel argument block");
+hipError_t launch_flat_tree_premul(int dt, const FlatTreePreMulParams& p, unsigned grid, hipStream_t s);
 struct FlatTreePartsFill {
   nexrFlatTreePart* dst;
   int n, pad;

@@ -431,6 +431,72 @@ nexrResult_t prepare(nexrRingComm* c, int datatype, int op, size_t* esz, nexrDev
   return r;
 }
 
+// The op of a reduction on thread ranks, one nexrDevRedOpFull per rank: hostToDevRedOp with its `default:` row
+// (enqueue.cc:2266-2275). A built-in op is prepare's encoding n times. A user-created op (a handle of
+// nexrRingRedOpCreatePreMulSum) is looked up in the communicator's table, every check before any device call:
+// a handle out of range, destroyed or never issued and a datatype other than the op's are nexrInvalidArgument
+// (:2269-2273, :2509, argcheck.cc:66). Rank r's op is then PreMulSum with scalars[r]; a device-resident scalar is
+// read here, once per call and rank, by a copy ordered behind the rank's stream (hipMemcpyDefault: the scalar may
+// live in any memory the runtime knows), or by a plain load on a communicator that never touches HIP (a caller's
+// step functions: the address is then the host's). uniform: every rank's scalar has the same bits, so the
+// launches that carry ONE redOpArg (the group launches, the flat launches) serve the call as they serve Avg's
+// PreMulSum; otherwise only paths that give every rank its own argument do. readResident == false (the flat
+// launches with a scalar per rank, whose kernel reads a device-resident scalar itself): such scalars are not
+// read, rank[] holds no scalars and uniform is false; raw[] are the table's entries, addresses then.
+struct RedOps {
+  std::vector<nexrDevRedOpFull> rank;
+  bool uniform = true;
+  bool user = false;      // a user-created op
+  bool resident = false;  // ... whose scalars are device-resident
+  std::vector<uint64_t> raw;
+  // a launch with one redOpArg does not serve the call (a resident scalar counts: its kernel must read it)
+  bool perRank(bool read) const { return user && (!uniform || (resident && !read)); }
+};
+
+nexrResult_t prepareOps(nexrRingComm* c, int datatype, int op, size_t* esz, RedOps* ops, bool readResident = true) {
+  if (!c) return nexrInvalidArgument;
+  const int n = c->cfg.nRanks;
+  if (op >= 0 && op < nexrNumOps) {
+    nexrDevRedOpFull red;
+    const nexrResult_t r = prepare(c, datatype, op, esz, &red);
+    if (r == nexrSuccess) ops->rank.assign((size_t)n, red);
+    return r;
+  }
+  if (c->broken) return nexrInvalidUsage;
+  *esz = nexrTypeSize(datatype);
+  if (*esz == 0 || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
+  const int64_t ix = (int64_t)op - (int64_t)nexrNumOps;
+  if (c->peer || ix < 0 || ix >= (int64_t)c->userRedOps.size()) return nexrInvalidArgument;
+  const nexrRingComm::UserRedOp& user = c->userRedOps[(size_t)ix];
+  if (user.freeNext != -1 || user.datatype != datatype || (int)user.scalars.size() != n) return nexrInvalidArgument;
+  ops->rank.resize((size_t)n);
+  ops->user = true;
+  ops->resident = user.isPtr;
+  ops->raw = user.scalars;
+  for (int r = 0; r < n; r++) {
+    uint64_t bits = 0;
+    if (!user.isPtr) {
+      bits = user.scalars[(size_t)r];
+    } else if (!readResident) {
+      ops->uniform = false;
+    } else if (!c->needHip) {
+      memcpy(&bits, (const void*)(uintptr_t)user.scalars[(size_t)r], *esz);
+    } else {
+      hipStream_t s = c->streams[(size_t)r];
+      if (hipSetDevice(c->devices[(size_t)r]) != hipSuccess ||
+          hipMemcpyAsync(&bits, (const void*)(uintptr_t)user.scalars[(size_t)r], *esz, hipMemcpyDefault, s) != hipSuccess ||
+          hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipGetLastError();
+        return nexrUnhandledCudaError;
+      }
+    }
+    ops->rank[(size_t)r] = nexrDevRedOpFull{nexrDevPreMulSum, op, false, bits};
+    if (bits != ops->rank[0].scalarArg) ops->uniform = false;
+  }
+  c->started.store(true, std::memory_order_relaxed);  // a collective: the flag rule is fixed
+  return nexrSuccess;
+}
+
 // Test hook: NEXR_TEST_SPAWN_FAIL_AT=k makes the k-th thread creation (1-based) of the next
 // runThreads calls throw, as std::thread does when the system is out of threads. Read once per call
 // (tests set it between calls), never per thread.
@@ -814,12 +880,16 @@ nexrResult_t runGroup(nexrRingComm* c, std::vector<GroupMember>& members, int da
 
 // Thread-rank collectives: the ring schedules on one thread per rank.
 nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
-                            size_t count, int datatype, int op, int root, bool tryGroup = true) {
+                            size_t count, int datatype, int op, int root, bool tryGroup = true,
+                            const RedOps* resolved = nullptr) {
   if (!c || c->peer) return nexrInvalidArgument;
-  size_t esz;
-  nexrDevRedOpFull red;
-  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  size_t esz = nexrTypeSize(datatype);
+  RedOps own;
+  nexrResult_t r = resolved ? nexrSuccess : prepareOps(c, datatype, op, &esz, &own);
   if (r != nexrSuccess) return r;
+  const RedOps& ops = resolved ? *resolved : own;
+  const nexrDevRedOpFull& red = ops.rank[0];  // what a launch with one redOpArg carries (ops.uniform)
+  if (!ops.uniform) tryGroup = false;  // a scalar per rank: the mode the call would have run without the option
   const int n = c->cfg.nRanks;
   if ((coll == kReduce || coll == kBroadcast) && (root < 0 || root >= n)) return nexrInvalidArgument;
   if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
@@ -870,7 +940,7 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
       jobs.emplace_back([&, rank, part, member] {
         nexrRingComm* ck = channelComm(c, part.channel);
         if (ck->streams[rank]) (void)hipSetDevice(ck->devices[rank]);
-        Prims p = makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, red, g,
+        Prims p = makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, ops.rank[(size_t)rank], g,
                             ck->streams[rank], ck->status[rank]);
         p.recv[p.nRecv++] = ck->conns[rank];
         p.send[p.nSend++] = ck->conns[(rank + 1) % n];
@@ -922,7 +992,7 @@ nexrResult_t ringCollective(nexrRingComm* c, RingColl coll, const void* const* s
       }
       ck->cleanedSteps.store(cleaned0[ch++], std::memory_order_relaxed);
     }
-    return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root, false);
+    return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root, false, &ops);
   }
   if (r != nexrSuccess) c->broken = true;  // step counters are mid-protocol
   return r;
@@ -1037,12 +1107,15 @@ nexrResult_t peerFinish(nexrRingComm* c, Shared& sh) {
 // The tree all-reduce on thread ranks. Group launches (nexrRingCommSetLLGroup) as in ringCollective: every
 // Primitives of the call is a member, the root once and every other rank's two halves, 2n - 1 per channel.
 nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                           int datatype, int op, bool tryGroup = true) {
+                           int datatype, int op, bool tryGroup = true, const RedOps* resolved = nullptr) {
   if (!c || c->peer) return nexrInvalidArgument;
-  size_t esz;
-  nexrDevRedOpFull red;
-  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  size_t esz = nexrTypeSize(datatype);
+  RedOps own;
+  nexrResult_t r = resolved ? nexrSuccess : prepareOps(c, datatype, op, &esz, &own);
   if (r != nexrSuccess) return r;
+  const RedOps& ops = resolved ? *resolved : own;
+  const nexrDevRedOpFull& red = ops.rank[0];  // what a launch with one redOpArg carries (ops.uniform)
+  if (!ops.uniform) tryGroup = false;  // a scalar per rank: host-sequenced, as without the option
   const int n = c->cfg.nRanks;
   if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
   if (count == 0) return nexrSuccess;
@@ -1097,7 +1170,8 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
       const TreeLinks& t = ck->tree[rank];
       const bool leaf = t.down[0] == -1;
       auto make = [&, rank, ck](hipStream_t s, uint32_t* st) {
-        return makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, red, kGeomPipe, s, st);
+        return makePrims(ck, &sh, rank, sendbuffs[rank], recvbuffs[rank], esz, datatype, ops.rank[(size_t)rank],
+                         kGeomPipe, s, st);
       };
       GroupMember* member = group ? &members[jobs.size()] : nullptr;  // one job, one member, in this order
       if (t.up == -1) {  // root: recv from and send to every child
@@ -1150,7 +1224,7 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
           }
       ck->cleanedSteps.store(cleaned0[ch++], std::memory_order_relaxed);
     }
-    return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, false);
+    return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, false, &ops);
   }
   if (r != nexrSuccess) c->broken = true;  // step counters are mid-protocol
   return r;
@@ -1169,6 +1243,12 @@ nexrResult_t treeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* 
 bool flatHostEligible(const nexrRingComm* c) {
   return c && !c->peer && c->cfg.memMode == nexrRingHostMemory && c->proto == nexrRingProtoSimple &&
          c->cfg.fn == defaultHostFn && c->cfg.nRanks <= NEXR_SYM_MAX_RANKS;
+}
+
+// Whether a flat call reads a user op's device-resident scalars on the host (once, at its start) or leaves them to
+// the kernel: the launches with a scalar per rank exist for device memory only, and one rank has no launch.
+bool flatReadsResident(const nexrRingComm* c) {
+  return !c || c->cfg.memMode != nexrRingDeviceMemory || c->cfg.nRanks == 1;
 }
 
 template <typename Launch>
@@ -1253,13 +1333,21 @@ nexrResult_t symAllGather(nexrRingComm* c, const void* const* sendbuffs, void* c
 // SIMPLE communicator folds the user input first. No connection and no step counter is touched, so flat and
 // FIFO calls may alternate.
 nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
-                            size_t count, int datatype, int op, int root) {
+                            size_t count, int datatype, int op, int root, const RedOps* resolved = nullptr) {
   if (!c) return nexrInvalidArgument;
   if (c->peer) return nexrInvalidUsage;  // process ranks: as nexrRingCommSetFlat and symCollective answer
-  size_t esz;
-  nexrDevRedOpFull red;
-  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  size_t esz = nexrTypeSize(datatype);
+  RedOps own;
+  const bool host = flatHostEligible(c);  // host memory: the same launch through the nexrFlatHost* forms
+  const bool read = flatReadsResident(c);
+  nexrResult_t r = resolved ? nexrSuccess : prepareOps(c, datatype, op, &esz, &own, read);
   if (r != nexrSuccess) return r;
+  const RedOps& ops = resolved ? *resolved : own;
+  // A user op whose ranks' scalars differ, or are device-resident, takes the launches with a scalar per rank
+  // (nexrFlat*PreMul). They have no host-memory form: nexrInvalidUsage there (ringOrFlat does not come here).
+  const bool perRank = ops.perRank(read);
+  if (perRank && (host || c->cfg.memMode != nexrRingDeviceMemory)) return nexrInvalidUsage;
+  const nexrDevRedOpFull& red = ops.rank[0];
   const int n = c->cfg.nRanks;
   if (coll == kReduce && (root < 0 || root >= n)) return nexrInvalidArgument;
   if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
@@ -1268,10 +1356,15 @@ nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* s
   if (coll == kReduce)
     for (int i = 0; i < n; i++) outs[i] = recvbuffs[root];
   const int userFirst = c->proto == nexrRingProtoSimple ? 1 : 0;
-  const bool host = flatHostEligible(c);  // host memory: the same launch through the nexrFlatHost* forms
   return symCollective(
       c, sendbuffs, outs.data(), count, datatype,
       [&](int nr, nexrStream_t stream) {
+        if (perRank && coll == kReduceScatter)
+          return nexrFlatReduceScatterPreMul(nr, sendbuffs, recvbuffs, count, datatype, ops.raw.data(),
+                                             ops.resident ? 1 : 0, userFirst, stream);
+        if (perRank && coll == kReduce)
+          return nexrFlatReducePreMul(nr, sendbuffs, recvbuffs[root], root, count, datatype, ops.raw.data(),
+                                      ops.resident ? 1 : 0, userFirst, stream);
         if (coll == kReduceScatter)
           return (host ? nexrFlatHostReduceScatter : nexrFlatReduceScatter)(nr, sendbuffs, recvbuffs, count, datatype,
                                                                             red.op, red.scalarArg, userFirst, stream);
@@ -1282,6 +1375,9 @@ nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* s
         for (const ChannelPart& part : channelParts(c, (int64_t)count, esz, /*ncclFuncAllReduce*/ 2))
           parts.push_back({(uint64_t)part.offset, (uint64_t)part.count,
                            (uint64_t)chunkElems(channelComm(c, part.channel), kGeomRing, esz, false, 0)});
+        if (perRank)
+          return nexrFlatAllReducePreMul(nr, sendbuffs, recvbuffs, count, datatype, ops.raw.data(),
+                                         ops.resident ? 1 : 0, userFirst, parts.data(), (int)parts.size(), stream);
         return (host ? nexrFlatHostAllReduce : nexrFlatAllReduce)(nr, sendbuffs, recvbuffs, count, datatype, red.op,
                                                                   red.scalarArg, userFirst, parts.data(),
                                                                   (int)parts.size(), stream);
@@ -1294,13 +1390,18 @@ nexrResult_t flatCollective(nexrRingComm* c, RingColl coll, const void* const* s
 // the other tree of the double binary tree), and the operand order is the protocol's. The chunking inside a
 // part (chunkElems(..., kGeomPipe, ...)) does not enter the result.
 nexrResult_t flatTreeAllReduce(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                               int datatype, int op) {
+                               int datatype, int op, const RedOps* resolved = nullptr) {
   if (!c) return nexrInvalidArgument;
   if (c->peer) return nexrInvalidUsage;  // process ranks: as nexrRingCommSetFlat and symCollective answer
-  size_t esz;
-  nexrDevRedOpFull red;
-  nexrResult_t r = prepare(c, datatype, op, &esz, &red);
+  size_t esz = nexrTypeSize(datatype);
+  RedOps own;
+  const bool read = flatReadsResident(c);
+  nexrResult_t r = resolved ? nexrSuccess : prepareOps(c, datatype, op, &esz, &own, read);
   if (r != nexrSuccess) return r;
+  const RedOps& ops = resolved ? *resolved : own;
+  const bool perRank = ops.perRank(read);  // as flatCollective: nexrFlatTreeAllReducePreMul, device memory only
+  if (perRank && c->cfg.memMode != nexrRingDeviceMemory) return nexrInvalidUsage;
+  const nexrDevRedOpFull& red = ops.rank[0];
   if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
   const int userFirst = c->proto == nexrRingProtoSimple ? 1 : 0;
   return symCollective(
@@ -1322,6 +1423,10 @@ nexrResult_t flatTreeAllReduce(nexrRingComm* c, const void* const* sendbuffs, vo
         }
         const nexrFlatTreeLinks* tp[2] = {trees.size() > 0 ? trees[0].data() : nullptr,
                                           trees.size() > 1 ? trees[1].data() : nullptr};
+        if (perRank)
+          return nexrFlatTreeAllReducePreMul(nr, sendbuffs, recvbuffs, count, datatype, ops.raw.data(),
+                                             ops.resident ? 1 : 0, userFirst, tp, (int)trees.size(), parts.data(),
+                                             (int)parts.size(), stream);
         return (flatHostEligible(c) ? nexrFlatHostTreeAllReduce : nexrFlatTreeAllReduce)(
             nr, sendbuffs, recvbuffs, count, datatype, red.op, red.scalarArg, userFirst, tp, (int)trees.size(),
             parts.data(), (int)parts.size(), stream);
@@ -1389,7 +1494,17 @@ bool flatRouted(const nexrRingComm* c, int bit = NEXR_FLAT_RING) {
 nexrResult_t ringOrFlat(nexrRingComm* c, RingColl coll, const void* const* sendbuffs, void* const* recvbuffs,
                         size_t count, int datatype, int op, int root) {
   if (!flatRouted(c)) return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root);
-  const nexrResult_t r = flatCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root);
+  // The op is resolved once for either way. A user op whose ranks' scalars differ goes to the launches with a
+  // scalar per rank on a device-memory communicator (and so does a device-resident one, unread: the kernel reads
+  // it); a host-memory communicator has no such launch and runs the call as without the option, reporting how.
+  size_t esz;
+  RedOps ops;
+  const bool read = flatReadsResident(c);
+  nexrResult_t r = prepareOps(c, datatype, op, &esz, &ops, read);
+  if (r != nexrSuccess) return r;
+  if (ops.perRank(read) && c->cfg.memMode != nexrRingDeviceMemory)
+    return ringCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root, true, &ops);
+  r = flatCollective(c, coll, sendbuffs, recvbuffs, count, datatype, op, root, &ops);
   if (r == nexrSuccess) c->lastLLMode = 4;
   return r;
 }
@@ -1398,7 +1513,16 @@ nexrResult_t ringOrFlat(nexrRingComm* c, RingColl coll, const void* const* sendb
 nexrResult_t treeOrFlat(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
                         int datatype, int op) {
   if (!flatRouted(c, NEXR_FLAT_TREE)) return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
-  const nexrResult_t r = flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+  size_t esz;
+  RedOps ops;
+  const bool read = flatReadsResident(c);
+  nexrResult_t r = prepareOps(c, datatype, op, &esz, &ops, read);  // as ringOrFlat
+  if (r != nexrSuccess) return r;
+  if (ops.perRank(read) && c->cfg.memMode != nexrRingDeviceMemory) {
+    if (!c->llGroup) c->lastLLMode = 0;  // not the flat launch's 4: host-sequenced (with the group option the call reports)
+    return treeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, true, &ops);
+  }
+  r = flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, &ops);
   if (r == nexrSuccess) c->lastLLMode = 4;
   return r;
 }
@@ -1727,6 +1851,50 @@ NEXR_API nexrResult_t nexrRingAllGatherSymmetricLL(nexrRingComm_t c, const void*
                                                    int nBlocks) {
   DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
   return symLLAllGather(c, sendbuffs, recvbuffs, sendcount, datatype, nBlocks);
+}
+
+// ncclRedOpCreatePreMulSum (enqueue.cc:2447-2487) for a communicator that holds all n ranks: scalars[r] is what
+// rank r would have passed. The table grows and hands out entries exactly as the reference's.
+NEXR_API nexrResult_t nexrRingRedOpCreatePreMulSum(nexrRingComm_t c, int* op, const void* const* scalars, int datatype,
+                                                   int residence) {
+  if (!c || !op) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;
+  const size_t esz = nexrTypeSize(datatype);
+  if (esz == 0 || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
+  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
+  if (!scalars) return nexrInvalidArgument;
+  const int n = c->cfg.nRanks;
+  for (int r = 0; r < n; r++)
+    if (!scalars[r]) return nexrInvalidArgument;
+  if (c->userRedOpFreeHead == (int)c->userRedOps.size()) {  // double the capacity
+    const size_t cap = std::max<size_t>(4, 2 * c->userRedOps.size());
+    const size_t old = c->userRedOps.size();
+    c->userRedOps.resize(cap);
+    for (size_t ix = old; ix < cap; ix++) c->userRedOps[ix].freeNext = (int)ix + 1;
+  }
+  const int ix = c->userRedOpFreeHead;  // pop from the free list
+  nexrRingComm::UserRedOp& user = c->userRedOps[(size_t)ix];
+  c->userRedOpFreeHead = user.freeNext;
+  user.freeNext = -1;
+  user.datatype = datatype;
+  user.isPtr = residence == nexrScalarDevice;
+  user.scalars.assign((size_t)n, 0);
+  for (int r = 0; r < n; r++) {
+    if (user.isPtr) user.scalars[(size_t)r] = (uint64_t)(uintptr_t)scalars[r];
+    else memcpy(&user.scalars[(size_t)r], scalars[r], esz);
+  }
+  *op = (int)nexrNumOps + ix;
+  return nexrSuccess;
+}
+
+// ncclRedOpDestroy (enqueue.cc:2489-2518).
+NEXR_API nexrResult_t nexrRingRedOpDestroy(nexrRingComm_t c, int op) {
+  if (!c || op < (int)nexrNumOps) return nexrInvalidArgument;  // a built-in, or garbage
+  const int64_t ix = (int64_t)op - (int64_t)nexrNumOps;
+  if ((int64_t)c->userRedOps.size() <= ix || c->userRedOps[(size_t)ix].freeNext != -1) return nexrInvalidArgument;
+  c->userRedOps[(size_t)ix].freeNext = c->userRedOpFreeHead;  // push to the free list
+  c->userRedOpFreeHead = (int)ix;
+  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrRingCommGetStepWait(nexrRingComm_t c, int* word) {

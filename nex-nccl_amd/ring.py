@@ -25,7 +25,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
                     "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat",
-                    "nexrTreeTopology",
+                    "nexrTreeTopology", "nexrRingRedOpCreatePreMulSum", "nexrRingRedOpDestroy",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
                     "nexrRingCommSetLLFlagRule",
@@ -42,6 +42,8 @@ PROTO_SIMPLE = 0
 PROTO_LL = 1
 PROTO_LL128 = 2
 FLAT_RING, FLAT_TREE, FLAT_COPIES = 1, 2, 4  # NEXR_FLAT_*: nexrRingCommSetFlat's bits
+SCALAR_DEVICE, SCALAR_HOST_IMMEDIATE = 0, 1  # nexrScalarResidence_t (= ncclScalarResidence_t)
+NUM_OPS = 5  # nexrNumOps: the first user-created op's handle
 
 REDUCE_COPY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
@@ -90,6 +92,8 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingBroadcastFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingAllGatherFlat.argtypes = [vp, arr, arr, sz, i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.nexrRingRedOpCreatePreMulSum.argtypes = [vp, ctypes.POINTER(i32), arr, i32, i32]
+    L.nexrRingRedOpDestroy.argtypes = [vp, i32]
     L.nexrRingCommGetStepWait.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommGetQueued.argtypes = [vp, ctypes.POINTER(i32)]
     L.nexrRingCommSetLLGroup.argtypes = [vp, i32]
@@ -351,6 +355,40 @@ class RingComm:
         communicators and for host-memory communicators with a caller's fn, LL or LL128."""
         bits = (FLAT_RING if on else 0) | (FLAT_TREE if tree else 0) | (FLAT_COPIES if copies else 0)
         _check(self._L.nexrRingCommSetFlat(self._h, bits), "nexrRingCommSetFlat")
+
+    def create_premul_sum(self, scalars, datatype: int, residence: int = SCALAR_HOST_IMMEDIATE) -> int:
+        """ncclRedOpCreatePreMulSum for all ranks at once (nexrRingRedOpCreatePreMulSum): the handle of an op
+        under which rank r's own input is multiplied by scalars[r] before the sum. SCALAR_HOST_IMMEDIATE:
+        scalars[r] is one element of `datatype` as bytes or as anything with ``tobytes()`` (a numpy scalar of the
+        datatype's width), copied now. SCALAR_DEVICE: scalars[r] is an address, kept and read during every
+        collective that uses the op. None or a missing entry is passed on as a null pointer (InvalidArgument).
+        The handle goes where all_reduce, reduce_scatter, reduce, tree_all_reduce and their _flat forms take an
+        op; with differing scalars the group options and set_flat fall back (queued() reports what ran)."""
+        if scalars is None:
+            ptrs = None
+        else:
+            if len(scalars) != self.n_ranks:
+                raise NexrError(Result.InvalidArgument, "one scalar per rank")
+            keep = []
+            ptrs = (ctypes.c_void_p * self.n_ranks)()
+            for r, v in enumerate(scalars):
+                if v is None:
+                    ptrs[r] = None
+                elif residence == SCALAR_HOST_IMMEDIATE:
+                    raw = v.tobytes() if hasattr(v, "tobytes") else bytes(v)
+                    keep.append(ctypes.create_string_buffer(raw + bytes(8), len(raw) + 8))
+                    ptrs[r] = ctypes.addressof(keep[-1])
+                else:
+                    ptrs[r] = int(v)
+        op = ctypes.c_int(-1)
+        _check(self._L.nexrRingRedOpCreatePreMulSum(self._h, ctypes.byref(op), ptrs, int(datatype), int(residence)),
+               "nexrRingRedOpCreatePreMulSum")
+        return int(op.value)
+
+    def destroy_op(self, op: int) -> None:
+        """ncclRedOpDestroy (nexrRingRedOpDestroy): the handle is the next one create_premul_sum hands out.
+        InvalidArgument for a built-in op and for a handle that is not live."""
+        _check(self._L.nexrRingRedOpDestroy(self._h, int(op)), "nexrRingRedOpDestroy")
 
     def send_recv(self, sendbuffs, send_peers, recvbuffs, recv_peers, nbytes: int) -> None:
         """ncclSend/ncclRecv of every rank in one group: rank r sends nbytes of sendbuffs[r] to
