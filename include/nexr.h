@@ -1064,6 +1064,79 @@ NEXR_API nexrResult_t nexrFlatHostAllGather(int nRanks, const void* const* input
 NEXR_API nexrResult_t nexrGetFlatHostStats(nexrFlatHostStats* stats, int reset);
 
 /*
+ * nexrFlatGroup, nexrFlatGroupPlan — SEVERAL flat collectives as flat GROUP launches: what ncclGroupStart /
+ * ncclGroupEnd fuse (reference src/group.cc:17, :90-96; tasks binned by (func, op, datatype),
+ * src/enqueue.cc:374-385; several ncclDevWorkColl in one kernel, src/device/common.h:292-330). A single flat
+ * call is its launch and its completion wait; a group pays them once for many works. Additions only: the ABI
+ * stays 0.3. Device memory of the current device; PreMulSum with a scalar per rank, the tree all-reduce and
+ * host memory are not grouped.
+ *
+ * works[i] is one call. coll NEXR_FLAT_GROUP_ALL_REDUCE / _REDUCE_SCATTER / _REDUCE: nexrFlatAllReduce /
+ * nexrFlatReduceScatter / nexrFlatReduce with the work's datatype, devRedOp, redOpArg, root (reduce), inputs,
+ * outputs (the reduce reads outputs[root] only), nElts, and parts / nParts (all-reduce). NEXR_FLAT_GROUP_COPY:
+ * nElts BYTES from inputs[0] to outputs[0 .. nOutputs), as nexrFlatBroadcast copies (any byte alignment; an
+ * output at the source's address is skipped); a broadcast is one such work, an all-gather n of them. nRanks and
+ * userFirst hold for every reducing work.
+ *
+ * The result is the bytes the same works give when issued in array order through the single entries. The host
+ * walks the works in order and keeps one open launch per (datatype, devRedOp, min-or-max) and one for copies; a
+ * work joins its open launch. Two works conflict when a write range of one intersects a read or a write range
+ * of the other (byte ranges, half-open, as long as the entry's contract says: an all-reduce reads and writes
+ * nElts * esz bytes per buffer, a reduce-scatter reads n * nElts * esz, a reduce writes its root's output only);
+ * aliasing inside one work stays as the single entry defines it. A work that conflicts with a work of ANY open
+ * launch first closes all open launches, which are queued in the order they were opened; at the end the
+ * remaining ones are queued in that order. launchOf[i] (may be NULL) receives the launch of work i in queue
+ * order, -1 for a work with nElts == 0, which costs nothing.
+ *
+ * A launch runs the table of its works (flat_group_kernel / flat_group_copy_kernel): records with pointers for
+ * nRanks ranks only and the parts in a pool behind them. A table that fits NEXR_FLAT_GROUP_INLINE_BYTES rides
+ * in the kernel arguments, and the launch takes no workspace; a longer one goes by value, in short fill
+ * launches ahead of the launch, into stream-ordered memory that is freed behind it. Nothing of the caller's
+ * arrays is read after the call returns, so the call can be captured into a graph. maxWorkgroups caps every
+ * launch's grid (waves then stride over the items); 0: a wave per 2048-byte piece over the launch's summed
+ * pieces, four waves per workgroup. nWorks == 0 succeeds without a launch.
+ *
+ * info (may be NULL): works placed in a launch, launches, fill launches, cuts, the sum of the tables' bytes and of
+ * the launches' workgroups. nexrFlatGroupPlan does the same validation and fills launchOf and info without any
+ * device call.
+ *
+ * nexrInvalidArgument, before any device call: everything the single entry of a work refuses for its buffers,
+ * datatype, op, root, sizes and parts; a null `works`; nWorks < 0; an unknown coll; nOutputs
+ * outside 1..NEXR_SYM_MAX_RANKS or a null source or destination (copy); maxWorkgroups < 0.
+ */
+#define NEXR_FLAT_GROUP_ALL_REDUCE 0
+#define NEXR_FLAT_GROUP_REDUCE_SCATTER 1
+#define NEXR_FLAT_GROUP_REDUCE 2
+#define NEXR_FLAT_GROUP_COPY 3
+#define NEXR_FLAT_GROUP_INLINE_BYTES 3936 /* the longest table that rides in the kernel arguments */
+#define NEXR_FLAT_GROUP_FILL_BYTES 3968   /* what one fill launch carries of a longer one */
+typedef struct {
+  int coll;                   /* NEXR_FLAT_GROUP_* */
+  int datatype;               /* reducing works */
+  int devRedOp;
+  int root;                   /* reduce */
+  uint64_t redOpArg;
+  const void* const* inputs;  /* nRanks entries; copy: inputs[0] */
+  void* const* outputs;       /* nRanks entries; copy: nOutputs */
+  int nOutputs;               /* copy only */
+  int nParts;                 /* all-reduce only */
+  const nexrFlatPart* parts;
+  size_t nElts;               /* copy: bytes */
+} nexrFlatGroupWork;
+typedef struct {
+  int works;          /* works that went into a launch */
+  int launches;       /* group launches */
+  int fillLaunches;   /* launches that carry tables too long for the kernel arguments */
+  int cuts;           /* conflicts that closed the open launches */
+  uint64_t tableBytes;
+  uint64_t workgroups;
+} nexrFlatGroupInfo;
+NEXR_API nexrResult_t nexrFlatGroup(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst,
+                                    int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatGroupPlan(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst,
+                                        int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info);
+
+/*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
  * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.

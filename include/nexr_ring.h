@@ -263,6 +263,42 @@ NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* con
 #define NEXR_FLAT_COPIES 4
 NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t comm, int on);
 
+/*
+ * nexrRingGroupStart, nexrRingGroupEnd — ncclGroupStart / ncclGroupEnd (reference src/nccl.h.in:472-504,
+ * src/group.cc:17, :90-96) for a thread-rank communicator: the collectives called between the two are recorded
+ * and run by the outermost nexrRingGroupEnd, and those that would run flat go out as flat GROUP launches
+ * (nexrFlatGroup, include/nexr.h), so that many small calls pay one launch per kind and one completion wait. The
+ * result is the bytes of the same calls made one by one in call order. Additions only: the ABI stays 0.3.
+ *
+ * Start and End nest by depth (ncclGroupDepth); an End without a Start and a process-rank communicator are
+ * nexrInvalidUsage. While the depth is above 0 every collective entry of this header checks its arguments (the
+ * communicator's state, datatype, op, root, null arrays and null buffers) and returns its error at once, without
+ * recording the call; otherwise it copies its pointer arrays, records the call and returns nexrSuccess. Nothing
+ * of the caller's arrays is read afterwards.
+ *
+ * The outermost End walks the recorded calls in order. A call becomes work records if it is a ring all-reduce,
+ * reduce-scatter, reduce, all-gather or broadcast that would run flat (an explicit ...Flat entry, or a plain call
+ * whose nexrRingCommSetFlat bit is set) on a device-memory communicator of 2 or more ranks on one GPU, without
+ * per-rank scalars; runs of consecutive such calls go to ONE nexrFlatGroup call on the communicator's first
+ * stream, each all-reduce with the channel parts it has alone (the reference's split of one channel set over the
+ * tasks of a group, scheduleCollTasksToPlan, is not restated: it would change a grouped float all-reduce's
+ * bytes). An all-gather is n copies, a broadcast one. Every other recorded call (the tree, a per-rank or
+ * device-resident PreMulSum op, the symmetric entries, the FIFO paths, host memory, one rank) ends the run,
+ * waits for what was queued and executes as it does alone. The End waits once for the group launches it queued.
+ * The first error of the execution is returned and later recorded calls are not run; the group is cleared either
+ * way. nexrRingCommGetQueued reports 5 after an End that queued at least one group launch.
+ *
+ * nexrRingGroupGetStats — since creation or the last reset: calls recorded, group launches, fill launches (tables
+ * beyond the kernel arguments), calls run singly, and cuts (conflicts between works that closed the open
+ * launches of a nexrFlatGroup call). reset != 0 zeroes the counters after reading them.
+ */
+typedef struct {
+  uint64_t calls, groupLaunches, fillLaunches, singles, cuts;
+} nexrRingGroupStats;
+NEXR_API nexrResult_t nexrRingGroupStart(nexrRingComm_t comm);
+NEXR_API nexrResult_t nexrRingGroupEnd(nexrRingComm_t comm);
+NEXR_API nexrResult_t nexrRingGroupGetStats(nexrRingComm_t comm, nexrRingGroupStats* stats, int reset);
+
 /* User-created reduction ops: ncclRedOpCreatePreMulSum / ncclRedOpDestroy (reference src/nccl.h.in:305-325,
  * src/enqueue.cc:2447-2518) and the `default:` row of hostToDevRedOp (:2266-2275). Under the op every rank's own
  * input is multiplied by that rank's own scalar (rounded to the datatype) before the sum; nothing else is scaled.

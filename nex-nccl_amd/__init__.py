@@ -97,6 +97,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrFlatTreeAllReducePreMul",
                "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
                "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
+               "nexrFlatGroup", "nexrFlatGroupPlan",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -115,6 +116,20 @@ class NexrError(RuntimeError):
 class FlatPart(ctypes.Structure):
     """nexrFlatPart: one channel's part of a flat all-reduce, in elements."""
     _fields_ = [("offset", ctypes.c_uint64), ("count", ctypes.c_uint64), ("chunkCount", ctypes.c_uint64)]
+
+
+class FlatGroupWork(ctypes.Structure):
+    """nexrFlatGroupWork: one call of a flat group (include/nexr.h)."""
+    _fields_ = [("coll", ctypes.c_int), ("datatype", ctypes.c_int), ("devRedOp", ctypes.c_int), ("root", ctypes.c_int),
+                ("redOpArg", ctypes.c_uint64), ("inputs", ctypes.POINTER(ctypes.c_void_p)),
+                ("outputs", ctypes.POINTER(ctypes.c_void_p)), ("nOutputs", ctypes.c_int), ("nParts", ctypes.c_int),
+                ("parts", ctypes.POINTER(FlatPart)), ("nElts", ctypes.c_size_t)]
+
+
+class FlatGroupInfo(ctypes.Structure):
+    """nexrFlatGroupInfo: what a flat group call made of its works."""
+    _fields_ = [("works", ctypes.c_int), ("launches", ctypes.c_int), ("fillLaunches", ctypes.c_int),
+                ("cuts", ctypes.c_int), ("tableBytes", ctypes.c_uint64), ("workgroups", ctypes.c_uint64)]
 
 
 class FlatTreeLinks(ctypes.Structure):
@@ -379,6 +394,10 @@ def lib() -> ctypes.CDLL:
         f = getattr(L, host)   # the device entry's argument list
         f.argtypes = dev.argtypes
         f.restype = i32
+    L.nexrFlatGroup.argtypes = [i32, P(FlatGroupWork), i32, i32, i32, P(i32), P(FlatGroupInfo), vp]
+    L.nexrFlatGroup.restype = i32
+    L.nexrFlatGroupPlan.argtypes = [i32, P(FlatGroupWork), i32, i32, i32, P(i32), P(FlatGroupInfo)]
+    L.nexrFlatGroupPlan.restype = i32
     L.nexrGetFlatHostStats.argtypes = [P(FlatHostStats), i32]
     L.nexrGetFlatHostStats.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
@@ -940,6 +959,60 @@ def flat_reduce(inputs: Sequence[int], output: int, root: int, n_elts: int, data
                               int(red_op_arg) & 0xFFFFFFFFFFFFFFFF, 1 if user_first else 0,
                               ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatReduce")
+
+
+FLAT_GROUP_ALL_REDUCE, FLAT_GROUP_REDUCE_SCATTER, FLAT_GROUP_REDUCE, FLAT_GROUP_COPY = 0, 1, 2, 3  # NEXR_FLAT_GROUP_*
+FLAT_GROUP_INLINE_BYTES = 3936  # NEXR_FLAT_GROUP_INLINE_BYTES
+FLAT_GROUP_FILL_BYTES = 3968    # NEXR_FLAT_GROUP_FILL_BYTES
+
+
+def flat_group_works(works: Sequence[dict]):
+    """(array of nexrFlatGroupWork, keep-alive) for works given as dicts: ``coll`` (FLAT_GROUP_*), ``inputs`` and
+    ``outputs`` (device addresses; a copy: one input and its destinations), ``n_elts`` (a copy: bytes), and for
+    the reducing ones ``datatype``, ``dev_red_op``, ``red_op_arg`` (0), ``root`` (0) and, all-reduce only,
+    ``parts`` as (offset, count, chunkCount)."""
+    arr = (FlatGroupWork * max(1, len(works)))()
+    keep = []
+    for i, w in enumerate(works):
+        ins, outs = _ptr_array(w["inputs"]), _ptr_array(w["outputs"])
+        parts = w.get("parts") or ()
+        pa = (FlatPart * max(1, len(parts)))(*[FlatPart(int(o), int(c), int(k)) for o, c, k in parts])
+        keep += [ins, outs, pa]
+        arr[i] = FlatGroupWork(int(w["coll"]), int(w.get("datatype", 0)), int(w.get("dev_red_op", 0)),
+                               int(w.get("root", 0)), int(w.get("red_op_arg", 0)) & 0xFFFFFFFFFFFFFFFF,
+                               ctypes.cast(ins, ctypes.POINTER(ctypes.c_void_p)),
+                               ctypes.cast(outs, ctypes.POINTER(ctypes.c_void_p)), len(w["outputs"]), len(parts), pa,
+                               int(w["n_elts"]))
+    return arr, keep
+
+
+def _flat_group(plan_only: bool, n_ranks: int, works: Sequence[dict], user_first: bool, max_workgroups: int,
+                stream: int):
+    arr, keep = flat_group_works(works)
+    launch_of = (ctypes.c_int * max(1, len(works)))()
+    info = FlatGroupInfo()
+    args = [int(n_ranks), arr, len(works), 1 if user_first else 0, int(max_workgroups), launch_of, ctypes.byref(info)]
+    if plan_only:
+        _check(lib().nexrFlatGroupPlan(*args), "nexrFlatGroupPlan")
+    else:
+        _check(lib().nexrFlatGroup(*args, ctypes.c_void_p(int(stream)) if stream else None), "nexrFlatGroup")
+    del keep
+    return list(launch_of[:len(works)]), {"works": info.works, "launches": info.launches,
+                                          "fill_launches": info.fillLaunches, "cuts": info.cuts, "table_bytes": info.tableBytes,
+                                          "workgroups": info.workgroups}
+
+
+def flat_group(n_ranks: int, works: Sequence[dict], user_first: bool, max_workgroups: int = 0, stream: int = 0):
+    """Several flat collectives as flat GROUP launches (``nexrFlatGroup``): the bytes of the same works issued in
+    order through flat_all_reduce / flat_reduce_scatter / flat_reduce / flat_broadcast, one launch per (datatype,
+    op, min-or-max) and one for copies between two conflicts. ``works`` as flat_group_works takes them. Returns
+    (launch_of, info): the launch of every work (-1: empty) and the counts. Stream-ordered."""
+    return _flat_group(False, n_ranks, works, user_first, max_workgroups, stream)
+
+
+def flat_group_plan(n_ranks: int, works: Sequence[dict], user_first: bool, max_workgroups: int = 0):
+    """flat_group's validation and launch plan without any device call (``nexrFlatGroupPlan``)."""
+    return _flat_group(True, n_ranks, works, user_first, max_workgroups, 0)
 
 
 FLAT_TREE_SLOTS = 8          # NEXR_FLAT_TREE_SLOTS

@@ -2828,6 +2828,290 @@ NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* con
   return nexrSuccess;
 }
 
+// ---- nexrFlatGroup, nexrFlatGroupPlan: several flat collectives as group launches -----------------------------
+// The plan (no device call): every work through its single entry's checks, then the walk of include/nexr.h: one
+// open launch per key, a conflict with a work of any open launch closes them all. Launches are queued in the
+// order they were opened, at a cut and at the end alike, so a launch's number is its place in `launches`.
+namespace {
+struct GroupRange {
+  uintptr_t beg, end;
+};
+struct GroupWork {  // a checked work with nElts > 0
+  int index;        // in works[]
+  int coll, key;
+  int dt, op;       // the dispatch, after the semantics
+  int root, isMin;
+  int nFold, shift, preOp, postOp;
+  uint64_t regionBytes, redArg, items;
+  std::vector<GroupRange> rd, wr;
+};
+struct GroupLaunch {
+  int key;
+  std::vector<int> members;  // indices into the GroupWork list, in call order
+  int maxOut = 0;            // copies: the longest destination list
+  uint64_t nParts = 0, items = 0, tableBytes = 0;
+  unsigned grid = 0;
+  int fills = 0;
+};
+constexpr int kGroupCopyKey = -1;
+
+bool groupHit(const std::vector<GroupRange>& a, const std::vector<GroupRange>& b) {
+  for (const GroupRange& x : a)
+    for (const GroupRange& y : b)
+      if (x.beg < y.end && y.beg < x.end) return true;
+  return false;
+}
+bool groupConflict(const GroupWork& a, const GroupWork& b) {
+  return groupHit(a.wr, b.rd) || groupHit(a.wr, b.wr) || groupHit(b.wr, a.rd);
+}
+
+nexrResult_t groupPlan(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst, int maxWorkgroups,
+                       int* launchOf, nexrFlatGroupInfo* info, std::vector<GroupWork>* gwp,
+                       std::vector<GroupLaunch>* lp) {
+  std::vector<GroupWork>& gw = *gwp;
+  std::vector<GroupLaunch>& launches = *lp;
+  if (!works || nWorks < 0 || maxWorkgroups < 0) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  std::vector<int> placed((size_t)nWorks, -1);  // work -> its GroupWork
+  FlatParams p;
+  for (int i = 0; i < nWorks; i++) {
+    const nexrFlatGroupWork& w = works[i];
+    GroupWork g;
+    g.index = i;
+    g.coll = w.coll;
+    g.root = 0;
+    g.isMin = 0;
+    g.dt = g.op = 0;
+    g.nFold = g.shift = g.preOp = g.postOp = 0;
+    g.redArg = w.redOpArg;
+    nexrResult_t res = nexrSuccess;
+    if (w.coll == NEXR_FLAT_GROUP_COPY) {
+      if (!w.inputs || !w.inputs[0] || !w.outputs) return nexrInvalidArgument;
+      if (w.nOutputs < 1 || w.nOutputs > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+      for (int r = 0; r < w.nOutputs; r++)
+        if (!w.outputs[r]) return nexrInvalidArgument;
+      g.key = kGroupCopyKey;
+      g.regionBytes = w.nElts;
+      g.items = ((uint64_t)w.nElts + 2047) / 2048;
+      if (w.nElts) {
+        const uintptr_t src = (uintptr_t)w.inputs[0];
+        g.rd.push_back({src, src + w.nElts});
+        for (int r = 0; r < w.nOutputs; r++)
+          if ((uintptr_t)w.outputs[r] != src) g.wr.push_back({(uintptr_t)w.outputs[r], (uintptr_t)w.outputs[r] + w.nElts});
+      }
+    } else {
+      if (w.coll == NEXR_FLAT_GROUP_ALL_REDUCE) {
+        res = flatAllReduceCheck(nRanks, w.inputs, w.outputs, w.nElts, w.datatype, w.devRedOp, w.redOpArg, userFirst,
+                                 w.parts, w.nParts, &p, &g.dt, &g.op);
+      } else if (w.coll == NEXR_FLAT_GROUP_REDUCE_SCATTER) {
+        res = flatReduceScatterCheck(nRanks, w.inputs, w.outputs, w.nElts, w.datatype, w.devRedOp, w.redOpArg,
+                                     userFirst, &p, &g.dt, &g.op);
+      } else if (w.coll == NEXR_FLAT_GROUP_REDUCE) {
+        if (!w.outputs || w.root < 0 || w.root >= nRanks) return nexrInvalidArgument;
+        res = flatReduceCheck(nRanks, w.inputs, w.outputs[w.root], w.root, w.nElts, w.datatype, w.devRedOp,
+                              w.redOpArg, userFirst, &p, &g.dt, &g.op);
+      } else {
+        return nexrInvalidArgument;
+      }
+      if (res != nexrSuccess) return res;
+      const bool minMax = w.devRedOp == nexrDevMinMax;
+      g.isMin = minMax && (w.redOpArg & 1) == 0;
+      g.key = w.datatype << 8 | w.devRedOp << 1 | (minMax ? (int)(w.redOpArg & 1) : 0);
+      g.root = p.root;
+      g.nFold = p.nFold;
+      g.shift = p.shift;
+      g.preOp = p.preOp;
+      g.postOp = p.postOp;
+      g.regionBytes = p.regionBytes;
+      const int nRegions = w.coll == NEXR_FLAT_GROUP_REDUCE_SCATTER ? nRanks : 1;
+      g.items = (p.regionBytes + 2047) / 2048 * (uint64_t)nRegions;
+      const uint64_t inBytes = p.regionBytes * (uint64_t)nRegions;
+      for (int r = 0; r < nRanks && w.nElts; r++) {
+        g.rd.push_back({(uintptr_t)w.inputs[r], (uintptr_t)w.inputs[r] + inBytes});
+        if (w.coll != NEXR_FLAT_GROUP_REDUCE || r == w.root)
+          g.wr.push_back({(uintptr_t)w.outputs[r], (uintptr_t)w.outputs[r] + p.regionBytes});
+      }
+    }
+    if (w.nElts == 0 || g.wr.empty()) continue;  // nothing to do: no launch, launchOf -1
+    placed[i] = (int)gw.size();
+    gw.push_back(std::move(g));
+  }
+
+  std::vector<int> open;         // open launches, in the order they were opened
+  int cuts = 0;
+  std::vector<int> launchOfGw(gw.size(), -1);
+  for (size_t k = 0; k < gw.size(); k++) {
+    bool cut = false;
+    for (size_t o = 0; o < open.size() && !cut; o++)
+      for (int m : launches[open[o]].members)
+        if (groupConflict(gw[m], gw[k])) {
+          cut = true;
+          break;
+        }
+    if (cut) {
+      open.clear();
+      cuts++;
+    }
+    int at = -1;
+    for (int o : open)
+      if (launches[o].key == gw[k].key) at = o;
+    if (at < 0) {
+      at = (int)launches.size();
+      launches.emplace_back();
+      launches[at].key = gw[k].key;
+      open.push_back(at);
+    }
+    GroupLaunch& L = launches[at];
+    L.members.push_back((int)k);
+    L.items += gw[k].items;
+    const nexrFlatGroupWork& w = works[gw[k].index];
+    if (gw[k].key == kGroupCopyKey) L.maxOut = std::max(L.maxOut, w.nOutputs);
+    else if (gw[k].coll == NEXR_FLAT_GROUP_ALL_REDUCE) L.nParts += (uint64_t)w.nParts;
+    launchOfGw[k] = at;
+  }
+
+  nexrFlatGroupInfo inf;
+  memset(&inf, 0, sizeof(inf));
+  inf.works = (int)gw.size();
+  inf.launches = (int)launches.size();
+  inf.cuts = cuts;
+  for (GroupLaunch& L : launches) {
+    const uint64_t W = L.members.size();
+    L.tableBytes = L.key == kGroupCopyKey
+                       ? W * (kFlatGroupCopyRecBytes + 8ull * (uint64_t)L.maxOut)
+                       : W * (kFlatGroupRecBytes + 16ull * (uint64_t)nRanks) + L.nParts * sizeof(nexrFlatPart);
+    if (L.tableBytes > 0xffffffffull) return nexrInvalidArgument;  // the pool's offset is 32 bits
+    L.fills = L.tableBytes <= (uint64_t)kFlatGroupInlineBytes
+                  ? 0
+                  : (int)((L.tableBytes / 8 + kFlatGroupFillWords - 1) / kFlatGroupFillWords);
+    uint64_t grid = std::min<uint64_t>((L.items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+    if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
+    L.grid = (unsigned)grid;
+    inf.fillLaunches += L.fills;
+    inf.tableBytes += L.tableBytes;
+    inf.workgroups += grid;
+  }
+  if (launchOf)
+    for (int i = 0; i < nWorks; i++) launchOf[i] = placed[i] < 0 ? -1 : launchOfGw[placed[i]];
+  if (info) *info = inf;
+  return nexrSuccess;
+}
+
+// The table of one launch, as nexr_internal.h lays it out.
+void groupTable(const GroupLaunch& L, const std::vector<GroupWork>& gw, const nexrFlatGroupWork* works, int nRanks,
+                std::vector<uint64_t>* tp, uint32_t* poolAt) {
+  std::vector<uint64_t>& t = *tp;
+  t.assign(L.tableBytes / 8, 0);
+  uint64_t items = 0;
+  if (L.key == kGroupCopyKey) {
+    const size_t stride = (kFlatGroupCopyRecBytes + 8u * (size_t)L.maxOut) / 8;
+    for (size_t k = 0; k < L.members.size(); k++) {
+      const GroupWork& g = gw[L.members[k]];
+      const nexrFlatGroupWork& w = works[g.index];
+      uint64_t* rec = t.data() + k * stride;
+      items += g.items;
+      rec[0] = items;
+      rec[1] = g.regionBytes;
+      rec[2] = (uint64_t)(uintptr_t)w.inputs[0];
+      for (int r = 0; r < w.nOutputs; r++) rec[3 + r] = w.outputs[r] == w.inputs[0] ? 0 : (uint64_t)(uintptr_t)w.outputs[r];
+    }
+    *poolAt = 0;
+    return;
+  }
+  const size_t stride = (kFlatGroupRecBytes + 16u * (size_t)nRanks) / 8;
+  const size_t pool = L.members.size() * stride;
+  *poolAt = (uint32_t)(pool * 8);
+  uint32_t partsAt = 0;
+  for (size_t k = 0; k < L.members.size(); k++) {
+    const GroupWork& g = gw[L.members[k]];
+    const nexrFlatGroupWork& w = works[g.index];
+    uint64_t* rec = t.data() + k * stride;
+    items += g.items;
+    const uint32_t nParts = g.coll == NEXR_FLAT_GROUP_ALL_REDUCE ? (uint32_t)w.nParts : 0u;
+    rec[0] = items;
+    rec[1] = g.regionBytes;
+    rec[2] = g.redArg;
+    rec[3] = (uint64_t)(uint32_t)g.coll | (uint64_t)(uint32_t)g.root << 32;
+    rec[4] = (uint64_t)nParts | (uint64_t)partsAt << 32;
+    for (int r = 0; r < nRanks; r++) {
+      rec[5 + r] = (uint64_t)(uintptr_t)w.inputs[r];
+      if (g.coll != NEXR_FLAT_GROUP_REDUCE || r == g.root) rec[5 + nRanks + r] = (uint64_t)(uintptr_t)w.outputs[r];
+    }
+    if (nParts) memcpy(t.data() + pool + (size_t)partsAt * 3, w.parts, (size_t)nParts * sizeof(nexrFlatPart));
+    partsAt += nParts;
+  }
+}
+static_assert(sizeof(nexrFlatPart) == 24, "the pool's entries are three words");
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatGroupPlan(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst,
+                                        int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info) {
+  std::vector<GroupWork> gw;
+  std::vector<GroupLaunch> launches;
+  return groupPlan(nRanks, works, nWorks, userFirst, maxWorkgroups, launchOf, info, &gw, &launches);
+}
+
+NEXR_API nexrResult_t nexrFlatGroup(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst,
+                                    int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info, nexrStream_t stream) {
+  std::vector<GroupWork> gw;
+  std::vector<GroupLaunch> launches;
+  const nexrResult_t res = groupPlan(nRanks, works, nWorks, userFirst, maxWorkgroups, launchOf, info, &gw, &launches);
+  if (res != nexrSuccess) return res;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<uint64_t> table;
+  for (const GroupLaunch& L : launches) {
+    uint32_t poolAt = 0;
+    groupTable(L, gw, works, nRanks, &table, &poolAt);
+    uint64_t* ws = nullptr;
+    if (L.fills) {  // the table by value in short launches ahead of the one: nothing is read after return
+      NEXR_HIP(hipMallocAsync((void**)&ws, L.tableBytes, s));
+      FlatGroupFill f;
+      for (size_t at = 0; at < table.size(); at += kFlatGroupFillWords) {
+        f.dst = ws + at;
+        f.n = (int)std::min<size_t>(kFlatGroupFillWords, table.size() - at);
+        f.pad = 0;
+        memcpy(f.words, table.data() + at, (size_t)f.n * 8);
+        const hipError_t e = launch_flat_group_fill(f, s);
+        if (e != hipSuccess) {
+          (void)hipFreeAsync(ws, s);
+          return hipFail(e);
+        }
+      }
+    }
+    hipError_t e;
+    if (L.key == kGroupCopyKey) {
+      FlatGroupCopyParams p;
+      memset((void*)&p, 0, sizeof(p));
+      p.ext = (const char*)ws;
+      p.nItems = L.items;
+      p.nWorks = (int)L.members.size();
+      p.maxOut = L.maxOut;
+      if (!ws) memcpy(p.inl, table.data(), L.tableBytes);
+      e = launch_flat_group_copy(p, L.grid, s);
+    } else {
+      const GroupWork& g0 = gw[L.members[0]];
+      FlatGroupParams p;
+      memset((void*)&p, 0, sizeof(p));
+      p.ext = (const char*)ws;
+      p.nItems = L.items;
+      p.nWorks = (int)L.members.size();
+      p.nRanks = nRanks;
+      p.nFold = g0.nFold;
+      p.shift = g0.shift;
+      p.userFirst = userFirst ? 1 : 0;
+      p.preOp = g0.preOp;
+      p.postOp = g0.postOp;
+      p.isMin = g0.isMin;
+      p.poolAt = poolAt;
+      if (!ws) memcpy(p.inl, table.data(), L.tableBytes);
+      e = launch_flat_group(g0.dt, g0.op, p, L.grid, s);
+    }
+    if (ws) (void)hipFreeAsync(ws, s);
+    NEXR_HIP(e);
+  }
+  return nexrSuccess;
+}
+
 // ---- nexrFlatHost*: the flat entries over host memory -------------------------------------------------------
 // The device entries' checks, then one helper for all six (flatHostRun). Every DISTINCT (address, length) among
 // the call's buffers is classified once, as nexrReduceCopyHost classifies a buffer: the registration cache

@@ -222,6 +222,19 @@ struct nexrRingComm {
   };
   std::vector<UserRedOp> userRedOps;
   int userRedOpFreeHead = 0;
+  // nexrRingGroupStart / nexrRingGroupEnd: the depth, the calls recorded while it is above 0 (the entry, its
+  // scalars and copies of its pointer arrays), whether the End is running them, and nexrRingGroupGetStats' counters.
+  struct GroupCall {
+    int entry = 0;
+    std::vector<const void*> send;
+    std::vector<void*> recv;
+    size_t count = 0;
+    int datatype = 0, op = 0, root = 0, nBlocks = 0;
+  };
+  int groupDepth = 0;
+  bool groupRunning = false;
+  std::vector<GroupCall> groupCalls;
+  nexrRingGroupStats groupStats{0, 0, 0, 0, 0};
   void* groupWs = nullptr;
   size_t groupWsBytes = 0;
   int groupWsDevice = 0;

@@ -222,7 +222,12 @@ __device__ __forceinline__ void flat_run(const PT& P) {
   const uint64_t nWaves = (uint64_t)gridDim.x * (kBlock / 64);
   const uint32_t shift = (uint32_t)P.shift;
   const uint32_t nOut = coll == kFlatAllReduce ? (uint32_t)P.nOut : 1u;
-  for (uint64_t it = (uint64_t)blockIdx.x * (kBlock / 64) + wave; it < nItems; it += nWaves) {
+  uint64_t it0 = (uint64_t)blockIdx.x * (kBlock / 64) + wave, itEnd = nItems;
+  if constexpr (PT::kOneItem) {  // flat_group_run (nexr_flat_group.hip): the wave's one item of the work P views
+    it0 = P.item;
+    itEnd = P.item + 1;
+  }
+  for (uint64_t it = it0; it < itEnd; it += nWaves) {
     uint64_t k = it;
     uint32_t d = 0;
     if (nRegions > 1) sym_split(it, nRegions, &k, &d);  // region fastest: few waves still touch every chunk

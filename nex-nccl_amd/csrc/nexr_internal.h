@@ -257,6 +257,7 @@ enum { kFlatAllReduce = 0, kFlatReduceScatter = 1, kFlatReduce = 2 };
 constexpr int kFlatInlineParts = NEXR_FLAT_INLINE_PARTS;
 struct FlatParams {
   static constexpr bool kPerRank = false;  // one pre-op factor for the call: redArg
+  static constexpr bool kOneItem = false;  // a launch of its own: the grid strides over every item
   const char* in[NEXR_SYM_MAX_RANKS];
   char* out[NEXR_SYM_MAX_RANKS];  // the reduce: out[root] only
   uint64_t regionBytes;
@@ -279,6 +280,7 @@ static_assert(sizeof(FlatParams) <= 4000, "kernel argument block");
 constexpr int kFlatPreMulInlineParts = NEXR_FLAT_PREMUL_INLINE_PARTS;
 struct FlatPreMulParams {
   static constexpr bool kPerRank = true;
+  static constexpr bool kOneItem = false;
   const char* in[NEXR_SYM_MAX_RANKS];
   char* out[NEXR_SYM_MAX_RANKS];
   uint64_t scalars[NEXR_SYM_MAX_RANKS];
@@ -363,6 +365,49 @@ struct FlatBcastParams {
 hipError_t launch_flat_tree(int dt, int op, const FlatTreeParams& p, unsigned grid, hipStream_t s);
 hipError_t launch_flat_tree_parts(const FlatTreePartsFill& f, hipStream_t s);
 hipError_t launch_flat_bcast(const FlatBcastParams& p, unsigned grid, hipStream_t s);
+
+// Several flat collectives in one launch (nexrFlatGroup; nexr_flat_group.hip). A launch runs a table of works
+// of one (datatype, device op, min-or-max): nWorks records of kFlatGroupRecBytes + 16 * nRanks bytes,
+//   +0 itemEnd (the launch's items up to and including this work: its pieces, times nRanks for a reduce-scatter)
+//   +8 regionBytes  +16 redArg  +24 coll  +28 root  +32 nParts  +36 partsAt (first part's index in the pool)
+//   +40 in[nRanks]  then out[nRanks]
+// then, at byte poolAt, the pool of the all-reduces' nexrFlatPart. The table rides in inl[] or, beyond it, in a
+// stream-ordered workspace (`ext`) that flat_group_fill_kernel launches fill by value ahead of the launch. What
+// the semantics make of the call (nFold, shift, preOp, postOp) holds for the whole launch.
+constexpr int kFlatGroupInlineBytes = NEXR_FLAT_GROUP_INLINE_BYTES;
+constexpr uint32_t kFlatGroupRecBytes = 40;
+struct FlatGroupParams {
+  const char* ext;  // non-null: the table is there, not in inl[]
+  uint64_t nItems;
+  int nWorks, nRanks;
+  int nFold, shift, userFirst, preOp, postOp;  // as FlatParams'
+  int isMin;                                   // nexrDevMinMax: the launch's direction
+  uint32_t poolAt;
+  int pad;
+  char inl[kFlatGroupInlineBytes];
+};
+static_assert(sizeof(FlatGroupParams) <= 4000 && offsetof(FlatGroupParams, inl) % 8 == 0, "kernel argument block");
+// Copies: records of kFlatGroupCopyRecBytes + 8 * maxOut bytes, {itemEnd, nBytes, src, dst[maxOut]}; a null
+// destination is not written.
+constexpr uint32_t kFlatGroupCopyRecBytes = 24;
+struct FlatGroupCopyParams {
+  const char* ext;
+  uint64_t nItems;
+  int nWorks, maxOut;
+  char inl[kFlatGroupInlineBytes];
+};
+static_assert(sizeof(FlatGroupCopyParams) <= 4000 && offsetof(FlatGroupCopyParams, inl) % 8 == 0,
+              "kernel argument block");
+constexpr int kFlatGroupFillWords = NEXR_FLAT_GROUP_FILL_BYTES / 8;
+struct FlatGroupFill {
+  uint64_t* dst;
+  int n, pad;
+  uint64_t words[kFlatGroupFillWords];
+};
+static_assert(sizeof(FlatGroupFill) <= 4000, "kernel argument block");
+hipError_t launch_flat_group(int dt, int op, const FlatGroupParams& p, unsigned grid, hipStream_t s);
+hipError_t launch_flat_group_copy(const FlatGroupCopyParams& p, unsigned grid, hipStream_t s);
+hipError_t launch_flat_group_fill(const FlatGroupFill& f, hipStream_t s);
 
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit

@@ -1198,3 +1198,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 // The ring collectives in one launch with the ring's bytes: the same code object again.
 #include "nexr_flat.hip"
 #include "nexr_flat_tree.hip"
+// Several of them in one launch (nexrFlatGroup): the same code object again.
+#include "nexr_flat_group.hip"

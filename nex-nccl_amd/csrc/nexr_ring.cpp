@@ -1251,6 +1251,8 @@ bool flatReadsResident(const nexrRingComm* c) {
   return !c || c->cfg.memMode != nexrRingDeviceMemory || c->cfg.nRanks == 1;
 }
 
+nexrResult_t symWait(nexrRingComm* c, hipStream_t stream);
+
 template <typename Launch>
 nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
                            int datatype, Launch launch, const nexrDevRedOpFull* oneRankOp = nullptr,
@@ -1276,6 +1278,12 @@ nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* 
   hipStream_t stream = c->streams[0];
   nexrResult_t r = launch(n, (nexrStream_t)stream);
   if (r != nexrSuccess || host) return r;  // a host form returns with its outputs complete
+  return symWait(c, stream);
+}
+
+// The completion wait of a launch queued on the communicator's first stream: the step-completion word where the
+// communicator waits that way, else the stream.
+nexrResult_t symWait(nexrRingComm* c, hipStream_t stream) {
   uint32_t* done = c->stepWaitWord && !c->done.empty() ? c->done[0] : nullptr;
   if (done) {
     const int timeoutMs = c->cfg.timeoutMs > 0 ? c->cfg.timeoutMs : 60000;
@@ -1621,6 +1629,306 @@ nexrResult_t symLLAllGather(nexrRingComm* c, const void* const* sendbuffs, void*
                          });
 }
 
+// ---- nexrRingGroupStart / nexrRingGroupEnd --------------------------------------------------------------------
+// Every collective entry of include/nexr_ring.h by number: what a recorded call remembers, and what runEntry runs.
+enum RingEntry {
+  kEntAllReduce, kEntReduceScatter, kEntAllGather, kEntReduce, kEntBroadcast, kEntTree,
+  kEntSymAllReduce, kEntSymReduceScatter, kEntSymAllGather,
+  kEntFlatAllReduce, kEntFlatReduceScatter, kEntFlatReduce, kEntFlatTree, kEntFlatBroadcast, kEntFlatAllGather,
+  kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather
+};
+
+// The entry as it runs alone.
+nexrResult_t runEntry(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                      int datatype, int op, int root, int nBlocks) {
+  const bool dev = c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory;
+  const bool flatDev = c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c));
+  switch (entry) {
+    case kEntAllReduce: {
+      DeviceGuard dg(c && c->needHip);
+      return ringOrFlat(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+    }
+    case kEntReduceScatter: {
+      DeviceGuard dg(c && c->needHip);
+      return ringOrFlat(c, kReduceScatter, sendbuffs, recvbuffs, count, datatype, op, 0);
+    }
+    case kEntAllGather: {
+      DeviceGuard dg(c && c->needHip);
+      return copyOrFlat(c, kAllGather, sendbuffs, recvbuffs, count, datatype, 0);  // ncclAllGather: ncclSum
+    }
+    case kEntReduce: {
+      DeviceGuard dg(c && c->needHip);
+      return ringOrFlat(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+    }
+    case kEntBroadcast: {
+      DeviceGuard dg(c && c->needHip);
+      return copyOrFlat(c, kBroadcast, sendbuffs, recvbuffs, count, datatype, root);  // ncclBroadcast: ncclSum
+    }
+    case kEntTree: {
+      DeviceGuard dg(c && c->needHip);
+      return treeOrFlat(c, sendbuffs, recvbuffs, count, datatype, op);
+    }
+    case kEntSymAllReduce: {
+      DeviceGuard dg(dev);
+      return symAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+    }
+    case kEntSymReduceScatter: {
+      DeviceGuard dg(dev);
+      return symReduceScatter(c, sendbuffs, recvbuffs, count, datatype, op);
+    }
+    case kEntSymAllGather: {
+      DeviceGuard dg(dev);
+      return symAllGather(c, sendbuffs, recvbuffs, count, datatype);
+    }
+    case kEntFlatAllReduce: {
+      DeviceGuard dg(flatDev);
+      return flatCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+    }
+    case kEntFlatReduceScatter: {
+      DeviceGuard dg(flatDev);
+      return flatCollective(c, kReduceScatter, sendbuffs, recvbuffs, count, datatype, op, 0);
+    }
+    case kEntFlatReduce: {
+      DeviceGuard dg(flatDev);
+      return flatCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+    }
+    case kEntFlatTree: {
+      DeviceGuard dg(flatDev);
+      return flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+    }
+    case kEntFlatBroadcast: {
+      DeviceGuard dg(flatDev);
+      return flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
+    }
+    case kEntFlatAllGather: {
+      DeviceGuard dg(flatDev);
+      return flatAllGather(c, sendbuffs, recvbuffs, count, datatype);
+    }
+    case kEntSymLLAllReduce: {
+      DeviceGuard dg(dev);
+      return symLLAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+    }
+    case kEntSymLLReduceScatter: {
+      DeviceGuard dg(dev);
+      return symLLReduceScatter(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+    }
+    case kEntSymLLAllGather: {
+      DeviceGuard dg(dev);
+      return symLLAllGather(c, sendbuffs, recvbuffs, count, datatype, nBlocks);
+    }
+  }
+  return nexrInvalidArgument;
+}
+
+bool entryReduces(int e) {
+  return e != kEntAllGather && e != kEntBroadcast && e != kEntSymAllGather && e != kEntFlatBroadcast &&
+         e != kEntFlatAllGather && e != kEntSymLLAllGather;
+}
+bool entryIsReduce(int e) { return e == kEntReduce || e == kEntFlatReduce; }
+bool entryIsBroadcast(int e) { return e == kEntBroadcast || e == kEntFlatBroadcast; }
+// The explicit entries that answer nexrInvalidUsage on a communicator they do not serve.
+bool entryNeedsOneGpu(int e) { return e >= kEntSymAllReduce; }
+
+// A call inside a group: the checks that need no execution, then the record. A call that fails is not recorded.
+nexrResult_t groupRecord(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs,
+                         size_t count, int datatype, int op, int root, int nBlocks) {
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  const int n = c->cfg.nRanks;
+  size_t esz = 0;
+  if (entryReduces(entry)) {
+    RedOps ops;
+    const nexrResult_t r = prepareOps(c, datatype, op, &esz, &ops, false);
+    if (r != nexrSuccess) return r;
+  } else {
+    nexrDevRedOpFull red;
+    const nexrResult_t r = prepare(c, datatype, nexrSum, &esz, &red);
+    if (r != nexrSuccess) return r;
+  }
+  if ((entryIsReduce(entry) || entryIsBroadcast(entry)) && (root < 0 || root >= n)) return nexrInvalidArgument;
+  if (nBlocks < 0 || nBlocks > 64) return nexrInvalidArgument;
+  if (count > (size_t)-1 / esz / (size_t)n) return nexrInvalidArgument;
+  if (entryNeedsOneGpu(entry)) {
+    const bool host = entry >= kEntFlatAllReduce && entry <= kEntFlatAllGather && flatHostEligible(c);
+    if ((c->cfg.memMode != nexrRingDeviceMemory && !host) || (int)c->devices.size() < n || c->streams.empty() ||
+        !c->streams[0])
+      return nexrInvalidUsage;
+    for (int i = 0; i < n && !host; i++)
+      if (c->devices[i] != c->devices[0]) return nexrInvalidUsage;
+    if (n > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  }
+  for (int i = 0; i < n && count != 0; i++) {
+    const bool needSend = !entryIsBroadcast(entry) || i == root;
+    const bool needRecv = !entryIsReduce(entry) || i == root;
+    if ((needSend && !sendbuffs[i]) || (needRecv && !recvbuffs[i])) return nexrInvalidArgument;
+  }
+  nexrRingComm::GroupCall g;
+  g.entry = entry;
+  g.send.assign(sendbuffs, sendbuffs + n);
+  g.recv.assign(recvbuffs, recvbuffs + n);
+  g.count = count;
+  g.datatype = datatype;
+  g.op = op;
+  g.root = root;
+  g.nBlocks = nBlocks;
+  c->groupCalls.push_back(std::move(g));
+  c->groupStats.calls++;
+  return nexrSuccess;
+}
+
+nexrResult_t groupOrRun(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                        int datatype, int op, int root, int nBlocks) {
+  if (c && c->groupDepth > 0 && !c->groupRunning)
+    return groupRecord(c, entry, sendbuffs, recvbuffs, count, datatype, op, root, nBlocks);
+  return runEntry(c, entry, sendbuffs, recvbuffs, count, datatype, op, root, nBlocks);
+}
+
+// Whether a recorded call becomes work records: it would run flat, as a ring all-reduce, reduce-scatter, reduce,
+// all-gather or broadcast, on a device-memory communicator of 2+ ranks on one GPU, with one redOpArg.
+bool groupTakes(nexrRingComm* c, const nexrRingComm::GroupCall& g, RedOps* ops, size_t* esz) {
+  const int n = c->cfg.nRanks;
+  if (c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || n < 2 || n > NEXR_SYM_MAX_RANKS ||
+      (int)c->devices.size() < n || c->streams.empty() || !c->streams[0])
+    return false;
+  for (int i = 0; i < n; i++)
+    if (c->devices[i] != c->devices[0]) return false;
+  switch (g.entry) {
+    case kEntAllReduce: case kEntReduceScatter: case kEntReduce:
+      if (!flatRouted(c, NEXR_FLAT_RING)) return false;
+      break;
+    case kEntAllGather: case kEntBroadcast:
+      if (!flatRouted(c, NEXR_FLAT_COPIES)) return false;
+      break;
+    case kEntFlatAllReduce: case kEntFlatReduceScatter: case kEntFlatReduce: case kEntFlatBroadcast:
+    case kEntFlatAllGather:
+      break;
+    default:
+      return false;
+  }
+  if (!entryReduces(g.entry)) {
+    *esz = nexrTypeSize(g.datatype);
+    return true;
+  }
+  if (prepareOps(c, g.datatype, g.op, esz, ops, false) != nexrSuccess) return false;  // alone, it reports
+  return !ops->perRank(false);
+}
+
+// One run of consecutive calls that groupTakes, as ONE nexrFlatGroup call.
+struct GroupRun {
+  std::vector<nexrFlatGroupWork> works;
+  std::deque<std::vector<const void*>> ins;
+  std::deque<std::vector<void*>> outs;
+  std::deque<std::vector<nexrFlatPart>> parts;
+};
+
+void groupAdd(nexrRingComm* c, const nexrRingComm::GroupCall& g, const RedOps& ops, size_t esz, GroupRun* run) {
+  const int n = c->cfg.nRanks;
+  if (g.count == 0) return;
+  nexrFlatGroupWork w;
+  memset(&w, 0, sizeof(w));
+  if (g.entry == kEntAllGather || g.entry == kEntFlatAllGather) {  // n copies: rank r's input to chunk r of every output
+    for (int r = 0; r < n; r++) {
+      run->ins.emplace_back(1, g.send[r]);
+      run->outs.emplace_back();
+      for (int s = 0; s < n; s++) run->outs.back().push_back((char*)g.recv[s] + (size_t)r * g.count * esz);
+      w.coll = NEXR_FLAT_GROUP_COPY;
+      w.inputs = run->ins.back().data();
+      w.outputs = run->outs.back().data();
+      w.nOutputs = n;
+      w.nElts = g.count * esz;
+      run->works.push_back(w);
+    }
+    return;
+  }
+  if (entryIsBroadcast(g.entry)) {
+    run->ins.emplace_back(1, g.send[g.root]);
+    run->outs.emplace_back(g.recv);
+    w.coll = NEXR_FLAT_GROUP_COPY;
+    w.inputs = run->ins.back().data();
+    w.outputs = run->outs.back().data();
+    w.nOutputs = n;
+    w.nElts = g.count * esz;
+    run->works.push_back(w);
+    return;
+  }
+  const nexrDevRedOpFull& red = ops.rank[0];
+  run->ins.emplace_back(g.send);
+  run->outs.emplace_back(g.recv);
+  w.datatype = g.datatype;
+  w.devRedOp = red.op;
+  w.redOpArg = red.scalarArg;
+  w.root = g.root;
+  w.inputs = run->ins.back().data();
+  w.outputs = run->outs.back().data();
+  w.nElts = g.count;
+  if (g.entry == kEntReduce || g.entry == kEntFlatReduce) {
+    w.coll = NEXR_FLAT_GROUP_REDUCE;
+  } else if (g.entry == kEntReduceScatter || g.entry == kEntFlatReduceScatter) {
+    w.coll = NEXR_FLAT_GROUP_REDUCE_SCATTER;
+  } else {  // the channel parts the call has alone (flatCollective)
+    w.coll = NEXR_FLAT_GROUP_ALL_REDUCE;
+    run->parts.emplace_back();
+    for (const ChannelPart& part : channelParts(c, (int64_t)g.count, esz, /*ncclFuncAllReduce*/ 2))
+      run->parts.back().push_back({(uint64_t)part.offset, (uint64_t)part.count,
+                                   (uint64_t)chunkElems(channelComm(c, part.channel), kGeomRing, esz, false, 0)});
+    w.parts = run->parts.back().data();
+    w.nParts = (int)run->parts.back().size();
+  }
+  run->works.push_back(w);
+}
+
+// The outermost End: the recorded calls in order, runs of flat works as group launches on the first stream, every
+// other call alone at its place (behind a wait for what was queued), and one wait at the end.
+nexrResult_t groupExecute(nexrRingComm* c) {
+  std::vector<nexrRingComm::GroupCall> calls;
+  calls.swap(c->groupCalls);
+  c->groupRunning = true;
+  GroupRun run;
+  bool pending = false, queued = false;
+  nexrResult_t res = nexrSuccess;
+  hipStream_t stream = c->streams.empty() ? nullptr : c->streams[0];
+  auto flush = [&]() -> nexrResult_t {
+    if (run.works.empty()) return nexrSuccess;
+    DeviceGuard dg(true);
+    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+    nexrFlatGroupInfo info;
+    const nexrResult_t r = nexrFlatGroup(c->cfg.nRanks, run.works.data(), (int)run.works.size(),
+                                         c->proto == nexrRingProtoSimple ? 1 : 0, 0, nullptr, &info, (nexrStream_t)stream);
+    run = GroupRun();
+    if (r != nexrSuccess) return r;
+    c->groupStats.groupLaunches += (uint64_t)info.launches;
+    c->groupStats.fillLaunches += (uint64_t)info.fillLaunches;
+    c->groupStats.cuts += (uint64_t)info.cuts;
+    if (info.launches) pending = queued = true;
+    return nexrSuccess;
+  };
+  auto wait = [&]() -> nexrResult_t {
+    if (!pending) return nexrSuccess;
+    pending = false;
+    DeviceGuard dg(true);
+    return symWait(c, stream);
+  };
+  for (const nexrRingComm::GroupCall& g : calls) {
+    RedOps ops;
+    size_t esz = 0;
+    if (groupTakes(c, g, &ops, &esz)) {
+      groupAdd(c, g, ops, esz, &run);
+      continue;
+    }
+    res = flush();
+    if (res == nexrSuccess) res = wait();
+    if (res != nexrSuccess) break;
+    c->groupStats.singles++;
+    res = runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
+    if (res != nexrSuccess) break;
+  }
+  if (res == nexrSuccess) res = flush();
+  const nexrResult_t w = wait();  // also behind an error: nothing stays in flight over the caller's buffers
+  if (res == nexrSuccess) res = w;
+  if (queued && res == nexrSuccess) c->lastLLMode = 5;
+  c->groupRunning = false;
+  return res;
+}
+
 // A communicator touches HIP when its FIFOs live in device memory or when any of its steps runs the
 // built-in (HIP) reduce-copy; one whose steps are all caller-supplied (a CPU checker) never does.
 bool needsHip(const nexrRingConfig& cfg) {
@@ -1734,76 +2042,85 @@ NEXR_API nexrResult_t nexrRingCommCreate(nexrRingComm_t* out, const nexrRingConf
 
 NEXR_API nexrResult_t nexrRingAllReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip);
-  return ringOrFlat(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+  return groupOrRun(c, kEntAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatter(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t recvcount, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip);
-  return ringOrFlat(c, kReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0);
+  return groupOrRun(c, kEntReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllGather(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t sendcount, int datatype) {
-  DeviceGuard dg(c && c->needHip);
-  return copyOrFlat(c, kAllGather, sendbuffs, recvbuffs, sendcount, datatype, 0);  // ncclAllGather: ncclSum
+  return groupOrRun(c, kEntAllGather, sendbuffs, recvbuffs, sendcount, datatype, nexrSum, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                      size_t count, int datatype, int op, int root) {
-  DeviceGuard dg(c && c->needHip);
-  return ringOrFlat(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+  return groupOrRun(c, kEntReduce, sendbuffs, recvbuffs, count, datatype, op, root, 0);
 }
 
 NEXR_API nexrResult_t nexrRingBroadcast(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int root) {
-  DeviceGuard dg(c && c->needHip);
-  return copyOrFlat(c, kBroadcast, sendbuffs, recvbuffs, count, datatype, root);  // ncclBroadcast: ncclSum
+  return groupOrRun(c, kEntBroadcast, sendbuffs, recvbuffs, count, datatype, nexrSum, root, 0);
 }
 
 NEXR_API nexrResult_t nexrTreeAllReduce(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         size_t count, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip);
-  return treeOrFlat(c, sendbuffs, recvbuffs, count, datatype, op);
+  return groupOrRun(c, kEntTree, sendbuffs, recvbuffs, count, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
                                                  void* const* recvbuffs, size_t count, int datatype, int op,
                                                  int nBlocks) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+  return groupOrRun(c, kEntSymAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0, nBlocks);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatterSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
                                                      void* const* recvbuffs, size_t recvcount, int datatype,
                                                      int op) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symReduceScatter(c, sendbuffs, recvbuffs, recvcount, datatype, op);
+  return groupOrRun(c, kEntSymReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllGatherSymmetric(nexrRingComm_t c, const void* const* sendbuffs,
                                                  void* const* recvbuffs, size_t sendcount, int datatype) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
+  return groupOrRun(c, kEntSymAllGather, sendbuffs, recvbuffs, sendcount, datatype, nexrSum, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t count, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
-  return flatCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+  return groupOrRun(c, kEntFlatAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t c, const void* const* sendbuffs,
                                                 void* const* recvbuffs, size_t recvcount, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
-  return flatCollective(c, kReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0);
+  return groupOrRun(c, kEntFlatReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                          size_t count, int datatype, int op, int root) {
-  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
-  return flatCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+  return groupOrRun(c, kEntFlatReduce, sendbuffs, recvbuffs, count, datatype, op, root, 0);
+}
+
+NEXR_API nexrResult_t nexrRingGroupStart(nexrRingComm_t c) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer || c->groupRunning) return nexrInvalidUsage;
+  c->groupDepth++;
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrRingGroupEnd(nexrRingComm_t c) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer || c->groupRunning || c->groupDepth == 0) return nexrInvalidUsage;
+  if (--c->groupDepth > 0) return nexrSuccess;
+  return groupExecute(c);
+}
+
+NEXR_API nexrResult_t nexrRingGroupGetStats(nexrRingComm_t c, nexrRingGroupStats* stats, int reset) {
+  if (!c || !stats) return nexrInvalidArgument;
+  *stats = c->groupStats;
+  if (reset) c->groupStats = nexrRingGroupStats{0, 0, 0, 0, 0};
+  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t c, int on) {
@@ -1816,41 +2133,35 @@ NEXR_API nexrResult_t nexrRingCommSetFlat(nexrRingComm_t c, int on) {
 
 NEXR_API nexrResult_t nexrTreeAllReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t count, int datatype, int op) {
-  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
-  return flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+  return groupOrRun(c, kEntFlatTree, sendbuffs, recvbuffs, count, datatype, op, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingBroadcastFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t count, int datatype, int root) {
-  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
-  return flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
+  return groupOrRun(c, kEntFlatBroadcast, sendbuffs, recvbuffs, count, datatype, nexrSum, root, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                             size_t sendcount, int datatype) {
-  DeviceGuard dg(c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c)));
-  return flatAllGather(c, sendbuffs, recvbuffs, sendcount, datatype);
+  return groupOrRun(c, kEntFlatAllGather, sendbuffs, recvbuffs, sendcount, datatype, nexrSum, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingAllReduceSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,
                                                    void* const* recvbuffs, size_t count, int datatype, int op,
                                                    int nBlocks) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symLLAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+  return groupOrRun(c, kEntSymLLAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0, nBlocks);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatterSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,
                                                        void* const* recvbuffs, size_t recvcount, int datatype,
                                                        int op, int nBlocks) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symLLReduceScatter(c, sendbuffs, recvbuffs, recvcount, datatype, op, nBlocks);
+  return groupOrRun(c, kEntSymLLReduceScatter, sendbuffs, recvbuffs, recvcount, datatype, op, 0, nBlocks);
 }
 
 NEXR_API nexrResult_t nexrRingAllGatherSymmetricLL(nexrRingComm_t c, const void* const* sendbuffs,
                                                    void* const* recvbuffs, size_t sendcount, int datatype,
                                                    int nBlocks) {
-  DeviceGuard dg(c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory);
-  return symLLAllGather(c, sendbuffs, recvbuffs, sendcount, datatype, nBlocks);
+  return groupOrRun(c, kEntSymLLAllGather, sendbuffs, recvbuffs, sendcount, datatype, nexrSum, 0, nBlocks);
 }
 
 // ncclRedOpCreatePreMulSum (enqueue.cc:2447-2487) for a communicator that holds all n ranks: scalars[r] is what

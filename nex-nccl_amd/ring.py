@@ -25,6 +25,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
                     "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat",
+                    "nexrRingGroupStart", "nexrRingGroupEnd", "nexrRingGroupGetStats",
                     "nexrTreeTopology", "nexrRingRedOpCreatePreMulSum", "nexrRingRedOpDestroy",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
                     "nexrRingCommSetSimpleGroup", "nexrRingCommSetDirect", "nexrRingCommGetDirect",
@@ -64,6 +65,34 @@ class PeerRingConfig(ctypes.Structure):
                 ("shmName", ctypes.c_char_p)]
 
 
+class RingGroupStats(ctypes.Structure):
+    """nexrRingGroupStats (include/nexr_ring.h)."""
+    _fields_ = [("calls", ctypes.c_uint64), ("groupLaunches", ctypes.c_uint64), ("fillLaunches", ctypes.c_uint64),
+                ("singles", ctypes.c_uint64), ("cuts", ctypes.c_uint64)]
+
+
+class _Group:
+    """RingComm.group(): nexrRingGroupStart on entry, nexrRingGroupEnd on exit (also behind an exception, whose
+    recorded calls then still run: the depth must come down)."""
+
+    def __init__(self, comm):
+        self._comm = comm
+
+    def __enter__(self):
+        self._comm.group_start()
+        return self._comm
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self._comm.group_end()
+        else:
+            try:
+                self._comm.group_end()
+            except NexrError:
+                pass
+        return False
+
+
 _libs = {}
 
 
@@ -91,6 +120,9 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrTreeAllReduceFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingBroadcastFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingAllGatherFlat.argtypes = [vp, arr, arr, sz, i32]
+    L.nexrRingGroupStart.argtypes = [vp]
+    L.nexrRingGroupEnd.argtypes = [vp]
+    L.nexrRingGroupGetStats.argtypes = [vp, ctypes.POINTER(RingGroupStats), i32]
     L.nexrTreeTopology.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.nexrRingRedOpCreatePreMulSum.argtypes = [vp, ctypes.POINTER(i32), arr, i32, i32]
     L.nexrRingRedOpDestroy.argtypes = [vp, i32]
@@ -356,6 +388,30 @@ class RingComm:
         bits = (FLAT_RING if on else 0) | (FLAT_TREE if tree else 0) | (FLAT_COPIES if copies else 0)
         _check(self._L.nexrRingCommSetFlat(self._h, bits), "nexrRingCommSetFlat")
 
+    def group_start(self) -> None:
+        """ncclGroupStart (nexrRingGroupStart): the collectives of this communicator are recorded until the
+        matching group_end. Nests by depth. InvalidUsage for process-rank communicators."""
+        _check(self._L.nexrRingGroupStart(self._h), "nexrRingGroupStart")
+
+    def group_end(self) -> None:
+        """ncclGroupEnd (nexrRingGroupEnd): the outermost one runs the recorded calls, those that would run flat
+        as flat group launches (one launch per kind between two conflicts, one wait), every other one alone at its
+        place; the bytes are those of the calls made one by one. queued() == 5 after an end that queued a group
+        launch. InvalidUsage without a group_start."""
+        _check(self._L.nexrRingGroupEnd(self._h), "nexrRingGroupEnd")
+
+    def group(self) -> "_Group":
+        """``with comm.group(): ...``: group_start / group_end around the block."""
+        return _Group(self)
+
+    def group_stats(self, reset: bool = False) -> dict:
+        """nexrRingGroupGetStats: calls recorded, group launches, fill launches, calls run singly and cuts since
+        creation or the last reset."""
+        st = RingGroupStats()
+        _check(self._L.nexrRingGroupGetStats(self._h, ctypes.byref(st), 1 if reset else 0), "nexrRingGroupGetStats")
+        return {"calls": st.calls, "group_launches": st.groupLaunches, "fill_launches": st.fillLaunches,
+                "singles": st.singles, "cuts": st.cuts}
+
     def create_premul_sum(self, scalars, datatype: int, residence: int = SCALAR_HOST_IMMEDIATE) -> int:
         """ncclRedOpCreatePreMulSum for all ranks at once (nexrRingRedOpCreatePreMulSum): the handle of an op
         under which rank r's own input is multiplied by scalars[r] before the sum. SCALAR_HOST_IMMEDIATE:
@@ -406,7 +462,8 @@ class RingComm:
         return "word" if w.value else "sync"
 
     def queued(self) -> int:
-        """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 4 one flat launch (set_flat),
+        """How the last ring collective ran its LL steps (nexrRingCommGetQueued): 5 flat group launches (a
+        group_end that queued at least one), 4 one flat launch (set_flat),
         3 group launches on
         one stream (set_ll_group; set_simple_group for SIMPLE), 2 runs on the device with device credits, 1 queued launches,
         0 host-sequenced (LL steps need every rank on one GPU and device memory for 1, 2 or 3; 1 and 2
