@@ -465,6 +465,7 @@ def c1_ring(iters: int = 20) -> dict:
             ("cpu_oracle", ring.HOST_MEMORY, cpu_fn, ring.PROTO_SIMPLE))
     nexr = importlib.import_module("nex-nccl_amd")
     for name, mode, fn, proto in legs:
+        owned = []
         if mode == ring.DEVICE_MEMORY:  # rank r's buffers on rank r's GPU (libnexr_ring: r mod visible)
             devs = [torch.device("cuda", r % torch.cuda.device_count()) for r in range(n)]
             send = [torch.from_numpy(v).to(d) for v, d in zip(x, devs)]
@@ -472,6 +473,16 @@ def c1_ring(iters: int = 20) -> dict:
             for d in set(devs):
                 torch.cuda.synchronize(d)
             out["device_gpus"] = [d.index for d in devs]
+        elif name == "host_registered":
+            # the user buffers from nexrHostMemAlloc (the reference's ncclMemAlloc-then-ncclCommRegister pattern):
+            # a runtime that cannot page-lock pages the process already has refuses numpy's own arrays
+            owned = [nexr.host_mem_alloc(4 * count) for _ in range(2 * n)]
+            bufs = [np.ctypeslib.as_array((ctypes.c_float * count).from_address(p)) for p in owned]
+            send, recv = bufs[:n], bufs[n:]
+            for b, v in zip(send, x):
+                b[:] = v
+            for b in recv:
+                b[:] = 0
         else:
             send, recv = [v.copy() for v in x], [np.zeros(count, np.float32) for _ in range(n)]
         sp = [t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data for t in send]
@@ -506,6 +517,8 @@ def c1_ring(iters: int = 20) -> dict:
                 "steps_per_call": round(steps / reps, 2), "zero_copy_steps": hp["zeroCopyCalls"] / steps,
                 "registered_hits": hp["registeredHits"], "pointer_queries": hp["pointerQueries"],
                 **{f"{k}_us": round(hp[k + "Ns"] / steps / 1e3, 2) for k in ("classify", "copy", "launch", "wait")}}
+        for p in owned:  # after the check: `got` are views of them
+            nexr.host_mem_free(p)
         if mode == ring.DEVICE_MEMORY:
             out[name]["step_wait"] = wait  # "word" with both ranks on one GPU, "sync" across GPUs
         if proto == ring.PROTO_LL:

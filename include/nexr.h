@@ -221,7 +221,11 @@ NEXR_API nexrResult_t nexrReduceCopyHost(int nSrcs, const void* const* srcs, int
  *                       (registered, or from nexrHostMemAlloc) shares that entry (one more reference);
  *                       a range that partly overlaps one returns nexrInvalidUsage. Disjoint ranges that
  *                       share a page are separate entries (the runtime maps each; if it refused one,
- *                       nexrInvalidUsage). *handle is an opaque id that is never reused.
+ *                       nexrInvalidUsage). *handle is an opaque id that is never reused. Where the runtime
+ *                       cannot page-lock memory the process already has (hipHostRegister fails, as in some
+ *                       virtual machines) a range outside the cache returns nexrUnhandledCudaError and no
+ *                       HIP error is left behind; there, take the memory from nexrHostMemAlloc (a range
+ *                       inside it registers as above).
  *   nexrHostDeregister  drops one reference; the last one unregisters the range (NULL: no-op). A
  *                       handle with no reference left, or never issued, returns nexrInvalidUsage.
  *   nexrHostMemAlloc    pinned, device-mapped host memory (hipHostMalloc), recorded in the same cache.

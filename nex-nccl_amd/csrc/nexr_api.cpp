@@ -969,8 +969,8 @@ uint16_t floatToBf16Rne(float f) {
 // call on registered memory costs no HIP query per buffer; because the library made every entry, it
 // also knows when one ends (nexrHostDeregister / nexrHostMemFree), so nothing here goes stale.
 // Entries hold exact byte ranges. hipHostRegister pins every page a range touches, and on this ROCm it
-// accepts a second range that shares a page with a registered one (adjacent heap buffers do, e.g. the
-// C1 bench's numpy arrays), giving it a mapping of its own, so such neighbours are separate entries
+// accepts a second range that shares a page with a registered one (adjacent heap buffers do, e.g.
+// numpy arrays), giving it a mapping of its own, so such neighbours are separate entries
 // whose deregistrations are independent (tests/test_host_register_gpu.py); should the runtime refuse
 // one, the call returns nexrInvalidUsage, not a raw HIP error. Handles are monotonic ids, never
 // addresses: a handle whose entry is gone stays invalid even when a later entry lands at the same
@@ -1276,10 +1276,10 @@ NEXR_API nexrResult_t nexrHostRegister(void* buff, size_t size, void** handle) {
   if (overlap) return nexrInvalidUsage;  // partly inside another entry: hipHostRegister would refuse it
   hipError_t e = hipHostRegister(buff, size, hipHostRegisterMapped | hipHostRegisterPortable);
   if (e != hipSuccess) {
-    if (sharesPage) {  // a page-sharing neighbour the runtime refused: the documented usage error
-      (void)hipGetLastError();
-      return nexrInvalidUsage;
-    }
+    // the runtime keeps a refused registration as the thread's last error, and the next kernel launch's check
+    // (the caller's own, e.g. torch's) would report it: it is returned here, so it is cleared
+    (void)hipGetLastError();
+    if (sharesPage) return nexrInvalidUsage;  // a page-sharing neighbour the runtime refused: the documented usage error
     return hipFail(e);
   }
   void* dev = nullptr;

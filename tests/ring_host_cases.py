@@ -9,7 +9,9 @@ multiple of 16 (rm aligns every user buffer to 16 bytes from the arena start). T
 
   pageable    the arena at PAGE + 48 of the mapping; nothing registered.
   registered  the same offset; the whole mapping registered: every user pointer is an interior, non-page-aligned
-              pointer of one cache entry.
+              pointer of one cache entry. Where the runtime cannot page-lock a mapping the process already has, the
+              caller hands in memory of the same size that the library allocated (nexrHostMemAlloc): the arena
+              lies there at the same offset, and that memory is registered whole (it shares the allocation's entry).
   pinned      the arena at PAGE + 48 of memory that the HIP runtime pinned and the library never saw (the caller's,
               e.g. a torch pin_memory() byte tensor of mapping_bytes); nothing registered.
   split       the arena placed so that a cut inside it falls on a page boundary of the mapping, and only [mapping
@@ -90,9 +92,10 @@ def cut_region(call, pl: Placement):
 
 class Mapping:
     """One anonymous mapping, page-aligned. `pinned` is the caller's runtime-pinned memory of at least the same
-    size as a uint8 array (None where the test has no such kind)."""
+    size as a uint8 array (None where the test has no such kind); `registered` is memory of at least the same size
+    in which the registered kind is placed and registered instead of the mapping (None: in the mapping)."""
 
-    def __init__(self, nbytes: int, pinned: Optional[np.ndarray] = None):
+    def __init__(self, nbytes: int, pinned: Optional[np.ndarray] = None, registered: Optional[np.ndarray] = None):
         assert nbytes % PAGE == 0
         self.m = mmap.mmap(-1, nbytes)
         self.buf = np.frombuffer(self.m, dtype=np.uint8)
@@ -100,9 +103,13 @@ class Mapping:
         assert self.base % PAGE == 0
         self.size = nbytes
         self.pinned = pinned
-        assert pinned is None or (pinned.dtype == np.uint8 and pinned.size >= nbytes)
+        self.registered = registered
+        for other in (pinned, registered):
+            assert other is None or (other.dtype == np.uint8 and other.size >= nbytes)
 
     def memory(self, pl: Placement) -> np.ndarray:
+        if pl.kind == "registered" and self.registered is not None:
+            return self.registered
         return self.pinned if pl.kind == "pinned" else self.buf
 
     @contextmanager
@@ -116,7 +123,8 @@ class Mapping:
         mem = self.memory(pl)
         view = mem[pl.offset:pl.offset + arena0.size]
         view[:] = arena0
-        handle = register(self.base, pl.registered) if pl.registered else None
+        reg_base = mem.ctypes.data if pl.kind == "registered" else self.base
+        handle = register(reg_base, pl.registered) if pl.registered else None
         try:
             yield pl, mem.ctypes.data + pl.offset, view
         finally:

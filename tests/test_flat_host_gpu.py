@@ -11,7 +11,10 @@ order-sensitive inputs of flat_cases run against its element-wise model directly
 
 The user buffers are of ring_host_cases.KINDS (pageable, registered, pinned by the runtime, split: registered up
 to a page boundary inside one buffer) and `alloc` (inside one nexrHostMemAlloc allocation), and
-nexrGetFlatHostStats is asserted for each: see expected_stats.
+nexrGetFlatHostStats is asserted for each: see expected_stats. Where the runtime cannot page-lock a mapping the
+process already has, `registered` lies in a nexrHostMemAlloc allocation that is registered whole for the call
+(tests/host_memory_support.py), the tests that need a registration to end inside the arena (split, the mixed
+kinds in one call) skip themselves, and the children leave split out.
 
 SIMPLE, rm.BUFF["simple"], timeoutMs = 20000. A flat launch has no credit, no poll and no residency requirement;
 children get a time limit."""
@@ -26,6 +29,7 @@ import pytest
 
 import arith_edges as ae
 import flat_cases as fc
+import host_memory_support as hm
 import ring_host_cases as rh
 import ring_modes_cases as rm
 from oracle import ring as oring
@@ -60,12 +64,13 @@ def table_calls(n, channels):
     return [rm.make_call(sp, n, SEED, oring, "simple", channels) for sp in rm.plan("simple", n, chunk_of)]
 
 
-_pinned, _alloc = {}, {}
+_pinned = {}
 
 
 def make_mapping(calls, kinds):
     """One mapping for the test; runtime-pinned memory (torch) or a nexrHostMemAlloc allocation of the same size
-    beside it where `kinds` needs one (kept for the module)."""
+    beside it where `kinds` needs one (kept for the process), and the registered kind's memory where that is not
+    the mapping itself."""
     size = rh.mapping_bytes(rh.largest_arena(calls))
     maps = {}
     for kind in kinds:
@@ -75,11 +80,8 @@ def make_mapping(calls, kinds):
                 _pinned[size] = torch.empty(size, dtype=torch.uint8).pin_memory()
             other = _pinned[size].numpy()
         elif kind == "alloc":
-            if size not in _alloc:
-                addr = nexr_mod().host_mem_alloc(size)
-                _alloc[size] = np.ctypeslib.as_array((np.ctypeslib.ctypes.c_uint8 * size).from_address(addr))
-            other = _alloc[size]
-        maps[kind] = rh.Mapping(size, other)
+            other = hm.allocation(size)
+        maps[kind] = rh.Mapping(size, other, hm.registered_memory(size) if kind == "registered" else None)
     return maps
 
 
@@ -179,6 +181,8 @@ def run_empty(comm, maps, call, kind, context):
 # ---- the count table ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,channels,kind", TABLE, ids=["%d-%d-%s" % t for t in TABLE])
 def test_table(ring, oracle, n, channels, kind):
+    if kind == "split":
+        hm.require_caller_registration()
     calls = table_calls(n, channels)
     maps = make_mapping(calls, (kind,))
     seen, staged_calls, cut_in, cut_out = {}, 0, 0, 0
@@ -281,18 +285,19 @@ def test_odd_offsets_int8_fp16(ring, oracle):
         count = n * chunk_of(coll, "simple", e) + n + 1
         call = model_call(oracle, rm.Spec(k, coll, "nC+n+1", count, dt, op, k % 2 == 1, k % n), n)
         size = rh.mapping_bytes(call.arena0.size)
-        mp = rh.Mapping(size)
+        mp = rh.Mapping(size, registered=hm.registered_memory(size))
         with make_comm(ring, n, 1) as comm:
             for register in (True, False):
                 off = rh.PAGE + 48 + e
-                view = mp.buf[off:off + call.arena0.size]
-                handle = nexr.host_register(mp.base, size) if register else None
+                mem = mp.registered if register and mp.registered is not None else mp.buf
+                view = mem[off:off + call.arena0.size]
+                handle = nexr.host_register(mem.ctypes.data, size) if register else None
                 try:
                     got = []
                     for bits in (0, ALL_BITS):
                         view[:] = call.arena0
                         comm.set_flat(bool(bits & 1), tree=bool(bits & 2), copies=bool(bits & 4))
-                        rm.issue(comm, call, mp.base + off)
+                        rm.issue(comm, call, mem.ctypes.data + off)
                         got.append(fc.canon_outputs(call, view.copy()))
                 finally:
                     if handle is not None:
@@ -334,6 +339,7 @@ def test_mixed_kinds_in_one_call(ring, oracle):
     """Two ranks, rank 0's buffers registered and rank 1's pageable: the mapping is registered up to the page
     boundary before rank 1's first buffer. Out of place and in place, all six collectives; the in-place
     reduce-scatter's output is chunk r of its input."""
+    hm.require_caller_registration()
     nexr = nexr_mod()
     n = 2
     specs = [rm.Spec(k, coll, "C+1", chunk_of(coll, "simple", 4) + 1, ae.F32, rm.SUM, k % 2 == 1, k % n)
@@ -439,7 +445,7 @@ def test_process_ranks_are_refused(ring, nexr):
 def test_one_rank(ring, oracle):
     nexr = nexr_mod()
     calls = [rm.make_call(sp, 1, SEED, oring) for sp in rh.one_rank_plan()]
-    mp = rh.Mapping(rh.mapping_bytes(rh.largest_arena(calls)))
+    mp = make_mapping(calls, ("registered",))["registered"]
     with ring.RingComm(1, ring.HOST_MEMORY, rm.BUFF["simple"], None, TIMEOUT_MS, 0, tree_ranks_per_node=1) as comm:
         comm.set_flat(True, tree=True, copies=True)
         for call in calls:
@@ -469,6 +475,11 @@ print("FLAT-HOST-CHILD-OK")
 """
 
 
+def child_kinds(*kinds):
+    """`kinds`, without split where the runtime cannot register the caller's pages."""
+    return tuple(k for k in kinds if k != "split" or hm.registers_caller_memory())
+
+
 def window_specs(n):
     """fp32 at 1023, 1024, 1025, 2049 and 3 * 1024 + 3 elements (1, 1, 2, 2 plus a tail window of 4 bytes, and 3
     plus a tail window of 12 bytes), bf16 at an odd count (4097: 2 windows plus a tail of 2 bytes); the ring
@@ -493,12 +504,13 @@ def window_worker():
     nexr = nexr_mod()
     n = 3
     calls = [rm.make_call(sp, n, SEED, oring, "simple", 2) for sp in window_specs(n)]
-    maps = make_mapping(calls, ("pageable", "split", "registered"))
+    kinds = child_kinds("pageable", "split", "registered")
+    maps = make_mapping(calls, kinds)
     with make_comm(ring, n, 2) as comm:
         for call in calls:
             region = call.spec.count * call.esz
             want = -(-region // WINDOW_CHUNK)
-            for kind in ("pageable", "split", "registered"):
+            for kind in kinds:
                 st = run_both(comm, maps, call, kind, ("windows", n), stats=False)
                 if kind == "registered":
                     assert st["windows"] == 1 and st["zeroCopyCalls"] == 1, (call.spec.what(), st)
@@ -516,10 +528,11 @@ def zero_copy_off_worker():
     ring = importlib.import_module("nex-nccl_amd.ring")
     n = 3
     calls = table_calls(n, 1)[::5]
-    maps = make_mapping(calls, ("registered", "alloc", "split"))
+    kinds = child_kinds("registered", "alloc", "split")
+    maps = make_mapping(calls, kinds)
     with make_comm(ring, n, 1) as comm:
         for call in calls:
-            for kind in ("registered", "alloc", "split"):
+            for kind in kinds:
                 st = run_both(comm, maps, call, kind, ("zero copy off", n), stats=False)
                 assert st["zeroCopyCalls"] == 0 and st["registeredHits"] == 0 and st["pointerQueries"] == 0, st
                 assert st["stagedBuffers"] > 0, st

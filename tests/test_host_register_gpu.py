@@ -1,11 +1,17 @@
-"""nexrReduceCopyHost on host memory the caller registered with hipHostRegister (include/nexr.h: "when
-every buffer is pinned host memory (hipHostMalloc / hipHostRegister / torch pin_memory) the kernel
-reads and writes it in place"). The fork's transport allocates its staging buffers once
-(src/include/device.h:753-771), so registering them once is how a caller gets the zero-copy path on
-memory it did not allocate with the HIP runtime.
+"""nexrReduceCopyHost on host memory the caller pinned through the runtime behind the library's back
+(include/nexr.h: "when every buffer is pinned host memory (hipHostMalloc / hipHostRegister / torch
+pin_memory) the kernel reads and writes it in place"), and on memory registered with nexrHostRegister. The
+fork's transport allocates its staging buffers once (src/include/device.h:753-771), so pinning them once is
+how a caller gets the zero-copy path.
 
-Every pointer here lies INSIDE one registered mapping, at offsets that are not page-aligned, so the
-library's device address for each must be the mapping's device base plus the offset; a wrong
+The caller's pinned ranges are anonymous mappings registered with hipHostRegister where the runtime takes
+them, and come from hipHostMalloc on machines that cannot page-lock memory a process already has (Region;
+the runtime answers the library's pointer and range queries for both). The tests of nexrHostRegister on an
+anonymous mapping (a registration that ends inside a buffer, that is dropped while the pages stay,
+neighbours in one page) skip themselves there (tests/host_memory_support.py).
+
+Every pointer here lies INSIDE one pinned range, at offsets that are not page-aligned, so the
+library's device address for each must be the range's device base plus the offset; a wrong
 translation would read or write the wrong bytes and the exact check would fail. fp32 a + b is one
 IEEE add, so numpy's float32 sum is the oracle's value bit for bit."""
 import ctypes
@@ -16,9 +22,11 @@ import time
 import numpy as np
 import pytest
 
+import host_memory_support as hm
+
 pytestmark = pytest.mark.gpu
 
-HIP_HOST_REGISTER_MAPPED = 2  # hipHostRegisterMapped
+HIP_HOST_MALLOC_MAPPED = 2  # hipHostMallocMapped
 
 
 @pytest.fixture(scope="module")
@@ -27,24 +35,31 @@ def hip():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     torch.cuda.init()
-    L = ctypes.CDLL("libamdhip64.so")
-    L.hipHostRegister.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
-    L.hipHostRegister.restype = ctypes.c_int
-    L.hipHostUnregister.argtypes = [ctypes.c_void_p]
-    L.hipHostUnregister.restype = ctypes.c_int
-    return L
+    return hm.hip_runtime()
 
 
 class Region:
-    """One anonymous mapping (page-aligned), registered with hipHostRegister for its lifetime."""
+    """Page-aligned host memory that the caller pinned and device-mapped through the runtime for its lifetime (the
+    library never saw it): one anonymous mapping registered with hipHostRegister, or from hipHostMalloc where the
+    runtime cannot register a mapping the process already has. With register=False one anonymous, pageable
+    mapping."""
 
     def __init__(self, hip, nbytes: int, register: bool = True):
-        self.hip, self.m = hip, mmap.mmap(-1, nbytes)
-        self.buf = np.frombuffer(self.m, dtype=np.uint8)
+        self.hip = hip
+        self.registered = self.allocated = False
+        if register and not hm.registers_caller_memory():
+            p = ctypes.c_void_p()
+            rc = hip.hipHostMalloc(ctypes.byref(p), nbytes, HIP_HOST_MALLOC_MAPPED)
+            assert rc == 0 and p.value, f"hipHostMalloc = {rc}"
+            self.allocated = True
+            self.buf = np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(p.value))
+        else:
+            self.m = mmap.mmap(-1, nbytes)
+            self.buf = np.frombuffer(self.m, dtype=np.uint8)
         self.base = self.buf.ctypes.data
-        self.registered = False
-        if register:
-            rc = hip.hipHostRegister(self.base, nbytes, HIP_HOST_REGISTER_MAPPED)
+        assert self.base % mmap.PAGESIZE == 0
+        if register and not self.allocated:
+            rc = hip.hipHostRegister(self.base, nbytes, hm.HIP_HOST_REGISTER_MAPPED)
             assert rc == 0, f"hipHostRegister = {rc}"
             self.registered = True
 
@@ -52,10 +67,14 @@ class Region:
         return self.buf[offset:offset + 4 * n].view(np.float32)
 
     def close(self):
-        """Unregisters; the mapping itself goes when the last numpy view of it does."""
+        """Unregisters, or frees the allocation (no view of it is read afterwards); an anonymous mapping goes when
+        the last numpy view of it does."""
         if self.registered:
             self.registered = False
             assert self.hip.hipHostUnregister(self.base) == 0
+        if self.allocated:
+            self.allocated = False
+            assert self.hip.hipHostFree(self.base) == 0
 
 
 def _fill(rng, v: np.ndarray):
@@ -80,7 +99,7 @@ def test_registered_interior_pointers_zero_copy(hip, n):
         nexr.reduce_copy_ptrs([reg.base + offs[0], reg.base + offs[1]], [reg.base + offs[2]], n, 7, 0, host=True)
         st = nexr.host_path_stats()
         # which path ran: one zero-copy call, every buffer classified by the runtime's pointer query
-        # (the caller registered it, not the library), no staging copies
+        # (the caller pinned it, not the library), no staging copies
         assert (st["calls"], st["zeroCopyCalls"], st["pointerQueries"], st["registeredHits"]) == (1, 1, 3, 0), st
         assert st["copyNs"] == 0, st
         assert np.array_equal(out.view(np.uint32), (a + b).view(np.uint32))
@@ -91,8 +110,8 @@ def test_registered_interior_pointers_zero_copy(hip, n):
 
 
 def test_registered_sources_pageable_destination(hip):
-    """A mix: the sources in a registered mapping, the destination in plain pageable memory (the
-    library reads the registered ones in place and stages only the destination)."""
+    """A mix: the sources in a range the caller pinned, the destination in plain pageable memory (the
+    library reads the pinned ones in place and stages only the destination)."""
     nexr = importlib.import_module("nex-nccl_amd")
     n = 3_000_017
     rng = np.random.default_rng(7)
@@ -109,8 +128,8 @@ def test_registered_sources_pageable_destination(hip):
 
 
 def test_registered_rate_beside_pageable(hip):
-    """C2's mix (2 x 256 MiB in, 1 out) on one registered mapping against the same bytes unregistered:
-    both exact; the registered call takes the zero-copy path, so it is not slower than the pageable
+    """C2's mix (2 x 256 MiB in, 1 out) on one range the caller pinned against the same bytes in a pageable
+    mapping: both exact; the pinned call takes the zero-copy path, so it is not slower than the pageable
     one (both rates printed; the bench's h2d_inclusive line carries the measured figures)."""
     nexr = importlib.import_module("nex-nccl_amd")
     n = 64 << 20
@@ -144,10 +163,10 @@ HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, HIP_POINTER_ATTRIBUTE_RANGE_SIZE = 11, 1
 def test_runtime_reports_the_registered_range(hip):
     """nexrReduceCopyHost reads a caller-registered buffer in place only when the range the runtime
     reports for it (hipPointerGetAttribute RANGE_START_ADDR / RANGE_SIZE) covers the whole buffer.
-    This pins that the runtime answers those queries for an interior pointer of a hipHostRegister-ed
-    mapping, so the check is live (profiles/r05*_host_register_gpu_tests.txt records the values)."""
-    hip.hipPointerGetAttribute.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    hip.hipPointerGetAttribute.restype = ctypes.c_int
+    This pins that the runtime answers those queries for an interior pointer of the range the caller
+    pinned (Region: a hipHostRegister-ed mapping, or a hipHostMalloc allocation where the runtime registers
+    none), so the check is live (profiles/r05*_host_register_gpu_tests.txt records the values for a
+    hipHostRegister-ed mapping)."""
     reg = Region(hip, 1 << 20)
     try:
         beg, size = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -166,6 +185,7 @@ def test_library_registration_is_read_in_place_without_queries(hip):
     buffers inside it is classified from the cache with no runtime query and runs zero-copy; a range
     inside it shares the entry; a partly overlapping one is refused; after the last deregistration
     the same call stages the (now pageable) bytes and is still exact."""
+    hm.require_caller_registration()
     nexr = importlib.import_module("nex-nccl_amd")
     n = 1_000_003
     gap = 4096 + 48
@@ -204,6 +224,7 @@ def test_buffer_past_a_registered_range_is_staged(hip):
     """A buffer that starts inside a registered range but runs past its end must not be read in place
     (the device mapping covers only the range): the cache lookup misses, the runtime reports the
     range, and the call stages the buffer instead (exact, zero-copy count 0)."""
+    hm.require_caller_registration()
     nexr = importlib.import_module("nex-nccl_amd")
     n = 1 << 20
     reg = Region(hip, 4 * n * 4, register=False)
@@ -231,6 +252,7 @@ def test_buffer_across_a_registration_edge_through_the_runtime_copies(hip, cut):
     (round 13: such a call returned nexrUnhandledCudaError). output-end / source-end: the registration ends
     inside `out` / inside `a`; source-begin: it begins inside `a`. Page-aligned cuts at odd element offsets of
     buffers that are not page-aligned."""
+    hm.require_caller_registration()
     nexr = importlib.import_module("nex-nccl_amd")
     n = (1 << 20) + 4099
     gap = 4096 + 48
@@ -316,10 +338,11 @@ def test_register_inside_an_allocation_then_free(hip):
 
 def test_sub_page_neighbours_register_separately(hip):
     """Advisor r5 (low): hipHostRegister pins whole pages, so two disjoint buffers in one page (adjacent
-    heap blocks, as the C1 bench's numpy arrays are) both touch the same page. On this ROCm the runtime
+    heap blocks, as numpy arrays of a few MiB are) both touch the same page. On this ROCm the runtime
     maps each registration separately: two entries, two handles, each buffer read in place from the
     cache, and deregistering one leaves the other's mapping working. A range that overlaps an entry's
     bytes is refused with nexrInvalidUsage."""
+    hm.require_caller_registration()
     nexr = importlib.import_module("nex-nccl_amd")
     reg = Region(hip, 4 * 4096, register=False)
     n = 100
@@ -354,3 +377,20 @@ def test_sub_page_neighbours_register_separately(hip):
                 assert st["registeredHits"] == 0, st
     finally:
         reg.close()
+
+
+def test_refused_registration_leaves_no_hip_error(hip):
+    """include/nexr.h: where the runtime cannot page-lock memory the process already has, nexrHostRegister of a
+    range outside the cache returns nexrUnhandledCudaError and leaves no HIP error behind (the runtime keeps a
+    refused hipHostRegister as the thread's last error, and the caller's next launch check would report it);
+    nexrGetLastHipError still has the code. Where the runtime registers the page there is nothing to refuse."""
+    if hm.registers_caller_memory():
+        pytest.skip("hipHostRegister works here: no registration is refused")
+    nexr = importlib.import_module("nex-nccl_amd")
+    reg = Region(hip, mmap.PAGESIZE, register=False)
+    assert hip.hipPeekAtLastError() == 0
+    with pytest.raises(nexr.NexrError) as e:
+        nexr.host_register(reg.base, mmap.PAGESIZE)
+    assert e.value.code == nexr.Result.UnhandledCudaError
+    assert nexr.lib().nexrGetLastHipError() != 0
+    assert hip.hipPeekAtLastError() == 0

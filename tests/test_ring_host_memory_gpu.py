@@ -7,7 +7,9 @@ tests/ring_modes_cases.py's count table (1 element to 2 n C + 3 and 0, all ten d
 of place, every root, 2 to 8 ranks, 1 and 2 channels), with and without set_direct, on user buffers that are
 
   pageable    every step staged through the calling thread's pinned slots;
-  registered  inside one nexrHostRegister-ed mapping: every step zero-copy, classified from the cache;
+  registered  inside one nexrHostRegister-ed mapping: every step zero-copy, classified from the cache (where the
+              runtime cannot page-lock a mapping the process already has, inside a nexrHostMemAlloc allocation that
+              is registered whole: tests/host_memory_support.py);
   pinned      pinned by the runtime, unknown to the library (torch pin_memory): zero-copy after the pointer query
               and its range check;
   split       registered up to a page boundary inside one rank's user buffer: zero-copy and staged steps in one
@@ -15,7 +17,10 @@ of place, every root, 2 to 8 ranks, 1 and 2 channels), with and without set_dire
 
 (tests/ring_host_cases.py places them), then the four kinds in turn on one mapping with direct toggled, the forced
 host paths (pageable FIFOs, the chunk pipeline, the copy team with small chunks) in child processes, C1's
-host_registered leg as bench.py runs it, and a communicator of one rank.
+host_registered leg with four registrations sharing pages, and a communicator of one rank. The tests that need a
+registration to end inside a buffer, or to be dropped while the pages stay (split, the mixed kinds, that C1 leg),
+skip themselves where the runtime cannot register the caller's pages; the forced children run `registered` in
+split's place there.
 
 SIMPLE, rm.BUFF["simple"] (4 KiB steps), the library's own fn, timeoutMs = 20000: a stuck protocol ends with an
 error. Every call's arena is compared whole with the expected bytes (rm.check): outputs, guards, inputs, and the
@@ -37,6 +42,7 @@ import numpy as np
 import pytest
 
 import arith_edges as ae
+import host_memory_support as hm
 import ring_host_cases as rh
 import ring_modes_cases as rm
 from oracle import ring as oring
@@ -86,14 +92,15 @@ _pinned = {}
 
 def make_mapping(calls, kinds):
     """The test's one mapping, with runtime-pinned memory of the same size beside it when `kinds` needs it (kept
-    for the module: the pinned allocator keeps it anyway)."""
+    for the module: the pinned allocator keeps it anyway), and the registered kind's memory where that is not the
+    mapping itself."""
     size = rh.mapping_bytes(rh.largest_arena(calls))
     pinned = None
     if "pinned" in kinds:
         if size not in _pinned:
             _pinned[size] = torch.empty(size, dtype=torch.uint8).pin_memory()
         pinned = _pinned[size].numpy()
-    return rh.Mapping(size, pinned)
+    return rh.Mapping(size, pinned, hm.registered_memory(size) if "registered" in kinds else None)
 
 
 def make_comm(ring, n, channels):
@@ -179,6 +186,8 @@ def run_mixed(comm, mapping, calls, kinds, context, fifos_pinned=True):
 @pytest.mark.parametrize("n,channels,kind,direct", TABLE,
                          ids=["%d-%d-%s%s" % (n, ch, kind, "-direct" if d else "") for n, ch, kind, d in TABLE])
 def test_table(ring, oracle, n, channels, kind, direct):
+    if kind == "split":
+        hm.require_caller_registration()
     calls = table_calls(n, channels)
     mapping = make_mapping(calls, (kind,))
     with make_comm(ring, n, channels) as comm:
@@ -193,6 +202,7 @@ def test_mixed_kinds_and_toggles(ring, oracle, n):
     whole (the pinned calls run in the runtime's memory beside it); direct changes every three calls. A stale
     cache entry, a leaked staging slot or a drifting step counter is a wrong byte, and a stale entry also a
     zero-copy step in a pageable call."""
+    hm.require_caller_registration()
     calls = mixed_calls(n)
     mapping = make_mapping(calls, rh.KINDS)
     with make_comm(ring, n, 2) as comm:
@@ -231,7 +241,12 @@ print("HOST-TABLES-OK")
 
 
 def forced_worker(kinds, fifos_pinned, env):
+    """Where the runtime cannot register the caller's pages, `registered` (in a nexrHostMemAlloc allocation) runs in
+    split's place: with `pageable` the forced path still sees steps staged on one side and pinned on the other
+    (the FIFOs), and steps pinned on both."""
     ring = importlib.import_module("nex-nccl_amd.ring")
+    if not hm.registers_caller_memory():
+        kinds = tuple("registered" if k == "split" else k for k in kinds)
     for n, channels in ((3, 1), (4, 2)):
         calls = table_calls(n, channels)
         mapping = make_mapping(calls, kinds)
@@ -257,10 +272,12 @@ def test_forced_host_paths(env, kinds):
 
 
 def test_c1_host_registered_as_the_bench_runs_it(ring, nexr):
-    """bench.py's host_registered leg of C1: 2 ranks, fp32 sum, 1 << 20 elements, the default FIFOs, four
-    buffers each registered on its own, neighbours sharing a page (64 bytes apart in one mapping, none
+    """C1's host_registered leg (2 ranks, fp32 sum, 1 << 20 elements, the default FIFOs) as bench.py ran it on
+    numpy arrays before it took its buffers from nexrHostMemAlloc, and as a caller with buffers of its own runs
+    it: four buffers each registered on its own, neighbours sharing a page (64 bytes apart in one mapping, none
     page-aligned). Every step zero-copy from the cache; after deregistration the same call stages every step.
     Small integers: a + b is exact in fp32 whatever the order."""
+    hm.require_caller_registration()
     count = 1 << 20
     gap = 4 * count + 64
     mapping = rh.Mapping(rh.page_ceil(4 * gap) + 2 * rh.PAGE)
@@ -307,7 +324,8 @@ def test_one_rank(ring, oracle, nexr, memory):
     a broadcast's of any bit pattern, NaN payloads included."""
     calls = [rm.make_call(sp, 1, SEED, oring) for sp in one_rank_plan()]
     mode = ring.DEVICE_MEMORY if memory == "device" else ring.HOST_MEMORY
-    mapping = rh.Mapping(rh.mapping_bytes(rh.largest_arena(calls)))
+    kind = None if memory == "device" else memory[5:]
+    mapping = make_mapping(calls, (kind,)) if kind else None
     with ring.RingComm(1, mode, rm.BUFF["simple"], None, TIMEOUT_MS, 0, tree_ranks_per_node=1) as comm:
         for call in calls:
             context = ("one rank", memory)
@@ -318,7 +336,6 @@ def test_one_rank(ring, oracle, nexr, memory):
                 torch.cuda.synchronize()
                 rm.check(call, dev.cpu().numpy(), context)
                 continue
-            kind = memory[5:]
             with mapping.placed(kind, call, nexr.host_register, nexr.host_deregister) as (_pl, base, view):
                 nexr.host_path_stats(reset=True)
                 rm.issue(comm, call, base)
