@@ -1141,6 +1141,37 @@ NEXR_API nexrResult_t nexrFlatGroupPlan(int nRanks, const nexrFlatGroupWork* wor
                                         int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info);
 
 /*
+ * nexrFlatAllToAll — the personalised exchange in ONE launch: what n * n ncclSend / ncclRecv inside one group do
+ * (reference src/device/sendrecv.h, the FuncCopy<int8_t> reduceCopy site), and what PyTorch issues as
+ * all_to_all_single. Additions only: the ABI stays 0.3. Device memory of the current device.
+ *
+ * The rule, for nRanks = n and nBytes = B per pair:
+ *     outputs[d][s * B + i] = inputs[s][d * B + i]        for all s, d < n and i < B.
+ * Every input and every output is n * B bytes. It is a bit copy at any byte alignment: no datatype enters, and
+ * neither does NEXR_SEMANTICS.
+ *
+ * How it runs. Block (s -> d) is a pure function of n, B and the 2n base pointers, so the launch has no table,
+ * no workspace and no fill launch at any n up to NEXR_SYM_MAX_RANKS (the same blocks as n * n NEXR_FLAT_GROUP_COPY
+ * works need a table beyond the kernel arguments from 16 ranks on). Two paths, chosen by the host:
+ *   B % 16 == 0 (packs): a wave takes one 2048-byte piece of one OUTPUT row, so consecutive waves write consecutive
+ *     addresses whatever B is; each lane derives the source rank of its 16-byte packs from its place in the row, and
+ *     a small block (B = 256) still fills all 64 lanes.
+ *   any other B >= 1 (bytes): a wave takes one 2048-byte piece of one block, the block's last B & 15 bytes one per
+ *     lane.
+ * The partition is static (no atomics, no polls), the call is stream-ordered, and nothing of the caller's arrays
+ * is read after it returns, so it can be captured into a graph. maxWorkgroups caps the grid (waves then stride
+ * over the pieces); 0: a wave per piece, four waves per workgroup. nBytes == 0 succeeds without a launch.
+ *
+ * nexrInvalidArgument, before any device call: nRanks outside 2..NEXR_SYM_MAX_RANKS; a null array or a null entry;
+ * maxWorkgroups < 0; nRanks * nBytes beyond size_t; any input range [inputs[s], + n * B) that intersects any
+ * output range [outputs[d], + n * B), or two output ranges that intersect (half-open byte ranges: one that ends
+ * where the other begins is accepted). In place is not offered: a grouped send / recv exchange in place is
+ * undefined in the reference too. Inputs may alias each other.
+ */
+NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, void* const* outputs,
+                                       size_t nBytes /* per pair */, int maxWorkgroups, nexrStream_t stream);
+
+/*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
  * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.

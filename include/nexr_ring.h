@@ -245,6 +245,29 @@ NEXR_API nexrResult_t nexrRingBroadcastFlat(nexrRingComm_t comm, const void* con
 NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* const* sendbuffs,
                                             void* const* recvbuffs, size_t sendcount, int datatype);
 
+/* The personalised exchange, all-to-all: what n * n ncclSend / ncclRecv inside one ncclGroupStart / ncclGroupEnd
+ * do (reference src/device/sendrecv.h) and what PyTorch issues as all_to_all_single. Rank s sends elements
+ * [d*count, (d+1)*count) of sendbuffs[s] to rank d, which receives them at [s*count, (s+1)*count) of recvbuffs[d];
+ * every buffer holds nRanks*count elements. A bit copy: every datatype the all-gather takes. Additions only: the
+ * ABI stays 0.3.
+ *   Thread ranks, device memory, every rank on one GPU, at most NEXR_SYM_MAX_RANKS ranks: ONE nexrFlatAllToAll
+ *     launch (include/nexr.h: no table at any rank count) on the communicator's first stream through the helper
+ *     of the flat entries above and its wait. No connection, no step counter and not nexrRingCommGetQueued's
+ *     report is touched, and no option is needed: the default library has no FIFO all-to-all to route away from.
+ *   Any other thread-rank communicator (host memory with any fn, ranks on several GPUs): n * n block copies in
+ *     (d, s) order, each ONE reduce-copy through the communicator's fn with one source and one destination on the
+ *     receiving rank (nexrUint8, nexrDevSum, count * esz elements), so a caller's fn sees every block; the call
+ *     returns with the outputs complete.
+ *   One rank: the one-rank copy. count == 0 succeeds. Process ranks: nexrInvalidUsage.
+ * nexrInvalidArgument as nexrRingAllGather answers it (a null array, a null buffer with count != 0, an unknown
+ * datatype, fp8 included; a broken communicator is nexrInvalidUsage), and for a send range that meets a receive
+ * range (half-open byte ranges of nRanks*count elements): in place is not offered, as a grouped send / recv in
+ * place is undefined in the reference. Inside nexrRingGroupStart / nexrRingGroupEnd the call is checked and
+ * recorded like every other entry and runs alone at its place (`singles`). Measured numbers: DESIGN §8.12
+ * (tools/alltoall_probe.py). */
+NEXR_API nexrResult_t nexrRingAllToAll(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                       size_t count /* elements per pair */, int datatype);
+
 /* Opt-in, off by default: which plain calls on an eligible communicator run as their flat entries above. `on`
  * is read as bits: NEXR_FLAT_RING (1) routes nexrRingAllReduce, nexrRingReduceScatter and nexrRingReduce;
  * NEXR_FLAT_TREE (2) routes nexrTreeAllReduce; NEXR_FLAT_COPIES (4) routes nexrRingAllGather and

@@ -97,7 +97,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrFlatTreeAllReducePreMul",
                "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
                "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
-               "nexrFlatGroup", "nexrFlatGroupPlan",
+               "nexrFlatGroup", "nexrFlatGroupPlan", "nexrFlatAllToAll",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -398,6 +398,8 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatGroup.restype = i32
     L.nexrFlatGroupPlan.argtypes = [i32, P(FlatGroupWork), i32, i32, i32, P(i32), P(FlatGroupInfo)]
     L.nexrFlatGroupPlan.restype = i32
+    L.nexrFlatAllToAll.argtypes = [i32, P(vp), P(vp), sz, i32, vp]
+    L.nexrFlatAllToAll.restype = i32
     L.nexrGetFlatHostStats.argtypes = [P(FlatHostStats), i32]
     L.nexrGetFlatHostStats.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
@@ -1123,6 +1125,19 @@ def flat_broadcast(input: int, outputs: Sequence[int], n_bytes: int, stream: int
     rc = lib().nexrFlatBroadcast(len(outputs), ctypes.c_void_p(int(input)) if input else None, _ptr_array(outputs),
                                  int(n_bytes), ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatBroadcast")
+
+
+def flat_all_to_all(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int, max_workgroups: int = 0,
+                    stream: Optional[int] = None) -> None:
+    """The all-to-all in ONE launch (``nexrFlatAllToAll``): ``outputs[d][s*B + i] = inputs[s][d*B + i]`` for
+    ``B = n_bytes`` per pair, a bit copy at any byte alignment; every buffer is ``len(inputs) * n_bytes`` bytes of
+    device memory. No table and no workspace at any rank count up to 64. Inputs and outputs must not overlap
+    (InvalidArgument); ``max_workgroups`` caps the grid, 0 for the default. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatAllToAll(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
+                                int(max_workgroups), ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllToAll")
 
 
 # ---- the flat collectives over host memory (nexrFlatHost*): the device forms' arguments, host addresses -------------

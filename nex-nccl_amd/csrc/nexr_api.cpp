@@ -2828,6 +2828,44 @@ NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* con
   return nexrSuccess;
 }
 
+// ---- nexrFlatAllToAll -------------------------------------------------------------------------------------------
+// Every check before any device call; the ranges are half-open, as nexrFlatGroupPlan compares them. The host
+// picks the instance: packs where no pack can straddle two blocks (nBytes % 16 == 0), bytes otherwise.
+NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
+                                       int maxWorkgroups, nexrStream_t stream) {
+  if (!inputs || !outputs || maxWorkgroups < 0) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (nBytes > (size_t)-1 / (size_t)nRanks) return nexrInvalidArgument;  // a buffer's nRanks * nBytes bytes
+  const uintptr_t row = (uintptr_t)nRanks * nBytes;
+  FlatAllToAllParams p;
+  memset((void*)&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+  }
+  auto hit = [row](const void* a, const void* b) {
+    return (uintptr_t)a < (uintptr_t)b + row && (uintptr_t)b < (uintptr_t)a + row;
+  };
+  for (int d = 0; d < nRanks && row; d++) {
+    for (int s = 0; s < nRanks; s++)
+      if (hit(outputs[d], inputs[s])) return nexrInvalidArgument;  // in place is not offered
+    for (int e = 0; e < d; e++)
+      if (hit(outputs[d], outputs[e])) return nexrInvalidArgument;
+  }
+  if (nBytes == 0) return nexrSuccess;
+  const bool bytes = (nBytes & 15u) != 0;
+  p.blockBytes = nBytes;
+  p.nRanks = nRanks;
+  p.piecesPer = ((bytes ? (uint64_t)nBytes : (uint64_t)row) + 2047) / 2048;
+  p.nItems = p.piecesPer * (uint64_t)nRanks * (bytes ? (uint64_t)nRanks : 1);
+  // a wave per item, four waves per workgroup; beyond the cap the waves stride
+  uint64_t grid = std::min<uint64_t>((p.nItems + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
+  NEXR_HIP(launch_flat_alltoall(p, bytes, (unsigned)grid, (hipStream_t)stream));
+  return nexrSuccess;
+}
+
 // ---- nexrFlatGroup, nexrFlatGroupPlan: several flat collectives as group launches -----------------------------
 // The plan (no device call): every work through its single entry's checks, then the walk of include/nexr.h: one
 // open launch per key, a conflict with a work of any open launch closes them all. Launches are queued in the

@@ -409,6 +409,21 @@ hipError_t launch_flat_group(int dt, int op, const FlatGroupParams& p, unsigned 
 hipError_t launch_flat_group_copy(const FlatGroupCopyParams& p, unsigned grid, hipStream_t s);
 hipError_t launch_flat_group_fill(const FlatGroupFill& f, hipStream_t s);
 
+// The all-to-all in one launch (nexrFlatAllToAll; nexr_flat_alltoall.hip): out[d][s * B + i] = in[s][d * B + i].
+// No table: the block of a lane follows from its place in the output. The pack instance (B % 16 == 0) cuts every
+// output ROW of nRanks * B bytes into piecesPer pieces, the byte instance every BLOCK; nItems is nRanks * piecesPer
+// or nRanks * nRanks * piecesPer. in[] leads the block: the kernel reads both arrays by their byte offsets.
+struct FlatAllToAllParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t blockBytes;  // B
+  uint64_t piecesPer;
+  uint64_t nItems;
+  int nRanks, pad;
+};
+static_assert(sizeof(FlatAllToAllParams) <= 4000, "kernel argument block");
+hipError_t launch_flat_alltoall(const FlatAllToAllParams& p, bool bytes, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

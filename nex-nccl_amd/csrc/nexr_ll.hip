@@ -1200,3 +1200,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 #include "nexr_flat_tree.hip"
 // Several of them in one launch (nexrFlatGroup): the same code object again.
 #include "nexr_flat_group.hip"
+// The all-to-all in one launch (nexrFlatAllToAll): the same code object again.
+#include "nexr_flat_alltoall.hip"

@@ -1481,6 +1481,69 @@ nexrResult_t flatAllGather(nexrRingComm* c, const void* const* sendbuffs, void* 
       nullptr, true);
 }
 
+// nexrRingAllToAll. The checks that need no execution (groupRecord repeats them for a recorded call): the
+// arguments as nexrRingAllGather's, and no send range [sendbuffs[s], + n * count * esz) may meet a receive range
+// (half-open byte ranges).
+nexrResult_t allToAllCheck(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                           int datatype, size_t* esz) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;
+  nexrDevRedOpFull red;
+  const nexrResult_t r = prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
+  if (r != nexrSuccess) return r;
+  const int n = c->cfg.nRanks;
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if (count > (size_t)-1 / *esz / (size_t)n) return nexrInvalidArgument;
+  if (count == 0) return nexrSuccess;
+  const uintptr_t row = (uintptr_t)n * count * *esz;
+  for (int i = 0; i < n; i++)
+    if (!sendbuffs[i] || !recvbuffs[i]) return nexrInvalidArgument;
+  for (int d = 0; d < n && n > 1; d++)
+    for (int s = 0; s < n; s++)
+      if ((uintptr_t)recvbuffs[d] < (uintptr_t)sendbuffs[s] + row && (uintptr_t)sendbuffs[s] < (uintptr_t)recvbuffs[d] + row)
+        return nexrInvalidArgument;
+  return nexrSuccess;
+}
+
+// Thread ranks in device memory on one GPU: ONE nexrFlatAllToAll launch on the first stream through symCollective
+// and its wait, as flatBroadcast. Any other thread-rank communicator: n * n block copies in (d, s) order, each ONE
+// reduce-copy with one source and one destination on the receiving rank (uint8, Sum, count * esz elements: a
+// caller's fn sees every block), and the call returns with the outputs complete.
+nexrResult_t allToAll(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                      int datatype) {
+  size_t esz = 0;
+  const nexrResult_t r = allToAllCheck(c, sendbuffs, recvbuffs, count, datatype, &esz);
+  if (r != nexrSuccess || count == 0) return r;
+  const int n = c->cfg.nRanks;
+  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
+  bool oneGpu = device && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() && c->streams[0];
+  for (int i = 0; oneGpu && i < n; i++)
+    if (c->devices[i] != c->devices[0]) oneGpu = false;
+  if (n == 1) {
+    nexrDevRedOpFull red;
+    const nexrResult_t e = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
+    return e != nexrSuccess ? e : oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, esz);
+  }
+  if (oneGpu)
+    return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
+      return nexrFlatAllToAll(nr, sendbuffs, recvbuffs, count * esz, 0, stream);
+    });
+  const size_t bytes = count * esz;
+  nexrResult_t res = nexrSuccess;
+  for (int d = 0; d < n && res == nexrSuccess; d++) {
+    if (c->streams[d]) (void)hipSetDevice(c->devices[d]);
+    for (int s = 0; s < n && res == nexrSuccess; s++) {
+      const void* src = (const char*)sendbuffs[s] + (size_t)d * bytes;
+      void* dst = (char*)recvbuffs[d] + (size_t)s * bytes;
+      res = c->cfg.fn(1, &src, 1, &dst, bytes, nexrUint8, nexrDevSum, 0, 0, nullptr, 0, (nexrStream_t)c->streams[d]);
+    }
+    // also behind an error: nothing stays in flight over the caller's buffers
+    if (device && c->streams[d] && hipStreamSynchronize(c->streams[d]) != hipSuccess && res == nexrSuccess)
+      res = nexrUnhandledCudaError;
+  }
+  return res;
+}
+
 // nexrRingCommSetFlat: whether the plain ring all-reduce, reduce-scatter and reduce of this communicator run
 // flat. Thread ranks in device memory on one GPU with the library's own kernels for the protocol (a caller's
 // fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes; or thread ranks in
@@ -1635,7 +1698,8 @@ enum RingEntry {
   kEntAllReduce, kEntReduceScatter, kEntAllGather, kEntReduce, kEntBroadcast, kEntTree,
   kEntSymAllReduce, kEntSymReduceScatter, kEntSymAllGather,
   kEntFlatAllReduce, kEntFlatReduceScatter, kEntFlatReduce, kEntFlatTree, kEntFlatBroadcast, kEntFlatAllGather,
-  kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather
+  kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather,
+  kEntAllToAll
 };
 
 // The entry as it runs alone.
@@ -1716,18 +1780,22 @@ nexrResult_t runEntry(nexrRingComm* c, int entry, const void* const* sendbuffs, 
       DeviceGuard dg(dev);
       return symLLAllGather(c, sendbuffs, recvbuffs, count, datatype, nBlocks);
     }
+    case kEntAllToAll: {
+      DeviceGuard dg(c && c->needHip);
+      return allToAll(c, sendbuffs, recvbuffs, count, datatype);
+    }
   }
   return nexrInvalidArgument;
 }
 
 bool entryReduces(int e) {
   return e != kEntAllGather && e != kEntBroadcast && e != kEntSymAllGather && e != kEntFlatBroadcast &&
-         e != kEntFlatAllGather && e != kEntSymLLAllGather;
+         e != kEntFlatAllGather && e != kEntSymLLAllGather && e != kEntAllToAll;
 }
 bool entryIsReduce(int e) { return e == kEntReduce || e == kEntFlatReduce; }
 bool entryIsBroadcast(int e) { return e == kEntBroadcast || e == kEntFlatBroadcast; }
 // The explicit entries that answer nexrInvalidUsage on a communicator they do not serve.
-bool entryNeedsOneGpu(int e) { return e >= kEntSymAllReduce; }
+bool entryNeedsOneGpu(int e) { return e >= kEntSymAllReduce && e != kEntAllToAll; }
 
 // A call inside a group: the checks that need no execution, then the record. A call that fails is not recorded.
 nexrResult_t groupRecord(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs,
@@ -1735,7 +1803,10 @@ nexrResult_t groupRecord(nexrRingComm* c, int entry, const void* const* sendbuff
   if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
   const int n = c->cfg.nRanks;
   size_t esz = 0;
-  if (entryReduces(entry)) {
+  if (entry == kEntAllToAll) {  // its own checks, the ranges' overlap among them
+    const nexrResult_t r = allToAllCheck(c, sendbuffs, recvbuffs, count, datatype, &esz);
+    if (r != nexrSuccess) return r;
+  } else if (entryReduces(entry)) {
     RedOps ops;
     const nexrResult_t r = prepareOps(c, datatype, op, &esz, &ops, false);
     if (r != nexrSuccess) return r;
@@ -2100,6 +2171,11 @@ NEXR_API nexrResult_t nexrRingReduceScatterFlat(nexrRingComm_t c, const void* co
 NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                          size_t count, int datatype, int op, int root) {
   return groupOrRun(c, kEntFlatReduce, sendbuffs, recvbuffs, count, datatype, op, root, 0);
+}
+
+NEXR_API nexrResult_t nexrRingAllToAll(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                       size_t count, int datatype) {
+  return groupOrRun(c, kEntAllToAll, sendbuffs, recvbuffs, count, datatype, nexrSum, 0, 0);
 }
 
 NEXR_API nexrResult_t nexrRingGroupStart(nexrRingComm_t c) {

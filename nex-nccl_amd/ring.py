@@ -24,7 +24,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllReduceSymmetricLL", "nexrRingReduceScatterSymmetricLL",
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
-                    "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat",
+                    "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat", "nexrRingAllToAll",
                     "nexrRingGroupStart", "nexrRingGroupEnd", "nexrRingGroupGetStats",
                     "nexrTreeTopology", "nexrRingRedOpCreatePreMulSum", "nexrRingRedOpDestroy",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
@@ -120,6 +120,7 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrTreeAllReduceFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingBroadcastFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingAllGatherFlat.argtypes = [vp, arr, arr, sz, i32]
+    L.nexrRingAllToAll.argtypes = [vp, arr, arr, sz, i32]
     L.nexrRingGroupStart.argtypes = [vp]
     L.nexrRingGroupEnd.argtypes = [vp]
     L.nexrRingGroupGetStats.argtypes = [vp, ctypes.POINTER(RingGroupStats), i32]
@@ -376,6 +377,14 @@ class RingComm:
         bytes are the ring's."""
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrRingAllGatherFlat(self._h, s, r, int(sendcount), int(datatype)), "nexrRingAllGatherFlat")
+
+    def all_to_all(self, sendbuffs, recvbuffs, count: int, datatype: int) -> None:
+        """The personalised exchange (nexrRingAllToAll): rank s's elements [d*count, (d+1)*count) arrive at
+        [s*count, (s+1)*count) of rank d's recvbuff, a bit copy; every buffer holds n_ranks*count elements and no
+        send range may meet a receive range. ONE launch on thread ranks in device memory on one GPU, n*n block
+        copies through the communicator's reduce-copy elsewhere; InvalidUsage for process ranks."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllToAll(self._h, s, r, int(count), int(datatype)), "nexrRingAllToAll")
 
     def set_flat(self, on: bool, tree: bool = False, copies: bool = False) -> None:
         """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat). `on` (FLAT_RING):
