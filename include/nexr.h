@@ -1171,6 +1171,70 @@ NEXR_API nexrResult_t nexrFlatGroupPlan(int nRanks, const nexrFlatGroupWork* wor
 NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, void* const* outputs,
                                        size_t nBytes /* per pair */, int maxWorkgroups, nexrStream_t stream);
 
+/* Where a value the library needs lives: in device memory, dereferenced on the device while the call runs, or in
+ * host memory, read before the call returns. Used by nexrFlatAllToAllv below and by the user-created reduction ops
+ * of include/nexr_ring.h. */
+typedef enum { nexrScalarDevice = 0, nexrScalarHostImmediate = 1 } nexrScalarResidence_t; /* = ncclScalarResidence_t */
+
+/*
+ * nexrFlatAllToAllv — the personalised exchange with a count per pair in ONE launch, the counts read on the device:
+ * what n * n ncclSend / ncclRecv of differing sizes inside one group do, and what PyTorch issues as
+ * all_to_all_single with input_split_sizes / output_split_sizes (expert-parallel token dispatch and combine).
+ * Additions only: the ABI stays 0.3. Device memory of the current device.
+ *
+ * The rule, for nRanks = n, esz bytes per element and counts[s * n + d] elements from rank s to rank d, packed on
+ * both sides as all_to_all_single defines it:
+ *     sendOff(s, d) = sum over d' < d of counts[s * n + d']
+ *     recvOff(d, s) = sum over s' < s of counts[s' * n + d]
+ *     outputs[d][(recvOff(d, s) + i) * esz + b] = inputs[s][(sendOff(s, d) + i) * esz + b]
+ *                                                 for i < counts[s * n + d], b < esz.
+ * It is a bit copy at any byte alignment of the bases: no datatype enters, and neither does NEXR_SEMANTICS. Bytes
+ * of outputs[d] behind its row total are not written. Explicit displacements (MPI's sdispls / rdispls) are not
+ * offered: the layout is the packed one.
+ *
+ * inElts[s] and outElts[d] are the capacities of the buffers in elements: host arrays, read before the call
+ * returns, for both residences. Whatever the counts say, no byte outside [inputs[s], + inElts[s] * esz) is read
+ * and none outside [outputs[d], + outElts[d] * esz) is written.
+ *
+ * residence == nexrScalarHostImmediate: `counts` is a host array, read before the call returns. A row sum above
+ * inElts[s] or a column sum above outElts[d] is nexrInvalidArgument before any device call. The exact number of
+ * 2048-byte pieces sizes the grid. The matrix rides in the kernel arguments up to
+ * NEXR_FLAT_ALLTOALLV_INLINE_RANKS ranks; beyond that it goes by value, in short fill launches (nexrFlatGroup's),
+ * into stream-ordered memory that is freed behind the launch: nothing of the caller's arrays is read after return.
+ * `status` may be NULL; where it is not, the launch writes 0 to it. All counts zero: success, no launch.
+ *
+ * residence == nexrScalarDevice: `counts` is device memory of the current device, 8-byte aligned, and is read by
+ * the kernel only: the values are whatever `stream`, or anything ordered before the call, wrote last. No host
+ * read, no synchronisation, no fill launch, so the call can be captured into a graph and replayed over rewritten
+ * counts. The grid is sized from the capacities (the pieces of outElts[d] * esz bytes per row). The kernel checks
+ * every count against its two capacities, every row sum against inElts[s] and every column sum against
+ * outElts[d]: on a violation NOTHING is written to any output and *status (a device word, required) becomes 1;
+ * otherwise it becomes 0.
+ *
+ * How it runs (nexr_flat_exchange_v.hip). Every workgroup first turns the matrix into byte offsets in 16 * n * n
+ * bytes of LDS by wave-wide scans of its rows and columns and reaches the verdict by itself; then a wave takes one
+ * 2048-byte piece of one packed OUTPUT row, so consecutive waves write consecutive addresses whatever the block
+ * sizes are. A lane finds the block of each of its two 16-byte packs by a search of at most six steps in LDS; a
+ * pack inside one block is one unaligned 16-byte load and store, one that meets a block boundary or the row's end
+ * goes byte by byte. No atomics, no polls. maxWorkgroups caps the grid (waves then stride); 0: a wave per piece,
+ * four waves per workgroup, up to the workgroups the device keeps resident (per CU eight, or as many as find their
+ * LDS where that is fewer: 2048 on an MI355X up to 35 ranks), so that on a large exchange one prologue serves many
+ * pieces.
+ *
+ * nexrInvalidArgument, before any device call, for both residences: nRanks outside 2..NEXR_SYM_MAX_RANKS; a null
+ * array; a null buffer whose capacity is not 0; esz not 1, 2, 4 or 8; maxWorkgroups < 0; an unknown residence; a
+ * capacity above 2^56 bytes (so that no sum of admitted counts wraps) or a range that wraps the address space; any
+ * input capacity range that meets any output capacity range, or two output capacity ranges that meet (half-open
+ * byte ranges: one that ends where the other begins is accepted; an empty range meets nothing). Device counts
+ * only: a NULL status, a misaligned `counts`, and the n * n * 8 bytes of `counts` or the status word meeting an
+ * output range. Inputs may alias each other. In place is not offered.
+ */
+#define NEXR_FLAT_ALLTOALLV_INLINE_RANKS 15
+NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, void* const* outputs,
+                                        const uint64_t* counts /* n*n, [s*n+d] */, int residence, size_t esz,
+                                        const size_t* inElts, const size_t* outElts, uint32_t* status,
+                                        int maxWorkgroups, nexrStream_t stream);
+
 /*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as

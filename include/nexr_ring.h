@@ -268,6 +268,35 @@ NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* con
 NEXR_API nexrResult_t nexrRingAllToAll(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
                                        size_t count /* elements per pair */, int datatype);
 
+/* The all-to-all with a count per pair (all_to_all_single with split sizes): counts[s*n + d] elements of `datatype`
+ * go from rank s to rank d, packed on both sides in rank order (the rule and the two residences of `counts`:
+ * nexrFlatAllToAllv, include/nexr.h; explicit displacements are not offered). sendElts[s] and recvElts[d] are the
+ * buffers' capacities in elements: host arrays, required for both residences. Additions only: the ABI stays 0.3.
+ *   Thread ranks, device memory, every rank on one GPU, 2..NEXR_SYM_MAX_RANKS ranks: ONE nexrFlatAllToAllv launch
+ *     on the communicator's first stream and the wait of the flat entries above. No connection, no step counter
+ *     and not nexrRingCommGetQueued's report is touched. Device counts (nexrScalarDevice) are read by that kernel
+ *     alone, whatever the first stream or anything ordered before the call wrote last: on a violation nothing is
+ *     written, *status (a device word, required) becomes 1 and the call returns nexrSuccess; else *status is 0.
+ *   Any other thread-rank communicator: device counts are first read to the host behind the streams' work (where
+ *     the communicator never touches HIP they are the host's own memory, as nexrScalarDevice scalars are) and then
+ *     checked as host counts; the non-empty blocks go in (d, s) order, each ONE reduce-copy through the
+ *     communicator's fn (nexrUint8, nexrDevSum), as nexrRingAllToAll's.
+ *   One rank: the one-rank copy of counts[0] elements. Process ranks: nexrInvalidUsage.
+ * Wherever the library itself holds the counts on the host (host counts on every path, device counts on every
+ * path but the one launch), a count, row sum or column sum above its capacity is nexrInvalidArgument before
+ * anything is copied, and `status`, if given, is written by the library: 1 on a violation, 0 otherwise (on a
+ * communicator that touches HIP by a copy, so the word may live in any memory the runtime knows).
+ * nexrInvalidArgument otherwise: the datatype checks of nexrRingAllGather (fp8 and unknown datatypes), and the
+ * array, residence, capacity and range checks of nexrFlatAllToAllv at any rank count. Inside nexrRingGroupStart /
+ * nexrRingGroupEnd the call is checked and recorded (host counts and both capacity arrays are copied, a device
+ * pointer is kept) and runs alone at its place (`singles`). Host counts above a capacity are refused when the call
+ * is made, as every other refusal (`status`, if given, becomes 1; nothing is recorded); device counts are looked at
+ * only when the call runs, at the End. On a broken communicator the one launch is nexrInvalidUsage, as the flat
+ * entries above. Measured numbers: DESIGN §8.13. */
+NEXR_API nexrResult_t nexrRingAllToAllv(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                        const uint64_t* counts, int residence, int datatype,
+                                        const size_t* sendElts, const size_t* recvElts, uint32_t* status);
+
 /* Opt-in, off by default: which plain calls on an eligible communicator run as their flat entries above. `on`
  * is read as bits: NEXR_FLAT_RING (1) routes nexrRingAllReduce, nexrRingReduceScatter and nexrRingReduce;
  * NEXR_FLAT_TREE (2) routes nexrTreeAllReduce; NEXR_FLAT_COPIES (4) routes nexrRingAllGather and
@@ -365,7 +394,7 @@ NEXR_API nexrResult_t nexrRingGroupGetStats(nexrRingComm_t comm, nexrRingGroupSt
  * A device-resident scalar on those device-memory flat calls is not read by the host at all: the kernel reads it
  * (also when all n turn out equal), so what the communicator's first stream, or anything ordered before the
  * call, wrote last is what counts. */
-typedef enum { nexrScalarDevice = 0, nexrScalarHostImmediate = 1 } nexrScalarResidence_t; /* = ncclScalarResidence_t */
+/* nexrScalarResidence_t (nexrScalarDevice = 0, nexrScalarHostImmediate = 1): include/nexr.h. */
 NEXR_API nexrResult_t nexrRingRedOpCreatePreMulSum(nexrRingComm_t comm, int* op, const void* const* scalars,
                                                    int datatype, int residence);
 NEXR_API nexrResult_t nexrRingRedOpDestroy(nexrRingComm_t comm, int op);

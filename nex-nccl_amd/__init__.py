@@ -97,7 +97,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrFlatTreeAllReducePreMul",
                "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
                "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
-               "nexrFlatGroup", "nexrFlatGroupPlan", "nexrFlatAllToAll",
+               "nexrFlatGroup", "nexrFlatGroupPlan", "nexrFlatAllToAll", "nexrFlatAllToAllv",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -400,6 +400,8 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatGroupPlan.restype = i32
     L.nexrFlatAllToAll.argtypes = [i32, P(vp), P(vp), sz, i32, vp]
     L.nexrFlatAllToAll.restype = i32
+    L.nexrFlatAllToAllv.argtypes = [i32, P(vp), P(vp), vp, i32, sz, P(sz), P(sz), vp, i32, vp]
+    L.nexrFlatAllToAllv.restype = i32
     L.nexrGetFlatHostStats.argtypes = [P(FlatHostStats), i32]
     L.nexrGetFlatHostStats.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
@@ -1138,6 +1140,33 @@ def flat_all_to_all(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int,
     rc = lib().nexrFlatAllToAll(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
                                 int(max_workgroups), ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatAllToAll")
+
+
+def _size_array(values: Sequence[int]):
+    return (ctypes.c_size_t * max(1, len(values)))(*[int(v) for v in values])
+
+
+def flat_all_to_all_v(inputs: Sequence[int], outputs: Sequence[int], counts, esz: int, in_elts: Sequence[int],
+                      out_elts: Sequence[int], status: int = 0, max_workgroups: int = 0,
+                      stream: Optional[int] = None) -> None:
+    """The all-to-all with a count per pair in ONE launch (``nexrFlatAllToAllv``): ``counts[s*n + d]`` elements of
+    ``esz`` bytes go from ``inputs[s]`` to ``outputs[d]``, packed on both sides in rank order (all_to_all_single with
+    split sizes). ``counts`` is a sequence of n*n integers (host counts, read before the call returns, sums above a
+    capacity are InvalidArgument) or an ``int``: the address of n*n uint64 in device memory, read by the kernel
+    alone, which writes nothing and sets the device word ``status`` to 1 on a violation (0 otherwise).
+    ``in_elts`` / ``out_elts`` are the buffers' capacities in elements. Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    if isinstance(counts, int):
+        residence, arg, keep = 0, ctypes.c_void_p(counts), None  # nexrScalarDevice
+    else:
+        keep = (ctypes.c_uint64 * max(1, len(counts)))(*[int(c) for c in counts])
+        residence, arg = 1, ctypes.cast(keep, ctypes.c_void_p)   # nexrScalarHostImmediate
+    rc = lib().nexrFlatAllToAllv(len(inputs), _ptr_array(inputs), _ptr_array(outputs), arg, residence, int(esz),
+                                 _size_array(in_elts), _size_array(out_elts),
+                                 ctypes.c_void_p(int(status)) if status else None, int(max_workgroups),
+                                 ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllToAllv")
 
 
 # ---- the flat collectives over host memory (nexrFlatHost*): the device forms' arguments, host addresses -------------

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "nexr_internal.h"
+#include "nexr_exchange_v_checks.h"
 
 namespace nexr {
 namespace {
@@ -2863,6 +2864,101 @@ NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, vo
   uint64_t grid = std::min<uint64_t>((p.nItems + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
   if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
   NEXR_HIP(launch_flat_alltoall(p, bytes, (unsigned)grid, (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+// ---- nexrFlatAllToAllv ------------------------------------------------------------------------------------------
+namespace {
+// Workgroups of flat_exchange_v_kernel the current device keeps resident, the default cap of its grid: per CU eight
+// (what the kernel's registers admit at 256 threads), or as many as find their 16 * n * n bytes of LDS in a CU's
+// 160 KiB where that is fewer (36 ranks and more: two at 64). 2,048 on the 256 CUs of an MI355X up to 35 ranks, which
+// is what DESIGN 8.13 measured; nothing above 16 ranks has been measured.
+nexrResult_t flatExchangeVResident(int n, uint64_t* resident) {
+  constexpr int kDevs = 16;
+  static std::atomic<int> cusOf[kDevs];
+  int dev = 0;
+  NEXR_HIP(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < kDevs;
+  int cus = cached ? cusOf[dev].load(std::memory_order_relaxed) : 0;
+  if (cus <= 0) {
+    NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (cached && cus > 0) cusOf[dev].store(cus, std::memory_order_relaxed);
+  }
+  const uint64_t perCu = std::min<uint64_t>(8, (uint64_t)(160 << 10) / ((uint64_t)16 * n * n));
+  *resident = std::max<uint64_t>(perCu * (uint64_t)std::max(cus, 1), 1);
+  return nexrSuccess;
+}
+}  // namespace
+
+// Every check before any device call. Host counts are summed here and size the grid exactly; device counts are
+// never read here, and the grid comes from the capacities (the kernel derives the true item count itself).
+NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, void* const* outputs,
+                                        const uint64_t* counts, int residence, size_t esz, const size_t* inElts,
+                                        const size_t* outElts, uint32_t* status, int maxWorkgroups,
+                                        nexrStream_t stream) {
+  if (!inputs || !outputs || !counts || !inElts || !outElts || maxWorkgroups < 0) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return nexrInvalidArgument;
+  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
+  const bool dev = residence == nexrScalarDevice;
+  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
+  const int n = nRanks;
+  if (!nexr_exchange_v::buffersOk(n, inputs, outputs, inElts, outElts, esz, counts, status, dev))
+    return nexrInvalidArgument;
+  FlatExchangeVParams p;
+  memset((void*)&p, 0, sizeof(p));
+  for (int r = 0; r < n; r++) {
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+    p.inElts[r] = inElts[r];
+    p.outElts[r] = outElts[r];
+  }
+  uint64_t items = 0;
+  if (dev) {
+    for (int d = 0; d < n; d++) items += ((uint64_t)outElts[d] * esz + 2047) / 2048;
+  } else {
+    uint64_t col[NEXR_SYM_MAX_RANKS];
+    if (!nexr_exchange_v::countsFit(n, counts, inElts, outElts, col)) return nexrInvalidArgument;
+    for (int d = 0; d < n; d++) items += (col[d] * esz + 2047) / 2048;
+    if (items == 0) return nexrSuccess;
+  }
+  p.status = status;
+  p.nRanks = n;
+  p.shift = esz == 1 ? 0 : esz == 2 ? 1 : esz == 4 ? 2 : 3;
+  // a wave per item, four waves per workgroup, up to the workgroups the device keeps resident: beyond that the
+  // waves stride, so that a workgroup's prologue serves many pieces and not four. Device counts with no capacity
+  // at all still launch one workgroup: the verdict is the kernel's.
+  uint64_t resident = 0;
+  const nexrResult_t res = flatExchangeVResident(n, &resident);
+  if (res != nexrSuccess) return res;
+  uint64_t grid = std::min<uint64_t>(std::max<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), 1), resident);
+  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
+  hipStream_t s = (hipStream_t)stream;
+  uint64_t* ws = nullptr;
+  const int words = n * n;
+  if (dev) {
+    p.ext = counts;
+  } else if (n <= kFlatExchangeVInlineRanks) {
+    memcpy(p.inl, counts, (size_t)words * 8);
+  } else {  // by value in short launches ahead of the one, as nexrFlatGroup's table: nothing is read after return
+    NEXR_HIP(hipMallocAsync((void**)&ws, (size_t)words * 8, s));
+    FlatGroupFill f;
+    for (int at = 0; at < words; at += kFlatGroupFillWords) {
+      f.dst = ws + at;
+      f.n = std::min(kFlatGroupFillWords, words - at);
+      f.pad = 0;
+      memcpy(f.words, counts + at, (size_t)f.n * 8);
+      const hipError_t e = launch_flat_group_fill(f, s);
+      if (e != hipSuccess) {
+        (void)hipFreeAsync(ws, s);
+        return hipFail(e);
+      }
+    }
+    p.ext = ws;
+  }
+  const hipError_t e = launch_flat_exchange_v(p, (unsigned)grid, s);
+  if (ws) (void)hipFreeAsync(ws, s);
+  NEXR_HIP(e);
   return nexrSuccess;
 }
 

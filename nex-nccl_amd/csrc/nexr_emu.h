@@ -230,6 +230,12 @@ struct nexrRingComm {
     std::vector<void*> recv;
     size_t count = 0;
     int datatype = 0, op = 0, root = 0, nBlocks = 0;
+    // nexrRingAllToAllv: host counts and both capacity arrays by value; device counts by their address
+    std::vector<uint64_t> counts;
+    std::vector<size_t> sendElts, recvElts;
+    const uint64_t* countsPtr = nullptr;
+    uint32_t* status = nullptr;
+    int residence = 0;
   };
   int groupDepth = 0;
   bool groupRunning = false;

@@ -424,6 +424,24 @@ struct FlatAllToAllParams {
 static_assert(sizeof(FlatAllToAllParams) <= 4000, "kernel argument block");
 hipError_t launch_flat_alltoall(const FlatAllToAllParams& p, bool bytes, unsigned grid, hipStream_t s);
 
+// The all-to-all with a count per pair in one launch (nexrFlatAllToAllv; nexr_flat_exchange_v.hip). The kernel reads
+// the n * n counts (elements of 1 << shift bytes, [s * n + d]) from inl[] (host counts of up to
+// kFlatExchangeVInlineRanks ranks) or from `ext`: the call's stream-ordered workspace, or the caller's device
+// memory. It checks them against the capacities (elements) before it writes anything, and reports in *status.
+constexpr int kFlatExchangeVInlineRanks = NEXR_FLAT_ALLTOALLV_INLINE_RANKS;
+struct FlatExchangeVParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t inElts[NEXR_SYM_MAX_RANKS];
+  uint64_t outElts[NEXR_SYM_MAX_RANKS];
+  const uint64_t* ext;  // non-null: the counts are there, not in inl[]
+  uint32_t* status;     // null: not reported
+  int nRanks, shift;
+  uint64_t inl[kFlatExchangeVInlineRanks * kFlatExchangeVInlineRanks];
+};
+static_assert(sizeof(FlatExchangeVParams) <= 4000, "kernel argument block");
+hipError_t launch_flat_exchange_v(const FlatExchangeVParams& p, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -1202,3 +1202,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 #include "nexr_flat_group.hip"
 // The all-to-all in one launch (nexrFlatAllToAll): the same code object again.
 #include "nexr_flat_alltoall.hip"
+// The all-to-all with a count per pair, counts read on the device (nexrFlatAllToAllv): the same code object again.
+#include "nexr_flat_exchange_v.hip"

@@ -12,6 +12,7 @@
 #include <unistd.h>
 
 #include "nexr_emu.h"
+#include "nexr_exchange_v_checks.h"
 
 namespace nexr_emu {
 
@@ -1544,6 +1545,120 @@ nexrResult_t allToAll(nexrRingComm* c, const void* const* sendbuffs, void* const
   return res;
 }
 
+// nexrRingAllToAllv. The checks that need no execution and no value of the matrix (they run when a call is
+// recorded): the datatype as nexrRingAllGather's, the arrays, the residence, and the capacity ranges as
+// nexrFlatAllToAllv compares them (half-open; an empty range meets nothing).
+nexrResult_t allToAllVCheck(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs,
+                            const uint64_t* counts, int residence, int datatype, const size_t* sendElts,
+                            const size_t* recvElts, const uint32_t* status, size_t* esz) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;
+  nexrDevRedOpFull red;
+  const nexrResult_t r = prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
+  if (r != nexrSuccess) return r;
+  if (!sendbuffs || !recvbuffs || !counts || !sendElts || !recvElts) return nexrInvalidArgument;
+  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
+  const bool dev = residence == nexrScalarDevice;
+  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
+  const bool ok = nexr_exchange_v::buffersOk(c->cfg.nRanks, sendbuffs, recvbuffs, sendElts, recvElts, *esz, counts, status, dev);
+  return ok ? nexrSuccess : nexrInvalidArgument;
+}
+
+// *status where the library writes it (host counts, and every path but the one launch): a plain store on a
+// communicator that never touches HIP, else a copy to whatever memory the word lives in.
+nexrResult_t allToAllVStatus(nexrRingComm* c, uint32_t* status, uint32_t v) {
+  if (!status) return nexrSuccess;
+  if (!c->needHip) {
+    *status = v;
+    return nexrSuccess;
+  }
+  return hipMemcpy(status, &v, sizeof(v), hipMemcpyDefault) == hipSuccess ? nexrSuccess : nexrUnhandledCudaError;
+}
+
+// Whether host counts keep inside the capacities (nexr_exchange_v::countsFit, at any rank count).
+bool allToAllVFits(int n, const uint64_t* counts, const size_t* sendElts, const size_t* recvElts) {
+  std::vector<uint64_t> col((size_t)n);
+  return nexr_exchange_v::countsFit(n, counts, sendElts, recvElts, col.data());
+}
+
+// Thread ranks in device memory on one GPU: ONE nexrFlatAllToAllv launch on the first stream and symCollective's
+// wait (not symCollective itself: it refuses a null buffer, which a capacity of 0 allows here), refused as there on
+// a broken communicator; device counts are read by that kernel alone, and so is *status written. Any other thread-rank
+// communicator: device counts are read to the host behind the streams' work (the host's own memory where the
+// communicator never touches HIP), checked as host counts, and the non-empty blocks go in (d, s) order, each ONE
+// reduce-copy through the communicator's fn, as allToAll.
+nexrResult_t allToAllV(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, const uint64_t* counts,
+                       int residence, int datatype, const size_t* sendElts, const size_t* recvElts,
+                       uint32_t* status) {
+  size_t esz = 0;
+  nexrResult_t res = allToAllVCheck(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status, &esz);
+  if (res != nexrSuccess) return res;
+  const int n = c->cfg.nRanks;
+  const bool dev = residence == nexrScalarDevice;
+  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
+  bool oneGpu = device && n >= 2 && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() &&
+                c->streams[0];
+  for (int i = 0; oneGpu && i < n; i++)
+    if (c->devices[i] != c->devices[0]) oneGpu = false;
+  if (oneGpu && c->broken) return nexrInvalidUsage;
+  if (oneGpu && dev) {
+    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+    res = nexrFlatAllToAllv(n, sendbuffs, recvbuffs, counts, residence, esz, sendElts, recvElts, status, 0,
+                            (nexrStream_t)c->streams[0]);
+    return res != nexrSuccess ? res : symWait(c, c->streams[0]);
+  }
+  std::vector<uint64_t> read;
+  if (dev) {  // once per call, behind what the ranks' streams hold
+    read.resize((size_t)n * n);
+    if (!c->needHip) {
+      memcpy(read.data(), counts, read.size() * 8);
+    } else {
+      for (int i = 0; i < n; i++)
+        if (c->streams[i] && (hipSetDevice(c->devices[i]) != hipSuccess || hipStreamSynchronize(c->streams[i]) != hipSuccess))
+          return nexrUnhandledCudaError;
+      if (hipMemcpy(read.data(), counts, read.size() * 8, hipMemcpyDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return nexrUnhandledCudaError;
+      }
+    }
+    counts = read.data();
+  }
+  const bool fits = allToAllVFits(n, counts, sendElts, recvElts);
+  res = allToAllVStatus(c, status, fits ? 0u : 1u);
+  if (!fits) return nexrInvalidArgument;
+  if (res != nexrSuccess) return res;
+  if (n == 1) {
+    if (counts[0] == 0) return nexrSuccess;
+    nexrDevRedOpFull red;
+    const nexrResult_t e = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
+    return e != nexrSuccess ? e : oneRank(c, 0, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype, red, esz);
+  }
+  if (oneGpu) {  // host counts: the launch reports nothing, the verdict is above
+    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+    res = nexrFlatAllToAllv(n, sendbuffs, recvbuffs, counts, nexrScalarHostImmediate, esz, sendElts, recvElts, nullptr,
+                            0, (nexrStream_t)c->streams[0]);
+    return res != nexrSuccess ? res : symWait(c, c->streams[0]);
+  }
+  std::vector<size_t> sendOff((size_t)n, 0);  // bytes of sendbuffs[s] already sent, to ranks below d
+  for (int d = 0; d < n && res == nexrSuccess; d++) {
+    if (c->streams[d]) (void)hipSetDevice(c->devices[d]);
+    size_t recvOff = 0;
+    for (int s = 0; s < n && res == nexrSuccess; s++) {
+      const size_t bytes = (size_t)counts[(size_t)s * n + d] * esz;
+      if (bytes == 0) continue;
+      const void* src = (const char*)sendbuffs[s] + sendOff[(size_t)s];
+      void* dst = (char*)recvbuffs[d] + recvOff;
+      res = c->cfg.fn(1, &src, 1, &dst, bytes, nexrUint8, nexrDevSum, 0, 0, nullptr, 0, (nexrStream_t)c->streams[d]);
+      sendOff[(size_t)s] += bytes;
+      recvOff += bytes;
+    }
+    // also behind an error: nothing stays in flight over the caller's buffers
+    if (device && c->streams[d] && hipStreamSynchronize(c->streams[d]) != hipSuccess && res == nexrSuccess)
+      res = nexrUnhandledCudaError;
+  }
+  return res;
+}
+
 // nexrRingCommSetFlat: whether the plain ring all-reduce, reduce-scatter and reduce of this communicator run
 // flat. Thread ranks in device memory on one GPU with the library's own kernels for the protocol (a caller's
 // fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes; or thread ranks in
@@ -1699,7 +1814,8 @@ enum RingEntry {
   kEntSymAllReduce, kEntSymReduceScatter, kEntSymAllGather,
   kEntFlatAllReduce, kEntFlatReduceScatter, kEntFlatReduce, kEntFlatTree, kEntFlatBroadcast, kEntFlatAllGather,
   kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather,
-  kEntAllToAll
+  kEntAllToAll,
+  kEntAllToAllV  // recorded by nexrRingAllToAllv itself; groupExecute runs it, not runEntry
 };
 
 // The entry as it runs alone.
@@ -1989,7 +2105,13 @@ nexrResult_t groupExecute(nexrRingComm* c) {
     if (res == nexrSuccess) res = wait();
     if (res != nexrSuccess) break;
     c->groupStats.singles++;
-    res = runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
+    if (g.entry == kEntAllToAllV) {
+      DeviceGuard dg(c->needHip);
+      res = allToAllV(c, g.send.data(), g.recv.data(), g.countsPtr ? g.countsPtr : g.counts.data(), g.residence,
+                      g.datatype, g.sendElts.data(), g.recvElts.data(), g.status);
+    } else {
+      res = runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
+    }
     if (res != nexrSuccess) break;
   }
   if (res == nexrSuccess) res = flush();
@@ -2176,6 +2298,39 @@ NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* se
 NEXR_API nexrResult_t nexrRingAllToAll(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                        size_t count, int datatype) {
   return groupOrRun(c, kEntAllToAll, sendbuffs, recvbuffs, count, datatype, nexrSum, 0, 0);
+}
+
+NEXR_API nexrResult_t nexrRingAllToAllv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                        const uint64_t* counts, int residence, int datatype, const size_t* sendElts,
+                                        const size_t* recvElts, uint32_t* status) {
+  if (c && c->groupDepth > 0 && !c->groupRunning) {  // checked and recorded: host arrays by value
+    size_t esz = 0;
+    const nexrResult_t r =
+        allToAllVCheck(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status, &esz);
+    if (r != nexrSuccess) return r;
+    // host counts are here already: a violation is refused now, as the call alone answers it, and not at the End
+    if (residence == nexrScalarHostImmediate && !allToAllVFits(c->cfg.nRanks, counts, sendElts, recvElts)) {
+      (void)allToAllVStatus(c, status, 1u);
+      return nexrInvalidArgument;
+    }
+    const size_t n = (size_t)c->cfg.nRanks;
+    nexrRingComm::GroupCall g;
+    g.entry = kEntAllToAllV;
+    g.send.assign(sendbuffs, sendbuffs + n);
+    g.recv.assign(recvbuffs, recvbuffs + n);
+    g.datatype = datatype;
+    g.residence = residence;
+    g.status = status;
+    g.sendElts.assign(sendElts, sendElts + n);
+    g.recvElts.assign(recvElts, recvElts + n);
+    if (residence == nexrScalarDevice) g.countsPtr = counts;
+    else g.counts.assign(counts, counts + n * n);
+    c->groupCalls.push_back(std::move(g));
+    c->groupStats.calls++;
+    return nexrSuccess;
+  }
+  DeviceGuard dg(c && c->needHip);
+  return allToAllV(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status);
 }
 
 NEXR_API nexrResult_t nexrRingGroupStart(nexrRingComm_t c) {

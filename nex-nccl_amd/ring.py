@@ -25,6 +25,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
                     "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat", "nexrRingAllToAll",
+                    "nexrRingAllToAllv",
                     "nexrRingGroupStart", "nexrRingGroupEnd", "nexrRingGroupGetStats",
                     "nexrTreeTopology", "nexrRingRedOpCreatePreMulSum", "nexrRingRedOpDestroy",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
@@ -121,6 +122,7 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingBroadcastFlat.argtypes = [vp, arr, arr, sz, i32, i32]
     L.nexrRingAllGatherFlat.argtypes = [vp, arr, arr, sz, i32]
     L.nexrRingAllToAll.argtypes = [vp, arr, arr, sz, i32]
+    L.nexrRingAllToAllv.argtypes = [vp, arr, arr, vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
     L.nexrRingGroupStart.argtypes = [vp]
     L.nexrRingGroupEnd.argtypes = [vp]
     L.nexrRingGroupGetStats.argtypes = [vp, ctypes.POINTER(RingGroupStats), i32]
@@ -385,6 +387,23 @@ class RingComm:
         copies through the communicator's reduce-copy elsewhere; InvalidUsage for process ranks."""
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrRingAllToAll(self._h, s, r, int(count), int(datatype)), "nexrRingAllToAll")
+
+    def all_to_all_v(self, sendbuffs, recvbuffs, counts, datatype: int, send_elts, recv_elts, status: int = 0) -> None:
+        """The all-to-all with a count per pair (nexrRingAllToAllv): counts[s*n + d] elements go from rank s to
+        rank d, packed on both sides in rank order. `counts` is a sequence of n*n integers (host counts) or an int,
+        the address of n*n uint64 read while the call runs (SCALAR_DEVICE; `status`, the address of a 32-bit
+        word, is then required). send_elts / recv_elts are the buffers' capacities in elements. ONE launch on
+        thread ranks in device memory on one GPU, the non-empty blocks through the communicator's reduce-copy
+        elsewhere; InvalidUsage for process ranks."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        if isinstance(counts, int):
+            residence, arg, keep = SCALAR_DEVICE, ctypes.c_void_p(counts), None
+        else:
+            keep = (ctypes.c_uint64 * max(1, len(counts)))(*[int(c) for c in counts])
+            residence, arg = SCALAR_HOST_IMMEDIATE, ctypes.cast(keep, ctypes.c_void_p)
+        caps = [(ctypes.c_size_t * max(1, len(e)))(*[int(v) for v in e]) for e in (send_elts, recv_elts)]
+        _check(self._L.nexrRingAllToAllv(self._h, s, r, arg, residence, int(datatype), caps[0], caps[1],
+                                         ctypes.c_void_p(int(status)) if status else None), "nexrRingAllToAllv")
 
     def set_flat(self, on: bool, tree: bool = False, copies: bool = False) -> None:
         """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat). `on` (FLAT_RING):
