@@ -1236,6 +1236,72 @@ NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, v
                                         int maxWorkgroups, nexrStream_t stream);
 
 /*
+ * nexrFlatReduceScatterv, nexrFlatAllGatherv — the reduce-scatter and the all-gather with a count per rank, each in
+ * ONE launch, the counts read on the device: what n ncclReduce (root d) / n ncclBroadcast (root r) inside one group
+ * do, which is how PyTorch lowers reduce_scatter / all_gather with uneven shards (FSDP over parameters that do not
+ * divide by the world size, the expert-parallel combine behind an all-to-all-v). Additions only: the ABI stays 0.3.
+ * Device memory of the current device.
+ *
+ * The rule, for nRanks = n, esz bytes per element and counts[d] elements in piece d, both sides packed in rank
+ * order:
+ *     off(d) = sum over d' < d of counts[d'],   total = off(n).
+ * Reduce-scatter-v: inputs[r] holds at least `total` elements, piece d being its elements [off(d), off(d) +
+ *   counts[d]). outputs[d][e], e < counts[d], gets exactly the bytes nexrFlatReduce writes with root = d, nElts =
+ *   counts[d], inputs inputs[r] + off(d) * esz and the same devRedOp, redOpArg and userFirst: the ring chain of
+ *   "Rule for one element" above started at s = (d + 1) mod n, one reduce-copy step and one rounding per rank, the
+ *   fp16 / bf16 canonicalisation after every step, the pre-op on every rank's own input, the post-op on the last
+ *   step, userFirst choosing the operand order, NEXR_SEMANTICS entering as it does there. Elements of outputs[d]
+ *   behind counts[d] are not written. The ten datatypes and five device ops of nexrFlatReduceScatter; the pre-op has
+ *   one factor for the whole call (a scalar per rank is not offered here).
+ * All-gather-v: outputs[t][(off(r) + i) * esz + b] = inputs[r][i * esz + b] for i < counts[r], b < esz and every t:
+ *   a bit copy at any byte alignment, no datatype and no semantics enter; esz is 1, 2, 4 or 8. Bytes of outputs[t]
+ *   behind `total` are not written.
+ *
+ * inElts[r] and outElts[r] are the capacities of the buffers in elements: host arrays, read before the call
+ * returns, for both residences. Whatever the counts say, no byte outside a capacity range is read or written. A
+ * violation is, for the reduce-scatter, counts[d] > outElts[d] or total > inElts[r] for any r; for the all-gather,
+ * counts[r] > inElts[r] or total > outElts[t] for any t.
+ *
+ * residence == nexrScalarHostImmediate: `counts` is a host array of n words, read before the call returns. A
+ * violation is nexrInvalidArgument before any device call. The exact number of 2048-byte pieces sizes the grid.
+ * `status` may be NULL; where it is not, the launch writes 0 to it. All counts zero: success, no launch.
+ *
+ * residence == nexrScalarDevice: `counts` is device memory of the current device, 8-byte aligned, read by the
+ * kernel only: the values are whatever `stream`, or anything ordered before the call, wrote last. No host read, no
+ * synchronisation and no fill launch, so the call can be captured into a graph and replayed over rewritten counts.
+ * The grid is sized from the capacities (the pieces of outElts[d] * esz, or inElts[r] * esz, bytes per row). On a
+ * violation NOTHING is written to any output and *status (a device word, required) becomes 1; otherwise 0.
+ *
+ * How they run (nexr_flat_scatter_v.hip). The n <= 64 counts ride in the kernel arguments or are loaded from
+ * `counts`: lane d of every wave holds counts[d] and rank d's capacities, one wave-wide scan in registers gives
+ * off(d) and the total, a ballot gives the verdict: no LDS, no barrier, no workspace and no fill launch at any rank
+ * count. A second scan over the rows' piece counts maps a wave's item number to (row, piece), row after row. The
+ * reduce-scatter's wave folds two 16-byte packs per lane through the flat collectives' own chain (start rank d + 1
+ * wave-uniform, every access unaligned-capable since a piece's phase in the inputs is arbitrary, the row's last
+ * bytes below a pack one element per lane); the all-gather's wave loads each pack once and stores it to all n
+ * outputs, the block's end below a pack one byte per lane. No atomics, no polls. maxWorkgroups caps the grid (waves
+ * then stride); 0: a wave per piece, four waves per workgroup, up to the workgroups the device keeps resident.
+ *
+ * nexrInvalidArgument, before any device call, for both residences: what nexrFlatAllToAllv refuses (nRanks outside
+ * 2..NEXR_SYM_MAX_RANKS; a null array; a null buffer whose capacity is not 0; maxWorkgroups < 0; an unknown
+ * residence; a capacity above 2^56 bytes or a range that wraps; any input capacity range that meets any output
+ * capacity range, or two output ranges that meet, as half-open byte ranges; with device counts a NULL status, a
+ * misaligned `counts`, and the n * 8 bytes of `counts` or the status word meeting an output range), and for the
+ * reduce-scatter what nexrFlatReduceScatter refuses (the datatype, fp8 among them; the op; a buffer that is not
+ * element-aligned), for the all-gather an esz other than 1, 2, 4 or 8. Inputs may alias each other. In place is
+ * not offered: with device counts the host cannot know where a piece lies.
+ */
+NEXR_API nexrResult_t nexrFlatReduceScatterv(int nRanks, const void* const* inputs, void* const* outputs,
+                                             const uint64_t* counts /* n */, int residence, int datatype,
+                                             int devRedOp, uint64_t redOpArg, int userFirst, const size_t* inElts,
+                                             const size_t* outElts, uint32_t* status, int maxWorkgroups,
+                                             nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatAllGatherv(int nRanks, const void* const* inputs, void* const* outputs,
+                                         const uint64_t* counts /* n */, int residence, size_t esz,
+                                         const size_t* inElts, const size_t* outElts, uint32_t* status,
+                                         int maxWorkgroups, nexrStream_t stream);
+
+/*
  * nexrLLCleanSlot — the cleanup for callers of the single-step nexrReduceCopyLL: writes lines
  * [firstLine, slotLines) of each of the nSend (<= NEXR_MAX_DSTS) slots sendLines[i] as
  * {0, sendFlags[i], 0, sendFlags[i]}, one 16-byte system-coherent store per line, stream-ordered.

@@ -297,6 +297,38 @@ NEXR_API nexrResult_t nexrRingAllToAllv(nexrRingComm_t comm, const void* const* 
                                         const uint64_t* counts, int residence, int datatype,
                                         const size_t* sendElts, const size_t* recvElts, uint32_t* status);
 
+/* The reduce-scatter and the all-gather with a count per rank (reduce_scatter / all_gather with uneven shards, which
+ * c10d lowers to n ncclReduce / n ncclBroadcast in a group): counts[d] elements of `datatype` make piece d, packed on
+ * both sides in rank order (the rule, the violations and the two residences of `counts`: nexrFlatReduceScatterv /
+ * nexrFlatAllGatherv, include/nexr.h). sendElts[r] and recvElts[r] are the buffers' capacities in elements: host
+ * arrays, required for both residences. Additions only: the ABI stays 0.3.
+ *   Thread ranks, device memory, every rank on one GPU, 2..NEXR_SYM_MAX_RANKS ranks, the library's own fn / llFn /
+ *     ll128Fn, and for the reduce-scatter a built-in op, nexrAvg or a user-created PreMulSum handle whose scalars
+ *     are bit-equal: ONE nexrFlatReduceScatterv / nexrFlatAllGatherv launch on the communicator's first stream and
+ *     the wait of the flat entries above, the operand order the protocol's as for nexrRingReduceFlat. No connection,
+ *     no step counter and not nexrRingCommGetQueued's report is touched. Device counts are read by that kernel
+ *     alone: on a violation nothing is written, *status (a device word, required) becomes 1 and the call returns
+ *     nexrSuccess; else *status is 0.
+ *   Any other thread-rank communicator (host memory, ranks on several GPUs, a caller's fn, a handle whose scalars
+ *     differ): device counts are first read to the host behind the streams' work and checked as host counts; the
+ *     non-empty pieces then run in rank order as the communicator's own nexrRingReduce with root d on piece d of
+ *     every sendbuff, or nexrRingBroadcast with root r of sendbuffs[r] into every recvbuff at off(r). Every path
+ *     gives the same bytes.
+ *   One rank: the one-rank path over counts[0] elements. Process ranks: nexrInvalidUsage.
+ * Wherever the library itself holds the counts on the host, a violation is nexrInvalidArgument before anything runs
+ * and `status`, if given, is written by the library (1, else 0), as nexrRingAllToAllv does. nexrInvalidArgument
+ * otherwise: the op and datatype checks of nexrRingReduce (the all-gather: of nexrRingAllGather), and the array,
+ * residence, capacity and range checks of the flat entries at any rank count. Inside nexrRingGroupStart /
+ * nexrRingGroupEnd the call is checked and recorded with nexrRingAllToAllv's rules (host counts and both capacity
+ * arrays are copied and a violation is refused at once; a device pointer is kept and looked at at the End) and
+ * runs alone at its place (`singles`). Measured numbers: DESIGN §8.14. */
+NEXR_API nexrResult_t nexrRingReduceScatterv(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                             const uint64_t* counts, int residence, int datatype, int op,
+                                             const size_t* sendElts, const size_t* recvElts, uint32_t* status);
+NEXR_API nexrResult_t nexrRingAllGatherv(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                         const uint64_t* counts, int residence, int datatype,
+                                         const size_t* sendElts, const size_t* recvElts, uint32_t* status);
+
 /* Opt-in, off by default: which plain calls on an eligible communicator run as their flat entries above. `on`
  * is read as bits: NEXR_FLAT_RING (1) routes nexrRingAllReduce, nexrRingReduceScatter and nexrRingReduce;
  * NEXR_FLAT_TREE (2) routes nexrTreeAllReduce; NEXR_FLAT_COPIES (4) routes nexrRingAllGather and

@@ -98,6 +98,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
                "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
                "nexrFlatGroup", "nexrFlatGroupPlan", "nexrFlatAllToAll", "nexrFlatAllToAllv",
+               "nexrFlatReduceScatterv", "nexrFlatAllGatherv",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -402,6 +403,10 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatAllToAll.restype = i32
     L.nexrFlatAllToAllv.argtypes = [i32, P(vp), P(vp), vp, i32, sz, P(sz), P(sz), vp, i32, vp]
     L.nexrFlatAllToAllv.restype = i32
+    L.nexrFlatReduceScatterv.argtypes = [i32, P(vp), P(vp), vp, i32, i32, i32, u64, i32, P(sz), P(sz), vp, i32, vp]
+    L.nexrFlatReduceScatterv.restype = i32
+    L.nexrFlatAllGatherv.argtypes = [i32, P(vp), P(vp), vp, i32, sz, P(sz), P(sz), vp, i32, vp]
+    L.nexrFlatAllGatherv.restype = i32
     L.nexrGetFlatHostStats.argtypes = [P(FlatHostStats), i32]
     L.nexrGetFlatHostStats.restype = i32
     L.nexrSymLLWindowBytes.argtypes = [i32, i32, P(sz)]
@@ -1167,6 +1172,51 @@ def flat_all_to_all_v(inputs: Sequence[int], outputs: Sequence[int], counts, esz
                                  ctypes.c_void_p(int(status)) if status else None, int(max_workgroups),
                                  ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatAllToAllv")
+
+
+def _counts_arg(counts):
+    """(residence, argument, what keeps it alive) of a count list (host) or an int (a device address)."""
+    if isinstance(counts, int):
+        return 0, ctypes.c_void_p(counts), None  # nexrScalarDevice
+    keep = (ctypes.c_uint64 * max(1, len(counts)))(*[int(c) for c in counts])
+    return 1, ctypes.cast(keep, ctypes.c_void_p), keep  # nexrScalarHostImmediate
+
+
+def flat_reduce_scatter_v(inputs: Sequence[int], outputs: Sequence[int], counts, datatype: int, dev_red_op: int,
+                          red_op_arg: int, user_first: bool, in_elts: Sequence[int], out_elts: Sequence[int],
+                          status: int = 0, max_workgroups: int = 0, stream: Optional[int] = None) -> None:
+    """The reduce-scatter with a count per rank in ONE launch (``nexrFlatReduceScatterv``): piece d of every input,
+    ``counts[d]`` elements behind the pieces below it, is folded as ``flat_reduce`` with root d folds it and lands at
+    the front of ``outputs[d]`` (reduce_scatter with uneven shards). ``counts`` is a sequence of n integers (host
+    counts; a count above ``out_elts[d]`` or a total above any ``in_elts[r]`` is InvalidArgument) or an ``int``: the
+    address of n uint64 in device memory, read by the kernel alone, which writes nothing and sets the device word
+    ``status`` to 1 on a violation (0 otherwise). Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    residence, arg, _keep = _counts_arg(counts)
+    rc = lib().nexrFlatReduceScatterv(len(inputs), _ptr_array(inputs), _ptr_array(outputs), arg, residence,
+                                      int(datatype), int(dev_red_op), int(red_op_arg), 1 if user_first else 0,
+                                      _size_array(in_elts), _size_array(out_elts),
+                                      ctypes.c_void_p(int(status)) if status else None, int(max_workgroups),
+                                      ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatReduceScatterv")
+
+
+def flat_all_gather_v(inputs: Sequence[int], outputs: Sequence[int], counts, esz: int, in_elts: Sequence[int],
+                      out_elts: Sequence[int], status: int = 0, max_workgroups: int = 0,
+                      stream: Optional[int] = None) -> None:
+    """The all-gather with a count per rank in ONE launch (``nexrFlatAllGatherv``): the first ``counts[r]`` elements
+    of ``esz`` bytes of ``inputs[r]`` land behind the blocks of the ranks below r in every output, a bit copy at any
+    byte alignment (all_gather with uneven shards). ``counts``, the capacities and ``status`` as
+    flat_reduce_scatter_v: a violation is a count above ``in_elts[r]`` or a total above any ``out_elts[t]``."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    residence, arg, _keep = _counts_arg(counts)
+    rc = lib().nexrFlatAllGatherv(len(inputs), _ptr_array(inputs), _ptr_array(outputs), arg, residence, int(esz),
+                                  _size_array(in_elts), _size_array(out_elts),
+                                  ctypes.c_void_p(int(status)) if status else None, int(max_workgroups),
+                                  ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllGatherv")
 
 
 # ---- the flat collectives over host memory (nexrFlatHost*): the device forms' arguments, host addresses -------------

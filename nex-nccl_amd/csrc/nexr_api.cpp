@@ -2282,9 +2282,8 @@ NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, vo
 // launch_simple_group: fork changes the dispatch type; shipped folds nothing, and what survives is the first
 // operand of the chain's last step).
 namespace {
-nexrResult_t flatPrepare(int nRanks, const void* const* inputs, int datatype, int devRedOp, uint64_t redOpArg,
-                         int userFirst, FlatParams* p, int* dt, int* op) {
-  if (!inputs) return nexrInvalidArgument;
+// The rank count, datatype and op that a flat reduction takes.
+nexrResult_t flatOpCheck(int nRanks, int datatype, int devRedOp, uint64_t redOpArg) {
   if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
   if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
     return nexrInvalidArgument;
@@ -2295,23 +2294,47 @@ nexrResult_t flatPrepare(int nRanks, const void* const* inputs, int datatype, in
     if (divisor == 0) divisor = 1;
     if ((int8_t)divisor == 0) return nexrInvalidArgument;
   }
+  return nexrSuccess;
+}
+
+// What the semantics make of a checked call: the dispatch and the fields that flat_fold reads (FlatParams' names).
+struct FlatSemantics {
+  int dt, op, nFold, shift, preOp, postOp;
+};
+FlatSemantics flatSemantics(int nRanks, int datatype, int devRedOp, int userFirst) {
+  int srcIsInput = 1, postOp = 1, firstWins = 0;
+  FlatSemantics m;
+  m.dt = datatype;
+  m.op = devRedOp;
+  llSemantics(&m.dt, &m.op, &srcIsInput, &postOp, &firstWins);
+  m.nFold = firstWins ? 1 : nRanks;
+  m.shift = firstWins && userFirst ? nRanks - 1 : 0;
+  m.preOp = srcIsInput;
+  m.postOp = postOp;
+  return m;
+}
+
+nexrResult_t flatPrepare(int nRanks, const void* const* inputs, int datatype, int devRedOp, uint64_t redOpArg,
+                         int userFirst, FlatParams* p, int* dt, int* op) {
+  if (!inputs) return nexrInvalidArgument;
+  const nexrResult_t res = flatOpCheck(nRanks, datatype, devRedOp, redOpArg);
+  if (res != nexrSuccess) return res;
   const uint64_t esz = typeSize(datatype);
   memset((void*)p, 0, sizeof(*p));
   for (int r = 0; r < nRanks; r++) {
     if (!inputs[r] || ((uintptr_t)inputs[r] & (esz - 1))) return nexrInvalidArgument;
     p->in[r] = (const char*)inputs[r];
   }
-  int srcIsInput = 1, postOp = 1, firstWins = 0;
-  *dt = datatype;
-  *op = devRedOp;
-  llSemantics(dt, op, &srcIsInput, &postOp, &firstWins);
+  const FlatSemantics m = flatSemantics(nRanks, datatype, devRedOp, userFirst);
+  *dt = m.dt;
+  *op = m.op;
   p->nRanks = nRanks;
   p->redArg = redOpArg;
   p->userFirst = userFirst ? 1 : 0;
-  p->nFold = firstWins ? 1 : nRanks;
-  p->shift = firstWins && userFirst ? nRanks - 1 : 0;
-  p->preOp = srcIsInput;
-  p->postOp = postOp;
+  p->nFold = m.nFold;
+  p->shift = m.shift;
+  p->preOp = m.preOp;
+  p->postOp = m.postOp;
   return nexrSuccess;
 }
 
@@ -2873,6 +2896,7 @@ namespace {
 // (what the kernel's registers admit at 256 threads), or as many as find their 16 * n * n bytes of LDS in a CU's
 // 160 KiB where that is fewer (36 ranks and more: two at 64). 2,048 on the 256 CUs of an MI355X up to 35 ranks, which
 // is what DESIGN 8.13 measured; nothing above 16 ranks has been measured.
+// n == 0: a kernel without LDS (nexr_flat_scatter_v.hip), eight per CU at any rank count.
 nexrResult_t flatExchangeVResident(int n, uint64_t* resident) {
   constexpr int kDevs = 16;
   static std::atomic<int> cusOf[kDevs];
@@ -2884,7 +2908,7 @@ nexrResult_t flatExchangeVResident(int n, uint64_t* resident) {
     NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     if (cached && cus > 0) cusOf[dev].store(cus, std::memory_order_relaxed);
   }
-  const uint64_t perCu = std::min<uint64_t>(8, (uint64_t)(160 << 10) / ((uint64_t)16 * n * n));
+  const uint64_t perCu = n ? std::min<uint64_t>(8, (uint64_t)(160 << 10) / ((uint64_t)16 * n * n)) : 8;
   *resident = std::max<uint64_t>(perCu * (uint64_t)std::max(cus, 1), 1);
   return nexrSuccess;
 }
@@ -2959,6 +2983,110 @@ NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, v
   const hipError_t e = launch_flat_exchange_v(p, (unsigned)grid, s);
   if (ws) (void)hipFreeAsync(ws, s);
   NEXR_HIP(e);
+  return nexrSuccess;
+}
+
+// ---- nexrFlatReduceScatterv, nexrFlatAllGatherv -----------------------------------------------------------------
+namespace {
+// The checks the two share with nexrFlatAllToAllv (arrays, residence, capacities, ranges), the host counts' fit,
+// and the launch's parameters but for what the reduction adds. *items: the 2048-byte pieces that size the grid,
+// exact under host counts (0: nothing to do), those of the capacities under device counts.
+nexrResult_t flatScatterVCheck(int n, const void* const* inputs, void* const* outputs, const uint64_t* counts,
+                               int residence, size_t esz, const size_t* inElts, const size_t* outElts,
+                               uint32_t* status, int maxWorkgroups, bool scatter, FlatScatterVParams* pp,
+                               uint64_t* items) {
+  FlatScatterVParams& p = *pp;
+  if (!inputs || !outputs || !counts || !inElts || !outElts || maxWorkgroups < 0) return nexrInvalidArgument;
+  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
+  const bool dev = residence == nexrScalarDevice;
+  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
+  if (!nexr_exchange_v::buffersOk(n, inputs, outputs, inElts, outElts, esz, counts, status, dev, (size_t)n))
+    return nexrInvalidArgument;
+  const size_t* own = scatter ? outElts : inElts;  // the capacities of the buffers that hold one piece
+  *items = 0;
+  if (dev) {
+    for (int d = 0; d < n; d++) *items += ((uint64_t)own[d] * esz + 2047) / 2048;
+    p.ext = counts;
+  } else {
+    uint64_t total = 0;
+    if (!nexr_exchange_v::piecesFit(n, counts, inElts, outElts, scatter, &total)) return nexrInvalidArgument;
+    for (int d = 0; d < n; d++) *items += (counts[d] * esz + 2047) / 2048;
+    memcpy(p.counts, counts, (size_t)n * 8);
+  }
+  for (int r = 0; r < n; r++) {
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+    p.inElts[r] = inElts[r];
+    p.outElts[r] = outElts[r];
+  }
+  p.status = status;
+  p.nRanks = n;
+  p.eszShift = esz == 1 ? 0 : esz == 2 ? 1 : esz == 4 ? 2 : 3;
+  return nexrSuccess;
+}
+
+// A wave per item, four waves per workgroup, up to the workgroups the device keeps resident; beyond that, and
+// under maxWorkgroups, the waves stride. Device counts with no capacity at all still launch one workgroup: the
+// verdict is the kernel's.
+nexrResult_t flatScatterVGrid(uint64_t items, int maxWorkgroups, unsigned* grid) {
+  uint64_t resident = 0;
+  const nexrResult_t res = flatExchangeVResident(0, &resident);
+  if (res != nexrSuccess) return res;
+  uint64_t g = std::min<uint64_t>(std::max<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), 1), resident);
+  if (maxWorkgroups > 0 && g > (uint64_t)maxWorkgroups) g = (uint64_t)maxWorkgroups;
+  *grid = (unsigned)g;
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatReduceScatterv(int nRanks, const void* const* inputs, void* const* outputs,
+                                             const uint64_t* counts, int residence, int datatype, int devRedOp,
+                                             uint64_t redOpArg, int userFirst, const size_t* inElts,
+                                             const size_t* outElts, uint32_t* status, int maxWorkgroups,
+                                             nexrStream_t stream) {
+  nexrResult_t res = flatOpCheck(nRanks, datatype, devRedOp, redOpArg);
+  if (res != nexrSuccess) return res;
+  const size_t esz = typeSize(datatype);
+  FlatScatterVParams p;
+  memset((void*)&p, 0, sizeof(p));
+  uint64_t items = 0;
+  res = flatScatterVCheck(nRanks, inputs, outputs, counts, residence, esz, inElts, outElts, status, maxWorkgroups,
+                          true, &p, &items);
+  if (res != nexrSuccess) return res;
+  for (int r = 0; r < nRanks; r++)
+    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
+  if (residence == nexrScalarHostImmediate && items == 0) return nexrSuccess;
+  const FlatSemantics m = flatSemantics(nRanks, datatype, devRedOp, userFirst);
+  p.redArg = redOpArg;
+  p.userFirst = userFirst ? 1 : 0;
+  p.nFold = m.nFold;
+  p.shift = m.shift;
+  p.preOp = m.preOp;
+  p.postOp = m.postOp;
+  unsigned grid = 0;
+  res = flatScatterVGrid(items, maxWorkgroups, &grid);
+  if (res != nexrSuccess) return res;
+  NEXR_HIP(launch_flat_scatter_v(m.dt, m.op, p, grid, (hipStream_t)stream));
+  return nexrSuccess;
+}
+
+NEXR_API nexrResult_t nexrFlatAllGatherv(int nRanks, const void* const* inputs, void* const* outputs,
+                                         const uint64_t* counts, int residence, size_t esz, const size_t* inElts,
+                                         const size_t* outElts, uint32_t* status, int maxWorkgroups,
+                                         nexrStream_t stream) {
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return nexrInvalidArgument;
+  FlatScatterVParams p;
+  memset((void*)&p, 0, sizeof(p));
+  uint64_t items = 0;
+  nexrResult_t res = flatScatterVCheck(nRanks, inputs, outputs, counts, residence, esz, inElts, outElts, status,
+                                       maxWorkgroups, false, &p, &items);
+  if (res != nexrSuccess) return res;
+  if (residence == nexrScalarHostImmediate && items == 0) return nexrSuccess;
+  unsigned grid = 0;
+  res = flatScatterVGrid(items, maxWorkgroups, &grid);
+  if (res != nexrSuccess) return res;
+  NEXR_HIP(launch_flat_gather_v(p, grid, (hipStream_t)stream));
   return nexrSuccess;
 }
 

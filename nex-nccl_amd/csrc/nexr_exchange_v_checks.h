@@ -1,6 +1,7 @@
 // nexr_exchange_v_checks.h — the checks of the all-to-all with a count per pair that need no device, shared by
 // nexrFlatAllToAllv (nexr_api.cpp) and nexrRingAllToAllv (nexr_ring.cpp, at any rank count): the half-open range
-// rule and the bound on a capacity stand here and nowhere else.
+// rule and the bound on a capacity stand here and nowhere else. The reduce-scatter and the all-gather with a count
+// per rank (nexrFlatReduceScatterv, nexrFlatAllGatherv and their ring entries) share them, with n counts.
 #pragma once
 
 #include <stddef.h>
@@ -18,16 +19,18 @@ struct Range {  // half-open; an empty range meets nothing, one that ends where 
 
 // The checks that read no count: every capacity within kMaxBytes and inside the address space, a buffer wherever a
 // capacity is not 0, no output range meeting an input range or another output range (in place is not offered; inputs
-// may alias each other) and, with device counts, none meeting the n * n counts or the status word.
+// may alias each other) and, with device counts, none meeting the counts (n * n of them, or countWords) or the
+// status word.
 inline bool buffersOk(int n, const void* const* in, void* const* out, const size_t* inElts, const size_t* outElts,
-                      size_t esz, const uint64_t* counts, const uint32_t* status, bool deviceCounts) {
+                      size_t esz, const uint64_t* counts, const uint32_t* status, bool deviceCounts,
+                      size_t countWords = 0) {
   auto range = [esz](const void* p, size_t elts) { return Range{(uintptr_t)p, (uintptr_t)p + elts * esz}; };
   for (int r = 0; r < n; r++) {
     if (inElts[r] > kMaxBytes / esz || outElts[r] > kMaxBytes / esz) return false;
     if ((inElts[r] && !in[r]) || (outElts[r] && !out[r])) return false;
     if (range(in[r], inElts[r]).end < (uintptr_t)in[r] || range(out[r], outElts[r]).end < (uintptr_t)out[r]) return false;
   }
-  const Range cnt = {(uintptr_t)counts, (uintptr_t)counts + (uintptr_t)n * n * 8u};
+  const Range cnt = {(uintptr_t)counts, (uintptr_t)counts + (countWords ? countWords : (uintptr_t)n * n) * 8u};
   const Range word = {(uintptr_t)status, (uintptr_t)status + 4u};
   for (int d = 0; d < n; d++) {
     const Range o = range(out[d], outElts[d]);
@@ -53,6 +56,23 @@ inline bool countsFit(int n, const uint64_t* counts, const size_t* inElts, const
       colSum[d] += c;
       if (row > inElts[s] || colSum[d] > outElts[d]) return false;
     }
+  }
+  return true;
+}
+
+// The same for a count per rank (host counts). scatter: piece d goes to out[d] alone and every in[r] holds all of
+// them (the reduce-scatter); else piece r comes from in[r] alone and every out[t] holds all of them (the all-gather).
+inline bool piecesFit(int n, const uint64_t* counts, const size_t* inElts, const size_t* outElts, bool scatter,
+                      uint64_t* total) {
+  const size_t* own = scatter ? outElts : inElts;
+  const size_t* all = scatter ? inElts : outElts;
+  uint64_t least = ~(uint64_t)0;
+  for (int r = 0; r < n; r++) least = all[r] < least ? all[r] : least;
+  *total = 0;
+  for (int d = 0; d < n; d++) {
+    if (counts[d] > own[d]) return false;
+    *total += counts[d];
+    if (*total > least) return false;
   }
   return true;
 }

@@ -442,6 +442,28 @@ struct FlatExchangeVParams {
 static_assert(sizeof(FlatExchangeVParams) <= 4000, "kernel argument block");
 hipError_t launch_flat_exchange_v(const FlatExchangeVParams& p, unsigned grid, hipStream_t s);
 
+// The reduce-scatter and the all-gather with a count per rank in one launch (nexrFlatReduceScatterv,
+// nexrFlatAllGatherv; nexr_flat_scatter_v.hip). The kernel reads the n counts (elements of 1 << eszShift bytes)
+// from counts[] (host counts) or from `ext` (the caller's device memory), checks them against the capacities
+// (elements) before it writes anything, and reports in *status. The fields flat_fold reads carry FlatParams'
+// names and meanings; the all-gather uses none of them.
+struct FlatScatterVParams {
+  static constexpr bool kPerRank = false;  // one pre-op factor for the call: redArg
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t inElts[NEXR_SYM_MAX_RANKS];
+  uint64_t outElts[NEXR_SYM_MAX_RANKS];
+  uint64_t counts[NEXR_SYM_MAX_RANKS];
+  const uint64_t* ext;  // non-null: the counts are there, not in counts[]
+  uint32_t* status;     // null: not reported
+  uint64_t redArg;
+  int nRanks, eszShift;
+  int nFold, shift, userFirst, preOp, postOp, pad;
+};
+static_assert(sizeof(FlatScatterVParams) <= 4000, "kernel argument block");
+hipError_t launch_flat_scatter_v(int dt, int op, const FlatScatterVParams& p, unsigned grid, hipStream_t s);
+hipError_t launch_flat_gather_v(const FlatScatterVParams& p, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

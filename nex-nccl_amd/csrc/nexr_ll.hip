@@ -1204,3 +1204,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 #include "nexr_flat_alltoall.hip"
 // The all-to-all with a count per pair, counts read on the device (nexrFlatAllToAllv): the same code object again.
 #include "nexr_flat_exchange_v.hip"
+// The reduce-scatter and the all-gather with a count per rank (nexrFlatReduceScatterv, nexrFlatAllGatherv): again.
+#include "nexr_flat_scatter_v.hip"

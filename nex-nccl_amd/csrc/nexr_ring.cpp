@@ -1815,7 +1815,8 @@ enum RingEntry {
   kEntFlatAllReduce, kEntFlatReduceScatter, kEntFlatReduce, kEntFlatTree, kEntFlatBroadcast, kEntFlatAllGather,
   kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather,
   kEntAllToAll,
-  kEntAllToAllV  // recorded by nexrRingAllToAllv itself; groupExecute runs it, not runEntry
+  kEntAllToAllV,  // recorded by nexrRingAllToAllv itself; groupExecute runs it, not runEntry
+  kEntReduceScatterV, kEntAllGatherV  // likewise, by nexrRingReduceScatterv / nexrRingAllGatherv (scatterVRecord)
 };
 
 // The entry as it runs alone.
@@ -1902,6 +1903,144 @@ nexrResult_t runEntry(nexrRingComm* c, int entry, const void* const* sendbuffs, 
     }
   }
   return nexrInvalidArgument;
+}
+
+// nexrRingReduceScatterv (scatter) and nexrRingAllGatherv. The checks that need no execution and no value of the
+// counts (they run when a call is recorded; readResident: whether a user op's device-resident scalars are read,
+// which a recording does not do): the op as nexrRingReduce's or the datatype as nexrRingAllGather's, the arrays,
+// the residence, and the capacity ranges as nexrFlatReduceScatterv compares them.
+nexrResult_t scatterVCheck(nexrRingComm* c, bool scatter, const void* const* sendbuffs, void* const* recvbuffs,
+                           const uint64_t* counts, int residence, int datatype, int op, const size_t* sendElts,
+                           const size_t* recvElts, const uint32_t* status, bool readResident, size_t* esz,
+                           RedOps* ops) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;
+  nexrDevRedOpFull red;
+  const nexrResult_t r = scatter ? prepareOps(c, datatype, op, esz, ops, readResident)
+                                 : prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
+  if (r != nexrSuccess) return r;
+  if (!sendbuffs || !recvbuffs || !counts || !sendElts || !recvElts) return nexrInvalidArgument;
+  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
+  const bool dev = residence == nexrScalarDevice;
+  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
+  const int n = c->cfg.nRanks;
+  const bool ok = nexr_exchange_v::buffersOk(n, sendbuffs, recvbuffs, sendElts, recvElts, *esz, counts, status, dev,
+                                             (size_t)n);
+  return ok ? nexrSuccess : nexrInvalidArgument;
+}
+
+// Thread ranks in device memory on one GPU with the library's own step functions, and an op that one redOpArg
+// serves: ONE nexrFlatReduceScatterv / nexrFlatAllGatherv launch on the first stream and symCollective's wait, as
+// allToAllV; device counts are read by that kernel alone, and so is *status written. Any other thread-rank
+// communicator, and a user op whose ranks' scalars differ: device counts are read to the host behind the streams'
+// work, checked as host counts, and the non-empty pieces run in rank order as the communicator's own
+// nexrRingReduce (root d) / nexrRingBroadcast (root r) on the piece, whose bytes the one launch's are.
+nexrResult_t scatterV(nexrRingComm* c, bool scatter, const void* const* sendbuffs, void* const* recvbuffs,
+                      const uint64_t* counts, int residence, int datatype, int op, const size_t* sendElts,
+                      const size_t* recvElts, uint32_t* status) {
+  size_t esz = 0;
+  RedOps ops;
+  nexrResult_t res = scatterVCheck(c, scatter, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
+                                   recvElts, status, true, &esz, &ops);
+  if (res != nexrSuccess) return res;
+  const int n = c->cfg.nRanks;
+  const bool dev = residence == nexrScalarDevice;
+  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
+  bool one = device && n >= 2 && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() &&
+             c->streams[0] && !(scatter && ops.perRank(true));
+  one = one && (c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
+                : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
+                                                 : c->cfg.fn == defaultDeviceFn);
+  for (int i = 0; one && i < n; i++)
+    if (c->devices[i] != c->devices[0]) one = false;
+  auto launch = [&](const uint64_t* cnt, int where, uint32_t* word) -> nexrResult_t {
+    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+    const nexrStream_t s = (nexrStream_t)c->streams[0];
+    const nexrResult_t r =
+        scatter ? nexrFlatReduceScatterv(n, sendbuffs, recvbuffs, cnt, where, datatype, ops.rank[0].op,
+                                         ops.rank[0].scalarArg, c->proto == nexrRingProtoSimple ? 1 : 0, sendElts,
+                                         recvElts, word, 0, s)
+                : nexrFlatAllGatherv(n, sendbuffs, recvbuffs, cnt, where, esz, sendElts, recvElts, word, 0, s);
+    return r != nexrSuccess ? r : symWait(c, c->streams[0]);
+  };
+  if (one && dev) return launch(counts, residence, status);
+  std::vector<uint64_t> read;
+  if (dev) {  // once per call, behind what the ranks' streams hold
+    read.resize((size_t)n);
+    if (!c->needHip) {
+      memcpy(read.data(), counts, read.size() * 8);
+    } else {
+      for (int i = 0; i < n; i++)
+        if (c->streams[i] && (hipSetDevice(c->devices[i]) != hipSuccess || hipStreamSynchronize(c->streams[i]) != hipSuccess))
+          return nexrUnhandledCudaError;
+      if (hipMemcpy(read.data(), counts, read.size() * 8, hipMemcpyDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        return nexrUnhandledCudaError;
+      }
+    }
+    counts = read.data();
+  }
+  uint64_t total = 0;
+  const bool fits = nexr_exchange_v::piecesFit(n, counts, sendElts, recvElts, scatter, &total);
+  res = allToAllVStatus(c, status, fits ? 0u : 1u);
+  if (!fits) return nexrInvalidArgument;
+  if (res != nexrSuccess) return res;
+  if (n == 1) {
+    if (counts[0] == 0) return nexrSuccess;
+    nexrDevRedOpFull red;
+    if (scatter) red = ops.rank[0];
+    else if ((res = nexrHostToDevRedOp(&red, nexrSum, datatype, 1)) != nexrSuccess) return res;
+    return oneRank(c, 0, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype, red, esz);
+  }
+  if (one) return total ? launch(counts, nexrScalarHostImmediate, nullptr) : nexrSuccess;  // the verdict is above
+  std::vector<const void*> ins((size_t)n);
+  std::vector<void*> outs((size_t)n);
+  size_t off = 0;  // bytes of the pieces below this one
+  for (int d = 0; d < n && res == nexrSuccess; d++) {
+    if (counts[d] == 0) continue;
+    for (int i = 0; i < n; i++) {
+      ins[(size_t)i] = scatter ? (const char*)sendbuffs[i] + off : sendbuffs[d];
+      outs[(size_t)i] = scatter ? recvbuffs[d] : (char*)recvbuffs[i] + off;
+    }
+    res = runEntry(c, scatter ? kEntReduce : kEntBroadcast, ins.data(), outs.data(), (size_t)counts[d], datatype,
+                   scatter ? op : nexrSum, d, 0);
+    off += (size_t)counts[d] * esz;
+  }
+  return res;
+}
+
+// A nexrRingReduceScatterv / nexrRingAllGatherv call inside a group: checked and recorded, host arrays by value,
+// with nexrRingAllToAllv's rules (host counts above a capacity are refused now, with their report).
+nexrResult_t scatterVRecord(nexrRingComm* c, int entry, bool scatter, const void* const* sendbuffs,
+                            void* const* recvbuffs, const uint64_t* counts, int residence, int datatype, int op,
+                            const size_t* sendElts, const size_t* recvElts, uint32_t* status) {
+  size_t esz = 0;
+  RedOps ops;
+  const nexrResult_t r = scatterVCheck(c, scatter, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
+                                       recvElts, status, false, &esz, &ops);
+  if (r != nexrSuccess) return r;
+  const size_t n = (size_t)c->cfg.nRanks;
+  uint64_t total = 0;
+  if (residence == nexrScalarHostImmediate &&
+      !nexr_exchange_v::piecesFit((int)n, counts, sendElts, recvElts, scatter, &total)) {
+    (void)allToAllVStatus(c, status, 1u);
+    return nexrInvalidArgument;
+  }
+  nexrRingComm::GroupCall g;
+  g.entry = entry;
+  g.send.assign(sendbuffs, sendbuffs + n);
+  g.recv.assign(recvbuffs, recvbuffs + n);
+  g.datatype = datatype;
+  g.op = op;
+  g.residence = residence;
+  g.status = status;
+  g.sendElts.assign(sendElts, sendElts + n);
+  g.recvElts.assign(recvElts, recvElts + n);
+  if (residence == nexrScalarDevice) g.countsPtr = counts;
+  else g.counts.assign(counts, counts + n);
+  c->groupCalls.push_back(std::move(g));
+  c->groupStats.calls++;
+  return nexrSuccess;
 }
 
 bool entryReduces(int e) {
@@ -2109,6 +2248,11 @@ nexrResult_t groupExecute(nexrRingComm* c) {
       DeviceGuard dg(c->needHip);
       res = allToAllV(c, g.send.data(), g.recv.data(), g.countsPtr ? g.countsPtr : g.counts.data(), g.residence,
                       g.datatype, g.sendElts.data(), g.recvElts.data(), g.status);
+    } else if (g.entry == kEntReduceScatterV || g.entry == kEntAllGatherV) {
+      DeviceGuard dg(c->needHip);
+      res = scatterV(c, g.entry == kEntReduceScatterV, g.send.data(), g.recv.data(),
+                     g.countsPtr ? g.countsPtr : g.counts.data(), g.residence, g.datatype, g.op, g.sendElts.data(),
+                     g.recvElts.data(), g.status);
     } else {
       res = runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
     }
@@ -2331,6 +2475,26 @@ NEXR_API nexrResult_t nexrRingAllToAllv(nexrRingComm_t c, const void* const* sen
   }
   DeviceGuard dg(c && c->needHip);
   return allToAllV(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status);
+}
+
+NEXR_API nexrResult_t nexrRingReduceScatterv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                             const uint64_t* counts, int residence, int datatype, int op,
+                                             const size_t* sendElts, const size_t* recvElts, uint32_t* status) {
+  if (c && c->groupDepth > 0 && !c->groupRunning)
+    return scatterVRecord(c, kEntReduceScatterV, true, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
+                          recvElts, status);
+  DeviceGuard dg(c && c->needHip);
+  return scatterV(c, true, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts, recvElts, status);
+}
+
+NEXR_API nexrResult_t nexrRingAllGatherv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                         const uint64_t* counts, int residence, int datatype,
+                                         const size_t* sendElts, const size_t* recvElts, uint32_t* status) {
+  if (c && c->groupDepth > 0 && !c->groupRunning)
+    return scatterVRecord(c, kEntAllGatherV, false, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum,
+                          sendElts, recvElts, status);
+  DeviceGuard dg(c && c->needHip);
+  return scatterV(c, false, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum, sendElts, recvElts, status);
 }
 
 NEXR_API nexrResult_t nexrRingGroupStart(nexrRingComm_t c) {

@@ -25,7 +25,7 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
                     "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat", "nexrRingAllToAll",
-                    "nexrRingAllToAllv",
+                    "nexrRingAllToAllv", "nexrRingReduceScatterv", "nexrRingAllGatherv",
                     "nexrRingGroupStart", "nexrRingGroupEnd", "nexrRingGroupGetStats",
                     "nexrTreeTopology", "nexrRingRedOpCreatePreMulSum", "nexrRingRedOpDestroy",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
@@ -123,6 +123,8 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingAllGatherFlat.argtypes = [vp, arr, arr, sz, i32]
     L.nexrRingAllToAll.argtypes = [vp, arr, arr, sz, i32]
     L.nexrRingAllToAllv.argtypes = [vp, arr, arr, vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+    L.nexrRingReduceScatterv.argtypes = [vp, arr, arr, vp, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+    L.nexrRingAllGatherv.argtypes = [vp, arr, arr, vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
     L.nexrRingGroupStart.argtypes = [vp]
     L.nexrRingGroupEnd.argtypes = [vp]
     L.nexrRingGroupGetStats.argtypes = [vp, ctypes.POINTER(RingGroupStats), i32]
@@ -404,6 +406,37 @@ class RingComm:
         caps = [(ctypes.c_size_t * max(1, len(e)))(*[int(v) for v in e]) for e in (send_elts, recv_elts)]
         _check(self._L.nexrRingAllToAllv(self._h, s, r, arg, residence, int(datatype), caps[0], caps[1],
                                          ctypes.c_void_p(int(status)) if status else None), "nexrRingAllToAllv")
+
+    def _v_args(self, counts, send_elts, recv_elts, status):
+        if isinstance(counts, int):
+            residence, arg, keep = SCALAR_DEVICE, ctypes.c_void_p(counts), None
+        else:
+            keep = (ctypes.c_uint64 * max(1, len(counts)))(*[int(c) for c in counts])
+            residence, arg = SCALAR_HOST_IMMEDIATE, ctypes.cast(keep, ctypes.c_void_p)
+        caps = [(ctypes.c_size_t * max(1, len(e)))(*[int(v) for v in e]) for e in (send_elts, recv_elts)]
+        return arg, residence, caps, ctypes.c_void_p(int(status)) if status else None, keep
+
+    def reduce_scatter_v(self, sendbuffs, recvbuffs, counts, datatype: int, op: int, send_elts, recv_elts,
+                         status: int = 0) -> None:
+        """The reduce-scatter with a count per rank (nexrRingReduceScatterv): piece d of every sendbuff, counts[d]
+        elements behind the pieces below it, is reduced as reduce(root=d) reduces it, into the front of
+        recvbuffs[d]. `counts` is a sequence of n integers (host counts) or an int, the address of n uint64 read
+        while the call runs (SCALAR_DEVICE; `status`, the address of a 32-bit word, is then required). ONE launch
+        on thread ranks in device memory on one GPU with the library's own kernels, the non-empty pieces as
+        reduce calls elsewhere, the same bytes either way; InvalidUsage for process ranks."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        arg, residence, caps, word, _keep = self._v_args(counts, send_elts, recv_elts, status)
+        _check(self._L.nexrRingReduceScatterv(self._h, s, r, arg, residence, int(datatype), int(op), caps[0], caps[1],
+                                              word), "nexrRingReduceScatterv")
+
+    def all_gather_v(self, sendbuffs, recvbuffs, counts, datatype: int, send_elts, recv_elts, status: int = 0) -> None:
+        """The all-gather with a count per rank (nexrRingAllGatherv): the first counts[r] elements of sendbuffs[r]
+        land behind the blocks of the ranks below r in every recvbuff, a bit copy. Arguments and paths as
+        reduce_scatter_v, the pieces as broadcast calls elsewhere."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        arg, residence, caps, word, _keep = self._v_args(counts, send_elts, recv_elts, status)
+        _check(self._L.nexrRingAllGatherv(self._h, s, r, arg, residence, int(datatype), caps[0], caps[1], word),
+               "nexrRingAllGatherv")
 
     def set_flat(self, on: bool, tree: bool = False, copies: bool = False) -> None:
         """Opt in to (or out of) flat launches for the plain calls (nexrRingCommSetFlat). `on` (FLAT_RING):
