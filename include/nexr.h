@@ -1171,6 +1171,49 @@ NEXR_API nexrResult_t nexrFlatGroupPlan(int nRanks, const nexrFlatGroupWork* wor
 NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, void* const* outputs,
                                        size_t nBytes /* per pair */, int maxWorkgroups, nexrStream_t stream);
 
+/*
+ * nexrFlatAllToAll2D, nexrFlatAllGather2D — the all-to-all along a dimension other than the outermost one, and the
+ * all-gather that concatenates along the last dimension, each in ONE launch: what nexrFlatAllToAll or an all-gather
+ * plus one or two permuting copies (permute().contiguous() on every rank's buffer) do today. Additions only: the
+ * ABI stays 0.3. Device memory of the current device.
+ *
+ * n ranks, R rows, B = nBytes per block row. A layout says how a buffer of n * R * B bytes is arranged:
+ *     nexrLayoutBlocks: [n][R][B], at(k, r) = k * R * B + r * B
+ *     nexrLayoutRows:   [R][n][B], at(k, r) = r * n * B + k * B
+ * The pitched all-to-all, for all s, d < n, r < R, i < B:
+ *     outputs[d][at_out(s, r) + i] = inputs[s][at_in(d, r) + i]
+ * (rows -> blocks) is the forward exchange of Ulysses sequence parallelism, [S/P, H, D] -> [S, H/P, D] with
+ * R = S/P and B = (H/P) * D elements; (blocks -> rows) is its backward; (rows -> rows) exchanges between
+ * token-major buffers; (blocks -> blocks), or R == 1 under any layouts, is nexrFlatAllToAll with R * B bytes per
+ * pair, and the host hands those calls to that entry.
+ * The last-dim all-gather: every input is [R][B], every output [R][n][B]:
+ *     outputs[d][r * n * B + s * B + i] = inputs[s][r * B + i]        for every d.
+ * Both are bit copies at any byte alignment of the bases: no datatype enters, and neither does NEXR_SEMANTICS.
+ *
+ * How it runs (nexr_flat_pitched.hip). One kernel serves both; to it a side is two strides filled in by the host.
+ * A wave takes one piece of one OUTPUT buffer in address order, so consecutive waves write consecutive addresses
+ * whatever R and B are, and each lane derives the rank and row of its two access units from their place in the
+ * output. The host picks the unit: 16 bytes where B % 16 == 0, 4 where B % 4 == 0, else 1, so that no unit
+ * straddles two block rows; the piece is 128 units. A block row of one piece or more selects between two
+ * scalar-loaded pointers; a smaller one keeps rank k's pointer in lane k, and a 16-byte block row still fills all
+ * 64 lanes. No table, no workspace, no atomics, no polls. The call is stream-ordered and nothing of the caller's
+ * arrays is read after it returns, so it can be captured into a graph. maxWorkgroups as in nexrFlatAllToAll.
+ * rows == 0 or nBytes == 0 succeeds without a launch. Measured numbers: DESIGN §8.15 (tools/pitched_probe.py).
+ *
+ * nexrInvalidArgument, before any device call: nRanks outside 2..NEXR_SYM_MAX_RANKS; a null array or a null entry;
+ * a layout other than 0 or 1; maxWorkgroups < 0; rows above 2^31 - 1; n * rows * nBytes beyond size_t; any input
+ * range (n * R * B bytes; R * B for the gather) that meets any output range, or two output ranges that meet
+ * (half-open byte ranges: one that ends where the other begins is accepted). In place is not offered. Inputs may
+ * alias each other.
+ */
+typedef enum { nexrLayoutBlocks = 0, nexrLayoutRows = 1 } nexrLayout_t;
+NEXR_API nexrResult_t nexrFlatAllToAll2D(int nRanks, const void* const* inputs, void* const* outputs, size_t rows,
+                                         size_t nBytes /* per block row */, int inLayout, int outLayout,
+                                         int maxWorkgroups, nexrStream_t stream);
+NEXR_API nexrResult_t nexrFlatAllGather2D(int nRanks, const void* const* inputs, void* const* outputs, size_t rows,
+                                          size_t nBytes /* per row of an input */, int maxWorkgroups,
+                                          nexrStream_t stream);
+
 /* Where a value the library needs lives: in device memory, dereferenced on the device while the call runs, or in
  * host memory, read before the call returns. Used by nexrFlatAllToAllv below and by the user-created reduction ops
  * of include/nexr_ring.h. */

@@ -268,6 +268,32 @@ NEXR_API nexrResult_t nexrRingAllGatherFlat(nexrRingComm_t comm, const void* con
 NEXR_API nexrResult_t nexrRingAllToAll(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
                                        size_t count /* elements per pair */, int datatype);
 
+/* The all-to-all along an inner dimension and the all-gather along the last one (the rule and the two layouts:
+ * nexrFlatAllToAll2D / nexrFlatAllGather2D, include/nexr.h; `count` is the elements of one block row, so a buffer
+ * holds nRanks*rows*count elements, a sendbuff of the gather rows*count). Rows in and blocks out is the forward
+ * exchange of Ulysses sequence parallelism, blocks in and rows out its backward. A bit copy: every datatype the
+ * all-gather takes. Additions only: the ABI stays 0.3. Routed exactly as nexrRingAllToAll:
+ *   Thread ranks, device memory, every rank on one GPU, at most NEXR_SYM_MAX_RANKS ranks: ONE nexrFlatAllToAll2D /
+ *     nexrFlatAllGather2D launch on the communicator's first stream through the helper of the flat entries above
+ *     and its wait. No connection, no step counter and not nexrRingCommGetQueued's report is touched.
+ *   Any other thread-rank communicator: the block rows in (d, s, r) order, each ONE reduce-copy through the
+ *     communicator's fn on the receiving rank (nexrUint8, nexrDevSum, count * esz elements); where a pair's rows
+ *     are contiguous on both sides (blocks in and blocks out, or rows == 1) they go as one copy of rows * count *
+ *     esz elements. The call returns with the outputs complete.
+ *   One rank: the one-rank copy of rows*count elements. rows == 0 or count == 0 succeeds. Process ranks:
+ *     nexrInvalidUsage.
+ * nexrInvalidArgument as nexrRingAllToAll answers it (a null array, a null buffer, an unknown datatype, fp8
+ * included; a broken communicator is nexrInvalidUsage), and for a layout other than 0 or 1, rows above 2^31 - 1,
+ * nRanks*rows*count*esz beyond size_t, a send range that meets a receive range or two receive ranges that meet
+ * (half-open byte ranges). In place is not offered. Inside nexrRingGroupStart / nexrRingGroupEnd the call is
+ * checked and recorded and runs alone at its place (`singles`). Measured numbers: DESIGN §8.15. */
+NEXR_API nexrResult_t nexrRingAllToAll2D(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                         size_t rows, size_t count /* elements per block row */, int datatype,
+                                         int inLayout, int outLayout);
+NEXR_API nexrResult_t nexrRingAllGather2D(nexrRingComm_t comm, const void* const* sendbuffs, void* const* recvbuffs,
+                                          size_t rows, size_t count /* elements per row of a sendbuff */,
+                                          int datatype);
+
 /* The all-to-all with a count per pair (all_to_all_single with split sizes): counts[s*n + d] elements of `datatype`
  * go from rank s to rank d, packed on both sides in rank order (the rule and the two residences of `counts`:
  * nexrFlatAllToAllv, include/nexr.h; explicit displacements are not offered). sendElts[s] and recvElts[d] are the

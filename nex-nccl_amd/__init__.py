@@ -98,7 +98,7 @@ ABI_SYMBOLS = ("nexrReduceCopy", "nexrReduceCopyBatch", "nexrReduceCopyMultiDevi
                "nexrFlatHostAllReduce", "nexrFlatHostReduceScatter", "nexrFlatHostReduce",
                "nexrFlatHostTreeAllReduce", "nexrFlatHostBroadcast", "nexrFlatHostAllGather", "nexrGetFlatHostStats",
                "nexrFlatGroup", "nexrFlatGroupPlan", "nexrFlatAllToAll", "nexrFlatAllToAllv",
-               "nexrFlatReduceScatterv", "nexrFlatAllGatherv",
+               "nexrFlatReduceScatterv", "nexrFlatAllGatherv", "nexrFlatAllToAll2D", "nexrFlatAllGather2D",
                "nexrLLCleanSlot", "nexrQueryLaunch", "nexrGetPoolStats", "nexrTypeSize", "nexrGetErrorString", "nexrGetVersion",
                "nexrGetLastHipError", "nexrSetSemantics", "nexrGetSemantics", "nexrHostRegister", "nexrHostDeregister",
                "nexrHostMemAlloc", "nexrHostMemFree", "nexrGetHostPathStats")
@@ -403,6 +403,10 @@ def lib() -> ctypes.CDLL:
     L.nexrFlatAllToAll.restype = i32
     L.nexrFlatAllToAllv.argtypes = [i32, P(vp), P(vp), vp, i32, sz, P(sz), P(sz), vp, i32, vp]
     L.nexrFlatAllToAllv.restype = i32
+    L.nexrFlatAllToAll2D.argtypes = [i32, P(vp), P(vp), sz, sz, i32, i32, i32, vp]
+    L.nexrFlatAllToAll2D.restype = i32
+    L.nexrFlatAllGather2D.argtypes = [i32, P(vp), P(vp), sz, sz, i32, vp]
+    L.nexrFlatAllGather2D.restype = i32
     L.nexrFlatReduceScatterv.argtypes = [i32, P(vp), P(vp), vp, i32, i32, i32, u64, i32, P(sz), P(sz), vp, i32, vp]
     L.nexrFlatReduceScatterv.restype = i32
     L.nexrFlatAllGatherv.argtypes = [i32, P(vp), P(vp), vp, i32, sz, P(sz), P(sz), vp, i32, vp]
@@ -1145,6 +1149,38 @@ def flat_all_to_all(inputs: Sequence[int], outputs: Sequence[int], n_bytes: int,
     rc = lib().nexrFlatAllToAll(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(n_bytes),
                                 int(max_workgroups), ctypes.c_void_p(int(stream)) if stream else None)
     _check(rc, "nexrFlatAllToAll")
+
+
+LAYOUT_BLOCKS = 0  # nexrLayoutBlocks: a buffer is [n][R][B]
+LAYOUT_ROWS = 1    # nexrLayoutRows: a buffer is [R][n][B]
+
+
+def flat_all_to_all_2d(inputs: Sequence[int], outputs: Sequence[int], rows: int, n_bytes: int, in_layout: int,
+                       out_layout: int, max_workgroups: int = 0, stream: Optional[int] = None) -> None:
+    """The pitched all-to-all in ONE launch (``nexrFlatAllToAll2D``): ``outputs[d][at_out(s, r) + i] =
+    inputs[s][at_in(d, r) + i]`` for ``r < rows`` and ``i < n_bytes``, where ``LAYOUT_BLOCKS`` is ``at(k, r) =
+    (k*rows + r) * n_bytes`` and ``LAYOUT_ROWS`` is ``at(k, r) = (r*n + k) * n_bytes``. Rows in and blocks out is the
+    Ulysses forward exchange, blocks in and rows out its backward. A bit copy at any byte alignment; inputs and
+    outputs must not overlap (InvalidArgument). Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatAllToAll2D(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(rows), int(n_bytes),
+                                  int(in_layout), int(out_layout), int(max_workgroups),
+                                  ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllToAll2D")
+
+
+def flat_all_gather_2d(inputs: Sequence[int], outputs: Sequence[int], rows: int, n_bytes: int,
+                       max_workgroups: int = 0, stream: Optional[int] = None) -> None:
+    """The all-gather along the last dimension in ONE launch (``nexrFlatAllGather2D``): every input is
+    ``[rows][n_bytes]``, every output ``[rows][n][n_bytes]``, ``outputs[d][(r*n + s) * n_bytes + i] =
+    inputs[s][r*n_bytes + i]``. A bit copy at any byte alignment; inputs and outputs must not overlap
+    (InvalidArgument). Stream-ordered."""
+    if len(inputs) != len(outputs):
+        raise NexrError(Result.InvalidArgument, "one input and one output per rank")
+    rc = lib().nexrFlatAllGather2D(len(inputs), _ptr_array(inputs), _ptr_array(outputs), int(rows), int(n_bytes),
+                                   int(max_workgroups), ctypes.c_void_p(int(stream)) if stream else None)
+    _check(rc, "nexrFlatAllGather2D")
 
 
 def _size_array(values: Sequence[int]):

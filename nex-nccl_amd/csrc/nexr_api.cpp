@@ -2890,6 +2890,75 @@ NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, vo
   return nexrSuccess;
 }
 
+// ---- nexrFlatAllToAll2D, nexrFlatAllGather2D ----------------------------------------------------------------------
+namespace {
+// Every check before any device call, then the launch. A side's two strides follow from its layout; the gather is
+// the exchange whose source has no block stride and the input's own row pitch, written rows out. The host picks the
+// access width so that no unit can straddle two block rows.
+nexrResult_t flatPitched(int nRanks, const void* const* inputs, void* const* outputs, size_t rows, size_t nBytes,
+                         int inLayout, int outLayout, bool gather, int maxWorkgroups, nexrStream_t stream) {
+  if (!inputs || !outputs || maxWorkgroups < 0) return nexrInvalidArgument;
+  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
+  if ((inLayout != nexrLayoutBlocks && inLayout != nexrLayoutRows) ||
+      (outLayout != nexrLayoutBlocks && outLayout != nexrLayoutRows))
+    return nexrInvalidArgument;
+  if (rows > (size_t)0x7fffffff) return nexrInvalidArgument;
+  const size_t n = (size_t)nRanks;
+  if (rows && nBytes > (size_t)-1 / n / rows) return nexrInvalidArgument;  // a buffer's n * rows * nBytes bytes
+  const uintptr_t outLen = (uintptr_t)(n * rows * nBytes), inLen = gather ? (uintptr_t)(rows * nBytes) : outLen;
+  FlatPitchedParams p;
+  memset((void*)&p, 0, sizeof(p));
+  for (int r = 0; r < nRanks; r++) {
+    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
+    p.in[r] = (const char*)inputs[r];
+    p.out[r] = (char*)outputs[r];
+  }
+  auto hit = [](const void* a, uintptr_t aLen, const void* b, uintptr_t bLen) {
+    return (uintptr_t)a < (uintptr_t)b + bLen && (uintptr_t)b < (uintptr_t)a + aLen;
+  };
+  for (int d = 0; d < nRanks && outLen; d++) {
+    for (int s = 0; s < nRanks; s++)
+      if (hit(outputs[d], outLen, inputs[s], inLen)) return nexrInvalidArgument;  // in place is not offered
+    for (int e = 0; e < d; e++)
+      if (hit(outputs[d], outLen, outputs[e], outLen)) return nexrInvalidArgument;
+  }
+  if (outLen == 0) return nexrSuccess;
+  if (!gather && (rows == 1 || (inLayout == nexrLayoutBlocks && outLayout == nexrLayoutBlocks)))
+    return nexrFlatAllToAll(nRanks, inputs, outputs, rows * nBytes, maxWorkgroups, stream);
+  const uint64_t B = nBytes;
+  const int width = (B & 15u) == 0 ? 16 : (B & 3u) == 0 ? 4 : 1;
+  p.runBytes = B;
+  p.inBlock = gather ? 0 : inLayout == nexrLayoutBlocks ? (uint64_t)rows * B : B;
+  p.inPitch = gather || inLayout == nexrLayoutBlocks ? B : (uint64_t)n * B;
+  p.outBlock = outLayout == nexrLayoutBlocks ? (uint64_t)rows * B : B;
+  p.outPitch = outLayout == nexrLayoutBlocks ? B : (uint64_t)n * B;
+  p.inner = outLayout == nexrLayoutBlocks ? (uint32_t)rows : (uint32_t)n;
+  p.outBytes = outLen;
+  p.nRuns = (uint64_t)n * rows;
+  p.nRanks = nRanks;
+  const uint64_t piece = (uint64_t)128 * (uint64_t)width;
+  p.piecesPer = p.outBytes / piece + (p.outBytes % piece ? 1 : 0);
+  p.nItems = p.piecesPer * (uint64_t)n;
+  // a wave per item, four waves per workgroup; beyond the cap the waves stride
+  uint64_t grid = std::min<uint64_t>((p.nItems + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
+  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
+  NEXR_HIP(launch_flat_pitched(p, width, (unsigned)grid, (hipStream_t)stream));
+  return nexrSuccess;
+}
+}  // namespace
+
+NEXR_API nexrResult_t nexrFlatAllToAll2D(int nRanks, const void* const* inputs, void* const* outputs, size_t rows,
+                                         size_t nBytes, int inLayout, int outLayout, int maxWorkgroups,
+                                         nexrStream_t stream) {
+  return flatPitched(nRanks, inputs, outputs, rows, nBytes, inLayout, outLayout, false, maxWorkgroups, stream);
+}
+
+NEXR_API nexrResult_t nexrFlatAllGather2D(int nRanks, const void* const* inputs, void* const* outputs, size_t rows,
+                                          size_t nBytes, int maxWorkgroups, nexrStream_t stream) {
+  return flatPitched(nRanks, inputs, outputs, rows, nBytes, nexrLayoutRows, nexrLayoutRows, true, maxWorkgroups,
+                     stream);
+}
+
 // ---- nexrFlatAllToAllv ------------------------------------------------------------------------------------------
 namespace {
 // Workgroups of flat_exchange_v_kernel the current device keeps resident, the default cap of its grid: per CU eight

@@ -236,6 +236,9 @@ struct nexrRingComm {
     const uint64_t* countsPtr = nullptr;
     uint32_t* status = nullptr;
     int residence = 0;
+    // nexrRingAllToAll2D / nexrRingAllGather2D: the rows and the two layouts (`count` is a block row's elements)
+    size_t rows = 0;
+    int inLayout = 0, outLayout = 0;
   };
   int groupDepth = 0;
   bool groupRunning = false;

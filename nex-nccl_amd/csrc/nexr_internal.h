@@ -464,6 +464,26 @@ static_assert(sizeof(FlatScatterVParams) <= 4000, "kernel argument block");
 hipError_t launch_flat_scatter_v(int dt, int op, const FlatScatterVParams& p, unsigned grid, hipStream_t s);
 hipError_t launch_flat_gather_v(const FlatScatterVParams& p, unsigned grid, hipStream_t s);
 
+// The pitched all-to-all and the last-dim all-gather in one launch (nexrFlatAllToAll2D, nexrFlatAllGather2D;
+// nexr_flat_pitched.hip). Run (s, r) of rank d's output is read at in[s] + d * inBlock + r * inPitch; the output is
+// cut into piecesPer pieces of 128 * width bytes in address order, and run g of it is (g / inner, g % inner): (s, r)
+// with blocks out (outBlock > outPitch, inner = rows), (r, s) with rows out (inner = nRanks). in[] leads the block:
+// the kernel reads both arrays by their byte offsets.
+struct FlatPitchedParams {
+  const char* in[NEXR_SYM_MAX_RANKS];
+  char* out[NEXR_SYM_MAX_RANKS];
+  uint64_t runBytes;  // B
+  uint64_t inBlock, inPitch, outBlock, outPitch;
+  uint64_t outBytes;  // nRanks * rows * B
+  uint64_t nRuns;     // nRanks * rows
+  uint64_t piecesPer;
+  uint64_t nItems;  // nRanks * piecesPer
+  uint32_t inner;
+  int nRanks;
+};
+static_assert(sizeof(FlatPitchedParams) <= 4000, "kernel argument block");
+hipError_t launch_flat_pitched(const FlatPitchedParams& p, int width, unsigned grid, hipStream_t s);
+
 // A batch of independent reduce-copies with the same (datatype, op, K) in one launch.
 constexpr int kMaxBatch = 14;  // keeps the parameter block under the 4 KiB kernel-argument limit
 struct BatchParams {

@@ -1206,3 +1206,5 @@ hipError_t ll128_group_blocks_per_cu(int dt, int op, int* blocks) {
 #include "nexr_flat_exchange_v.hip"
 // The reduce-scatter and the all-gather with a count per rank (nexrFlatReduceScatterv, nexrFlatAllGatherv): again.
 #include "nexr_flat_scatter_v.hip"
+// The pitched all-to-all and the last-dim all-gather (nexrFlatAllToAll2D, nexrFlatAllGather2D): again.
+#include "nexr_flat_pitched.hip"

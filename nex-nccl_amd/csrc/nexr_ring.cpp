@@ -1545,6 +1545,92 @@ nexrResult_t allToAll(nexrRingComm* c, const void* const* sendbuffs, void* const
   return res;
 }
 
+// nexrRingAllToAll2D and nexrRingAllGather2D (gather). The checks that need no execution (a recorded call runs
+// them when it is made): the arguments as allToAllCheck's, the layouts, rows below 2^31, and the byte ranges as
+// nexrFlatAllToAll2D compares them (half-open; a send range is rows * count elements for the gather).
+nexrResult_t pitchedCheck(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs,
+                          size_t rows, size_t count, int datatype, int inLayout, int outLayout, size_t* esz) {
+  if (!c) return nexrInvalidArgument;
+  if (c->peer) return nexrInvalidUsage;
+  nexrDevRedOpFull red;
+  const nexrResult_t r = prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
+  if (r != nexrSuccess) return r;
+  const int n = c->cfg.nRanks;
+  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
+  if ((inLayout != nexrLayoutBlocks && inLayout != nexrLayoutRows) ||
+      (outLayout != nexrLayoutBlocks && outLayout != nexrLayoutRows))
+    return nexrInvalidArgument;
+  if (rows > (size_t)0x7fffffff) return nexrInvalidArgument;
+  if (rows && count > (size_t)-1 / *esz / (size_t)n / rows) return nexrInvalidArgument;
+  if (rows == 0 || count == 0) return nexrSuccess;
+  const uintptr_t out = (uintptr_t)n * rows * count * *esz, in = gather ? (uintptr_t)(rows * count * *esz) : out;
+  for (int i = 0; i < n; i++)
+    if (!sendbuffs[i] || !recvbuffs[i]) return nexrInvalidArgument;
+  for (int d = 0; d < n && n > 1; d++) {
+    for (int s = 0; s < n; s++)
+      if ((uintptr_t)recvbuffs[d] < (uintptr_t)sendbuffs[s] + in && (uintptr_t)sendbuffs[s] < (uintptr_t)recvbuffs[d] + out)
+        return nexrInvalidArgument;
+    for (int e = 0; e < d; e++)
+      if ((uintptr_t)recvbuffs[d] < (uintptr_t)recvbuffs[e] + out && (uintptr_t)recvbuffs[e] < (uintptr_t)recvbuffs[d] + out)
+        return nexrInvalidArgument;
+  }
+  return nexrSuccess;
+}
+
+// Routed as allToAll. Thread ranks in device memory on one GPU: ONE nexrFlatAllToAll2D / nexrFlatAllGather2D launch
+// on the first stream through symCollective and its wait. Any other thread-rank communicator: the block rows in
+// (d, s, r) order, each ONE reduce-copy with one source and one destination on the receiving rank (uint8, Sum); where
+// the rows of a pair are contiguous on both sides (blocks in and blocks out, or one row) they go as one copy. The
+// call returns with the outputs complete.
+nexrResult_t pitched(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs, size_t rows,
+                     size_t count, int datatype, int inLayout, int outLayout) {
+  size_t esz = 0;
+  const nexrResult_t r = pitchedCheck(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout, &esz);
+  if (r != nexrSuccess || rows == 0 || count == 0) return r;
+  const int n = c->cfg.nRanks;
+  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
+  bool oneGpu = device && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() && c->streams[0];
+  for (int i = 0; oneGpu && i < n; i++)
+    if (c->devices[i] != c->devices[0]) oneGpu = false;
+  if (n == 1) {  // both layouts of one rank are the rows in order
+    nexrDevRedOpFull red;
+    const nexrResult_t e = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
+    return e != nexrSuccess ? e : oneRank(c, 0, sendbuffs[0], recvbuffs[0], rows * count, datatype, red, esz);
+  }
+  size_t B = count * esz;
+  if (oneGpu)
+    return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
+      return gather ? nexrFlatAllGather2D(nr, sendbuffs, recvbuffs, rows, B, 0, stream)
+                    : nexrFlatAllToAll2D(nr, sendbuffs, recvbuffs, rows, B, inLayout, outLayout, 0, stream);
+    });
+  // the strides of nexr_flat_pitched.hip: run (s, r) of rank d is read at d * inBlock + r * inPitch and written at
+  // s * outBlock + r * outPitch
+  const size_t nn = (size_t)n;
+  const size_t inBlock = gather ? 0 : inLayout == nexrLayoutBlocks ? rows * B : B;
+  size_t inPitch = gather || inLayout == nexrLayoutBlocks ? B : nn * B;
+  const size_t outBlock = outLayout == nexrLayoutBlocks ? rows * B : B;  // the gather is written rows out
+  size_t outPitch = outLayout == nexrLayoutBlocks ? B : nn * B;
+  if (rows == 1 || (inPitch == B && outPitch == B)) {  // a pair's rows are one contiguous run on both sides
+    B *= rows;
+    rows = 1;
+    inPitch = outPitch = B;
+  }
+  nexrResult_t res = nexrSuccess;
+  for (int d = 0; d < n && res == nexrSuccess; d++) {
+    if (c->streams[d]) (void)hipSetDevice(c->devices[d]);
+    for (int s = 0; s < n && res == nexrSuccess; s++)
+      for (size_t row = 0; row < rows && res == nexrSuccess; row++) {
+        const void* src = (const char*)sendbuffs[s] + (size_t)d * inBlock + row * inPitch;
+        void* dst = (char*)recvbuffs[d] + (size_t)s * outBlock + row * outPitch;
+        res = c->cfg.fn(1, &src, 1, &dst, B, nexrUint8, nexrDevSum, 0, 0, nullptr, 0, (nexrStream_t)c->streams[d]);
+      }
+    // also behind an error: nothing stays in flight over the caller's buffers
+    if (device && c->streams[d] && hipStreamSynchronize(c->streams[d]) != hipSuccess && res == nexrSuccess)
+      res = nexrUnhandledCudaError;
+  }
+  return res;
+}
+
 // nexrRingAllToAllv. The checks that need no execution and no value of the matrix (they run when a call is
 // recorded): the datatype as nexrRingAllGather's, the arrays, the residence, and the capacity ranges as
 // nexrFlatAllToAllv compares them (half-open; an empty range meets nothing).
@@ -1816,7 +1902,8 @@ enum RingEntry {
   kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather,
   kEntAllToAll,
   kEntAllToAllV,  // recorded by nexrRingAllToAllv itself; groupExecute runs it, not runEntry
-  kEntReduceScatterV, kEntAllGatherV  // likewise, by nexrRingReduceScatterv / nexrRingAllGatherv (scatterVRecord)
+  kEntReduceScatterV, kEntAllGatherV,  // likewise, by nexrRingReduceScatterv / nexrRingAllGatherv (scatterVRecord)
+  kEntAllToAll2D, kEntAllGather2D      // likewise, by nexrRingAllToAll2D / nexrRingAllGather2D (pitchedOrRecord)
 };
 
 // The entry as it runs alone.
@@ -2108,6 +2195,32 @@ nexrResult_t groupOrRun(nexrRingComm* c, int entry, const void* const* sendbuffs
   return runEntry(c, entry, sendbuffs, recvbuffs, count, datatype, op, root, nBlocks);
 }
 
+// A nexrRingAllToAll2D / nexrRingAllGather2D call: inside a group it is checked and recorded, else it runs.
+nexrResult_t pitchedOrRecord(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs,
+                             size_t rows, size_t count, int datatype, int inLayout, int outLayout) {
+  if (c && c->groupDepth > 0 && !c->groupRunning) {
+    size_t esz = 0;
+    const nexrResult_t r =
+        pitchedCheck(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout, &esz);
+    if (r != nexrSuccess) return r;
+    const size_t n = (size_t)c->cfg.nRanks;
+    nexrRingComm::GroupCall g;
+    g.entry = gather ? kEntAllGather2D : kEntAllToAll2D;
+    g.send.assign(sendbuffs, sendbuffs + n);
+    g.recv.assign(recvbuffs, recvbuffs + n);
+    g.count = count;
+    g.datatype = datatype;
+    g.rows = rows;
+    g.inLayout = inLayout;
+    g.outLayout = outLayout;
+    c->groupCalls.push_back(std::move(g));
+    c->groupStats.calls++;
+    return nexrSuccess;
+  }
+  DeviceGuard dg(c && c->needHip);
+  return pitched(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout);
+}
+
 // Whether a recorded call becomes work records: it would run flat, as a ring all-reduce, reduce-scatter, reduce,
 // all-gather or broadcast, on a device-memory communicator of 2+ ranks on one GPU, with one redOpArg.
 bool groupTakes(nexrRingComm* c, const nexrRingComm::GroupCall& g, RedOps* ops, size_t* esz) {
@@ -2253,6 +2366,10 @@ nexrResult_t groupExecute(nexrRingComm* c) {
       res = scatterV(c, g.entry == kEntReduceScatterV, g.send.data(), g.recv.data(),
                      g.countsPtr ? g.countsPtr : g.counts.data(), g.residence, g.datatype, g.op, g.sendElts.data(),
                      g.recvElts.data(), g.status);
+    } else if (g.entry == kEntAllToAll2D || g.entry == kEntAllGather2D) {
+      DeviceGuard dg(c->needHip);
+      res = pitched(c, g.entry == kEntAllGather2D, g.send.data(), g.recv.data(), g.rows, g.count, g.datatype,
+                    g.inLayout, g.outLayout);
     } else {
       res = runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
     }
@@ -2442,6 +2559,16 @@ NEXR_API nexrResult_t nexrRingReduceFlat(nexrRingComm_t c, const void* const* se
 NEXR_API nexrResult_t nexrRingAllToAll(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                        size_t count, int datatype) {
   return groupOrRun(c, kEntAllToAll, sendbuffs, recvbuffs, count, datatype, nexrSum, 0, 0);
+}
+
+NEXR_API nexrResult_t nexrRingAllToAll2D(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                         size_t rows, size_t count, int datatype, int inLayout, int outLayout) {
+  return pitchedOrRecord(c, false, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout);
+}
+
+NEXR_API nexrResult_t nexrRingAllGather2D(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
+                                          size_t rows, size_t count, int datatype) {
+  return pitchedOrRecord(c, true, sendbuffs, recvbuffs, rows, count, datatype, nexrLayoutRows, nexrLayoutRows);
 }
 
 NEXR_API nexrResult_t nexrRingAllToAllv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,

@@ -25,7 +25,8 @@ RING_ABI_SYMBOLS = ("nexrRingCommCreate", "nexrRingAllReduce", "nexrRingReduceSc
                     "nexrRingAllGatherSymmetricLL",
                     "nexrRingAllReduceFlat", "nexrRingReduceScatterFlat", "nexrRingReduceFlat", "nexrRingCommSetFlat",
                     "nexrTreeAllReduceFlat", "nexrRingBroadcastFlat", "nexrRingAllGatherFlat", "nexrRingAllToAll",
-                    "nexrRingAllToAllv", "nexrRingReduceScatterv", "nexrRingAllGatherv",
+                    "nexrRingAllToAllv", "nexrRingReduceScatterv", "nexrRingAllGatherv", "nexrRingAllToAll2D",
+                    "nexrRingAllGather2D",
                     "nexrRingGroupStart", "nexrRingGroupEnd", "nexrRingGroupGetStats",
                     "nexrTreeTopology", "nexrRingRedOpCreatePreMulSum", "nexrRingRedOpDestroy",
                     "nexrRingCommGetStepWait", "nexrRingCommGetQueued", "nexrRingCommSetLLGroup",
@@ -125,6 +126,8 @@ def _bind_ring(L: ctypes.CDLL) -> None:
     L.nexrRingAllToAllv.argtypes = [vp, arr, arr, vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
     L.nexrRingReduceScatterv.argtypes = [vp, arr, arr, vp, i32, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
     L.nexrRingAllGatherv.argtypes = [vp, arr, arr, vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz), vp]
+    L.nexrRingAllToAll2D.argtypes = [vp, arr, arr, sz, sz, i32, i32, i32]
+    L.nexrRingAllGather2D.argtypes = [vp, arr, arr, sz, sz, i32]
     L.nexrRingGroupStart.argtypes = [vp]
     L.nexrRingGroupEnd.argtypes = [vp]
     L.nexrRingGroupGetStats.argtypes = [vp, ctypes.POINTER(RingGroupStats), i32]
@@ -389,6 +392,24 @@ class RingComm:
         copies through the communicator's reduce-copy elsewhere; InvalidUsage for process ranks."""
         s, r = self._arrays(sendbuffs, recvbuffs)
         _check(self._L.nexrRingAllToAll(self._h, s, r, int(count), int(datatype)), "nexrRingAllToAll")
+
+    def all_to_all_2d(self, sendbuffs, recvbuffs, rows: int, count: int, datatype: int, in_layout: int,
+                      out_layout: int) -> None:
+        """The pitched all-to-all (nexrRingAllToAll2D): block row r < rows of `count` elements that rank s holds for
+        rank d, at (d*rows + r)*count under LAYOUT_BLOCKS or (r*n + d)*count under LAYOUT_ROWS of its sendbuff,
+        arrives at the same formula of (s, r) under out_layout in rank d's recvbuff; a bit copy. Rows in and blocks
+        out is the Ulysses forward exchange. ONE launch on thread ranks in device memory on one GPU, block rows
+        through the communicator's reduce-copy elsewhere; InvalidUsage for process ranks."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllToAll2D(self._h, s, r, int(rows), int(count), int(datatype), int(in_layout),
+                                          int(out_layout)), "nexrRingAllToAll2D")
+
+    def all_gather_2d(self, sendbuffs, recvbuffs, rows: int, count: int, datatype: int) -> None:
+        """The all-gather along the last dimension (nexrRingAllGather2D): every sendbuff is [rows][count], every
+        recvbuff [rows][n][count] with rank s's row r at (r*n + s)*count; a bit copy. Routed as all_to_all_2d."""
+        s, r = self._arrays(sendbuffs, recvbuffs)
+        _check(self._L.nexrRingAllGather2D(self._h, s, r, int(rows), int(count), int(datatype)),
+               "nexrRingAllGather2D")
 
     def all_to_all_v(self, sendbuffs, recvbuffs, counts, datatype: int, send_elts, recv_elts, status: int = 0) -> None:
         """The all-to-all with a count per pair (nexrRingAllToAllv): counts[s*n + d] elements go from rank s to
