@@ -2853,6 +2853,16 @@ NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* con
 }
 
 // ---- nexrFlatAllToAll -------------------------------------------------------------------------------------------
+namespace {
+// The grid of the exchanges below: a wave per item, four waves per workgroup, at least `least` (0 or 1) and at most
+// `cap` workgroups, then maxWorkgroups where it is set. Beyond the grid the waves stride.
+unsigned waveGrid(uint64_t items, uint64_t cap, uint64_t least, int maxWorkgroups) {
+  uint64_t grid = std::min<uint64_t>(std::max<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), least), cap);
+  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
+  return (unsigned)grid;
+}
+}  // namespace
+
 // Every check before any device call; the ranges are half-open, as nexrFlatGroupPlan compares them. The host
 // picks the instance: packs where no pack can straddle two blocks (nBytes % 16 == 0), bytes otherwise.
 NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
@@ -2868,25 +2878,15 @@ NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, vo
     p.in[r] = (const char*)inputs[r];
     p.out[r] = (char*)outputs[r];
   }
-  auto hit = [row](const void* a, const void* b) {
-    return (uintptr_t)a < (uintptr_t)b + row && (uintptr_t)b < (uintptr_t)a + row;
-  };
-  for (int d = 0; d < nRanks && row; d++) {
-    for (int s = 0; s < nRanks; s++)
-      if (hit(outputs[d], inputs[s])) return nexrInvalidArgument;  // in place is not offered
-    for (int e = 0; e < d; e++)
-      if (hit(outputs[d], outputs[e])) return nexrInvalidArgument;
-  }
+  if (!nexr_exchange_v::fixedRangesOk(nRanks, inputs, outputs, row, row, true)) return nexrInvalidArgument;
   if (nBytes == 0) return nexrSuccess;
   const bool bytes = (nBytes & 15u) != 0;
   p.blockBytes = nBytes;
   p.nRanks = nRanks;
   p.piecesPer = ((bytes ? (uint64_t)nBytes : (uint64_t)row) + 2047) / 2048;
   p.nItems = p.piecesPer * (uint64_t)nRanks * (bytes ? (uint64_t)nRanks : 1);
-  // a wave per item, four waves per workgroup; beyond the cap the waves stride
-  uint64_t grid = std::min<uint64_t>((p.nItems + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
-  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
-  NEXR_HIP(launch_flat_alltoall(p, bytes, (unsigned)grid, (hipStream_t)stream));
+  const unsigned grid = waveGrid(p.nItems, gridCap(kBlock), 0, maxWorkgroups);
+  NEXR_HIP(launch_flat_alltoall(p, bytes, grid, (hipStream_t)stream));
   return nexrSuccess;
 }
 
@@ -2913,15 +2913,7 @@ nexrResult_t flatPitched(int nRanks, const void* const* inputs, void* const* out
     p.in[r] = (const char*)inputs[r];
     p.out[r] = (char*)outputs[r];
   }
-  auto hit = [](const void* a, uintptr_t aLen, const void* b, uintptr_t bLen) {
-    return (uintptr_t)a < (uintptr_t)b + bLen && (uintptr_t)b < (uintptr_t)a + aLen;
-  };
-  for (int d = 0; d < nRanks && outLen; d++) {
-    for (int s = 0; s < nRanks; s++)
-      if (hit(outputs[d], outLen, inputs[s], inLen)) return nexrInvalidArgument;  // in place is not offered
-    for (int e = 0; e < d; e++)
-      if (hit(outputs[d], outLen, outputs[e], outLen)) return nexrInvalidArgument;
-  }
+  if (!nexr_exchange_v::fixedRangesOk(nRanks, inputs, outputs, inLen, outLen, true)) return nexrInvalidArgument;
   if (outLen == 0) return nexrSuccess;
   if (!gather && (rows == 1 || (inLayout == nexrLayoutBlocks && outLayout == nexrLayoutBlocks)))
     return nexrFlatAllToAll(nRanks, inputs, outputs, rows * nBytes, maxWorkgroups, stream);
@@ -2939,10 +2931,8 @@ nexrResult_t flatPitched(int nRanks, const void* const* inputs, void* const* out
   const uint64_t piece = (uint64_t)128 * (uint64_t)width;
   p.piecesPer = p.outBytes / piece + (p.outBytes % piece ? 1 : 0);
   p.nItems = p.piecesPer * (uint64_t)n;
-  // a wave per item, four waves per workgroup; beyond the cap the waves stride
-  uint64_t grid = std::min<uint64_t>((p.nItems + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
-  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
-  NEXR_HIP(launch_flat_pitched(p, width, (unsigned)grid, (hipStream_t)stream));
+  const unsigned grid = waveGrid(p.nItems, gridCap(kBlock), 0, maxWorkgroups);
+  NEXR_HIP(launch_flat_pitched(p, width, grid, (hipStream_t)stream));
   return nexrSuccess;
 }
 }  // namespace
@@ -2981,6 +2971,43 @@ nexrResult_t flatExchangeVResident(int n, uint64_t* resident) {
   *resident = std::max<uint64_t>(perCu * (uint64_t)std::max(cus, 1), 1);
   return nexrSuccess;
 }
+
+// The grid of the counted launches: waveGrid up to the workgroups the device keeps resident (ldsRanks: what
+// flatExchangeVResident takes), so that a workgroup's prologue serves many pieces and not four. Device counts with
+// no capacity at all still launch one workgroup: the verdict is the kernel's.
+nexrResult_t flatCountedGrid(int ldsRanks, uint64_t items, int maxWorkgroups, unsigned* grid) {
+  uint64_t resident = 0;
+  const nexrResult_t res = flatExchangeVResident(ldsRanks, &resident);
+  if (res != nexrSuccess) return res;
+  *grid = waveGrid(items, resident, 1, maxWorkgroups);
+  return nexrSuccess;
+}
+
+// What the counted entries share once the rank count and the element size are checked: the arrays, the residence,
+// device counts' alignment and status word, the capacities and ranges (countWords counts), and the fields that
+// FlatExchangeVParams and FlatScatterVParams have in common.
+extern "C++" template <typename Params>
+nexrResult_t flatCountedPrelude(int n, const void* const* inputs, void* const* outputs, const uint64_t* counts,
+                                int residence, size_t esz, const size_t* inElts, const size_t* outElts,
+                                uint32_t* status, int maxWorkgroups, size_t countWords, Params* p) {
+  if (!inputs || !outputs || !counts || !inElts || !outElts || maxWorkgroups < 0) return nexrInvalidArgument;
+  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
+  const bool dev = residence == nexrScalarDevice;
+  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
+  if (!nexr_exchange_v::buffersOk(n, inputs, outputs, inElts, outElts, esz, counts, status, dev, countWords))
+    return nexrInvalidArgument;
+  for (int r = 0; r < n; r++) {
+    p->in[r] = (const char*)inputs[r];
+    p->out[r] = (char*)outputs[r];
+    p->inElts[r] = inElts[r];
+    p->outElts[r] = outElts[r];
+  }
+  p->status = status;
+  p->nRanks = n;
+  return nexrSuccess;
+}
+
+int eszShift(size_t esz) { return esz == 1 ? 0 : esz == 2 ? 1 : esz == 4 ? 2 : 3; }
 }  // namespace
 
 // Every check before any device call. Host counts are summed here and size the grid exactly; device counts are
@@ -2989,23 +3016,15 @@ NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, v
                                         const uint64_t* counts, int residence, size_t esz, const size_t* inElts,
                                         const size_t* outElts, uint32_t* status, int maxWorkgroups,
                                         nexrStream_t stream) {
-  if (!inputs || !outputs || !counts || !inElts || !outElts || maxWorkgroups < 0) return nexrInvalidArgument;
   if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
   if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return nexrInvalidArgument;
-  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
-  const bool dev = residence == nexrScalarDevice;
-  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
   const int n = nRanks;
-  if (!nexr_exchange_v::buffersOk(n, inputs, outputs, inElts, outElts, esz, counts, status, dev))
-    return nexrInvalidArgument;
+  const bool dev = residence == nexrScalarDevice;
   FlatExchangeVParams p;
   memset((void*)&p, 0, sizeof(p));
-  for (int r = 0; r < n; r++) {
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-    p.inElts[r] = inElts[r];
-    p.outElts[r] = outElts[r];
-  }
+  nexrResult_t res = flatCountedPrelude(n, inputs, outputs, counts, residence, esz, inElts, outElts, status,
+                                        maxWorkgroups, (size_t)n * n, &p);
+  if (res != nexrSuccess) return res;
   uint64_t items = 0;
   if (dev) {
     for (int d = 0; d < n; d++) items += ((uint64_t)outElts[d] * esz + 2047) / 2048;
@@ -3015,17 +3034,10 @@ NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, v
     for (int d = 0; d < n; d++) items += (col[d] * esz + 2047) / 2048;
     if (items == 0) return nexrSuccess;
   }
-  p.status = status;
-  p.nRanks = n;
-  p.shift = esz == 1 ? 0 : esz == 2 ? 1 : esz == 4 ? 2 : 3;
-  // a wave per item, four waves per workgroup, up to the workgroups the device keeps resident: beyond that the
-  // waves stride, so that a workgroup's prologue serves many pieces and not four. Device counts with no capacity
-  // at all still launch one workgroup: the verdict is the kernel's.
-  uint64_t resident = 0;
-  const nexrResult_t res = flatExchangeVResident(n, &resident);
+  p.shift = eszShift(esz);
+  unsigned grid = 0;
+  res = flatCountedGrid(n, items, maxWorkgroups, &grid);
   if (res != nexrSuccess) return res;
-  uint64_t grid = std::min<uint64_t>(std::max<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), 1), resident);
-  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
   hipStream_t s = (hipStream_t)stream;
   uint64_t* ws = nullptr;
   const int words = n * n;
@@ -3049,7 +3061,7 @@ NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, v
     }
     p.ext = ws;
   }
-  const hipError_t e = launch_flat_exchange_v(p, (unsigned)grid, s);
+  const hipError_t e = launch_flat_exchange_v(p, grid, s);
   if (ws) (void)hipFreeAsync(ws, s);
   NEXR_HIP(e);
   return nexrSuccess;
@@ -3065,15 +3077,12 @@ nexrResult_t flatScatterVCheck(int n, const void* const* inputs, void* const* ou
                                uint32_t* status, int maxWorkgroups, bool scatter, FlatScatterVParams* pp,
                                uint64_t* items) {
   FlatScatterVParams& p = *pp;
-  if (!inputs || !outputs || !counts || !inElts || !outElts || maxWorkgroups < 0) return nexrInvalidArgument;
-  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
-  const bool dev = residence == nexrScalarDevice;
-  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
-  if (!nexr_exchange_v::buffersOk(n, inputs, outputs, inElts, outElts, esz, counts, status, dev, (size_t)n))
-    return nexrInvalidArgument;
+  const nexrResult_t res = flatCountedPrelude(n, inputs, outputs, counts, residence, esz, inElts, outElts, status,
+                                              maxWorkgroups, (size_t)n, pp);
+  if (res != nexrSuccess) return res;
   const size_t* own = scatter ? outElts : inElts;  // the capacities of the buffers that hold one piece
   *items = 0;
-  if (dev) {
+  if (residence == nexrScalarDevice) {
     for (int d = 0; d < n; d++) *items += ((uint64_t)own[d] * esz + 2047) / 2048;
     p.ext = counts;
   } else {
@@ -3082,28 +3091,7 @@ nexrResult_t flatScatterVCheck(int n, const void* const* inputs, void* const* ou
     for (int d = 0; d < n; d++) *items += (counts[d] * esz + 2047) / 2048;
     memcpy(p.counts, counts, (size_t)n * 8);
   }
-  for (int r = 0; r < n; r++) {
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-    p.inElts[r] = inElts[r];
-    p.outElts[r] = outElts[r];
-  }
-  p.status = status;
-  p.nRanks = n;
-  p.eszShift = esz == 1 ? 0 : esz == 2 ? 1 : esz == 4 ? 2 : 3;
-  return nexrSuccess;
-}
-
-// A wave per item, four waves per workgroup, up to the workgroups the device keeps resident; beyond that, and
-// under maxWorkgroups, the waves stride. Device counts with no capacity at all still launch one workgroup: the
-// verdict is the kernel's.
-nexrResult_t flatScatterVGrid(uint64_t items, int maxWorkgroups, unsigned* grid) {
-  uint64_t resident = 0;
-  const nexrResult_t res = flatExchangeVResident(0, &resident);
-  if (res != nexrSuccess) return res;
-  uint64_t g = std::min<uint64_t>(std::max<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), 1), resident);
-  if (maxWorkgroups > 0 && g > (uint64_t)maxWorkgroups) g = (uint64_t)maxWorkgroups;
-  *grid = (unsigned)g;
+  p.eszShift = eszShift(esz);
   return nexrSuccess;
 }
 }  // namespace
@@ -3133,7 +3121,7 @@ NEXR_API nexrResult_t nexrFlatReduceScatterv(int nRanks, const void* const* inpu
   p.preOp = m.preOp;
   p.postOp = m.postOp;
   unsigned grid = 0;
-  res = flatScatterVGrid(items, maxWorkgroups, &grid);
+  res = flatCountedGrid(0, items, maxWorkgroups, &grid);
   if (res != nexrSuccess) return res;
   NEXR_HIP(launch_flat_scatter_v(m.dt, m.op, p, grid, (hipStream_t)stream));
   return nexrSuccess;
@@ -3153,7 +3141,7 @@ NEXR_API nexrResult_t nexrFlatAllGatherv(int nRanks, const void* const* inputs, 
   if (res != nexrSuccess) return res;
   if (residence == nexrScalarHostImmediate && items == 0) return nexrSuccess;
   unsigned grid = 0;
-  res = flatScatterVGrid(items, maxWorkgroups, &grid);
+  res = flatCountedGrid(0, items, maxWorkgroups, &grid);
   if (res != nexrSuccess) return res;
   NEXR_HIP(launch_flat_gather_v(p, grid, (hipStream_t)stream));
   return nexrSuccess;

@@ -1,7 +1,9 @@
 // nexr_exchange_v_checks.h — the checks of the all-to-all with a count per pair that need no device, shared by
 // nexrFlatAllToAllv (nexr_api.cpp) and nexrRingAllToAllv (nexr_ring.cpp, at any rank count): the half-open range
 // rule and the bound on a capacity stand here and nowhere else. The reduce-scatter and the all-gather with a count
-// per rank (nexrFlatReduceScatterv, nexrFlatAllGatherv and their ring entries) share them, with n counts.
+// per rank (nexrFlatReduceScatterv, nexrFlatAllGatherv and their ring entries) share them, with n counts. The
+// exchanges of a fixed size (nexrFlatAllToAll, nexrFlatAllToAll2D, nexrFlatAllGather2D and their ring entries) take
+// the range rule from fixedRangesOk.
 #pragma once
 
 #include <stddef.h>
@@ -39,6 +41,24 @@ inline bool buffersOk(int n, const void* const* in, void* const* out, const size
     for (int e = 0; e < d; e++)
       if (o.meets(range(out[e], outElts[e]))) return false;
     if (deviceCounts && (o.meets(cnt) || o.meets(word))) return false;
+  }
+  return true;
+}
+
+// The range rule for a fixed length per side: every in[s] is inLen bytes and every out[d] outLen bytes. No output
+// range may meet an input range (in place is not offered) nor, with amongOutputs, another output range. A length of
+// 0 meets nothing. These callers put no bound on a length, so an end is compared as the address arithmetic gives
+// it, without Range's order of beg and end.
+inline bool fixedRangesOk(int n, const void* const* in, void* const* out, uintptr_t inLen, uintptr_t outLen,
+                          bool amongOutputs) {
+  auto meets = [](const void* a, uintptr_t aLen, const void* b, uintptr_t bLen) {
+    return (uintptr_t)a < (uintptr_t)b + bLen && (uintptr_t)b < (uintptr_t)a + aLen;
+  };
+  for (int d = 0; d < n; d++) {
+    for (int s = 0; s < n; s++)
+      if (meets(out[d], outLen, in[s], inLen)) return false;
+    for (int e = 0; e < d && amongOutputs; e++)
+      if (meets(out[d], outLen, out[e], outLen)) return false;
   }
   return true;
 }

@@ -718,6 +718,14 @@ int llTicketEvery() {
   return every;
 }
 
+// Whether the steps of the communicator's protocol run the library's own device kernels: a caller's fn / llFn /
+// ll128Fn computes what it likes, so no launch of the library's may stand in for it.
+bool ownStepFn(const nexrRingComm* c) {
+  return c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
+         : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
+                                          : c->cfg.fn == defaultDeviceFn;
+}
+
 // Group launches (nexrRingCommSetLLGroup): every Primitives of the collective, a ring's (channel, rank) or
 // a tree's root and reduce-up / broadcast-down halves (2n - 1 per channel), is a member of one
 // nexrReduceCopyLLStepsGroup call on one stream (LL128: nexrReduceCopyLL128StepsGroup, whose ordered
@@ -726,9 +734,7 @@ int llTicketEvery() {
 // library's own kernels (not a caller's llFn / ll128Fn) and device head words on every connection; and at
 // most NEXR_LL_GROUP_MAX_MEMBERS members.
 bool llGroupAllowed(const nexrRingComm* c, size_t nMembers) {
-  const bool ownFn = c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
-                     : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
-                                                      : false;
+  const bool ownFn = c->proto != nexrRingProtoSimple && ownStepFn(c);
   if (!c->llGroup || !ownFn || c->cfg.memMode != nexrRingDeviceMemory || !c->stepWaitWord ||
       nMembers > NEXR_LL_GROUP_MAX_MEMBERS || c->streams.empty() || !c->streams[0] || !c->status[0] || !c->done[0])
     return false;
@@ -1252,6 +1258,29 @@ bool flatReadsResident(const nexrRingComm* c) {
   return !c || c->cfg.memMode != nexrRingDeviceMemory || c->cfg.nRanks == 1;
 }
 
+// "Thread ranks in device memory on one GPU", the communicators that one launch over every rank's buffers serves,
+// in the two parts that symCollective and groupRecord answer apart: a device for every rank with a first stream to
+// launch on, and every rank's device the first rank's (asked only after hasFirstStream).
+bool hasFirstStream(const nexrRingComm* c) {
+  return (int)c->devices.size() >= c->cfg.nRanks && !c->streams.empty() && c->streams[0];
+}
+bool ranksShareGpu(const nexrRingComm* c) {
+  for (int i = 0; i < c->cfg.nRanks; i++)
+    if (c->devices[i] != c->devices[0]) return false;
+  return true;
+}
+bool deviceRanksOnOneGpu(const nexrRingComm* c) {
+  return c->cfg.memMode == nexrRingDeviceMemory && c->cfg.nRanks <= NEXR_SYM_MAX_RANKS && hasFirstStream(c) &&
+         ranksShareGpu(c);
+}
+
+// One rank's collective that moves data without an op of its own: the copy of `count` elements (ncclSum).
+nexrResult_t oneRankCopy(nexrRingComm* c, const void* sendbuff, void* recvbuff, size_t count, int datatype) {
+  nexrDevRedOpFull red;
+  const nexrResult_t r = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
+  return r != nexrSuccess ? r : oneRank(c, 0, sendbuff, recvbuff, count, datatype, red, nexrTypeSize(datatype));
+}
+
 nexrResult_t symWait(nexrRingComm* c, hipStream_t stream);
 
 template <typename Launch>
@@ -1262,18 +1291,14 @@ nexrResult_t symCollective(nexrRingComm* c, const void* const* sendbuffs, void* 
   for (int i = 0; i < n; i++)
     if (count != 0 && (!sendbuffs[i] || !recvbuffs[i])) return nexrInvalidArgument;
   const bool host = flatHost && flatHostEligible(c);
-  if (c->peer || c->broken || (c->cfg.memMode != nexrRingDeviceMemory && !host) || (int)c->devices.size() < n ||
-      c->streams.empty() || !c->streams[0])
+  if (c->peer || c->broken || (c->cfg.memMode != nexrRingDeviceMemory && !host) || !hasFirstStream(c))
     return nexrInvalidUsage;
-  for (int i = 0; i < n && !host; i++)
-    if (c->devices[i] != c->devices[0]) return nexrInvalidUsage;
+  if (!host && !ranksShareGpu(c)) return nexrInvalidUsage;
   if (n > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
   if (count == 0) return nexrSuccess;
   if (n == 1) {
-    nexrDevRedOpFull red;
     if (oneRankOp) return oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, *oneRankOp, nexrTypeSize(datatype));
-    const nexrResult_t r = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
-    return r != nexrSuccess ? r : oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, nexrTypeSize(datatype));
+    return oneRankCopy(c, sendbuffs[0], recvbuffs[0], count, datatype);
   }
   if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
   hipStream_t stream = c->streams[0];
@@ -1482,62 +1507,31 @@ nexrResult_t flatAllGather(nexrRingComm* c, const void* const* sendbuffs, void* 
       nullptr, true);
 }
 
-// nexrRingAllToAll. The checks that need no execution (groupRecord repeats them for a recorded call): the
-// arguments as nexrRingAllGather's, and no send range [sendbuffs[s], + n * count * esz) may meet a receive range
-// (half-open byte ranges).
-nexrResult_t allToAllCheck(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                           int datatype, size_t* esz) {
-  if (!c) return nexrInvalidArgument;
-  if (c->peer) return nexrInvalidUsage;
-  nexrDevRedOpFull red;
-  const nexrResult_t r = prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
-  if (r != nexrSuccess) return r;
-  const int n = c->cfg.nRanks;
-  if (!sendbuffs || !recvbuffs) return nexrInvalidArgument;
-  if (count > (size_t)-1 / *esz / (size_t)n) return nexrInvalidArgument;
-  if (count == 0) return nexrSuccess;
-  const uintptr_t row = (uintptr_t)n * count * *esz;
-  for (int i = 0; i < n; i++)
-    if (!sendbuffs[i] || !recvbuffs[i]) return nexrInvalidArgument;
-  for (int d = 0; d < n && n > 1; d++)
-    for (int s = 0; s < n; s++)
-      if ((uintptr_t)recvbuffs[d] < (uintptr_t)sendbuffs[s] + row && (uintptr_t)sendbuffs[s] < (uintptr_t)recvbuffs[d] + row)
-        return nexrInvalidArgument;
-  return nexrSuccess;
-}
+// Every collective entry of include/nexr_ring.h by number: what a recorded call remembers, and what runCall runs.
+enum RingEntry {
+  kEntAllReduce, kEntReduceScatter, kEntAllGather, kEntReduce, kEntBroadcast, kEntTree,
+  kEntSymAllReduce, kEntSymReduceScatter, kEntSymAllGather,
+  kEntFlatAllReduce, kEntFlatReduceScatter, kEntFlatReduce, kEntFlatTree, kEntFlatBroadcast, kEntFlatAllGather,
+  kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather,
+  kEntAllToAll,
+  kEntAllToAllV, kEntReduceScatterV, kEntAllGatherV,  // the counted entries: countedOrRecord
+  kEntAllToAll2D, kEntAllGather2D                     // pitchedOrRecord
+};
 
-// Thread ranks in device memory on one GPU: ONE nexrFlatAllToAll launch on the first stream through symCollective
-// and its wait, as flatBroadcast. Any other thread-rank communicator: n * n block copies in (d, s) order, each ONE
-// reduce-copy with one source and one destination on the receiving rank (uint8, Sum, count * esz elements: a
-// caller's fn sees every block), and the call returns with the outputs complete.
-nexrResult_t allToAll(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
-                      int datatype) {
-  size_t esz = 0;
-  const nexrResult_t r = allToAllCheck(c, sendbuffs, recvbuffs, count, datatype, &esz);
-  if (r != nexrSuccess || count == 0) return r;
-  const int n = c->cfg.nRanks;
+// The copies of a collective on a communicator that has no one launch for it, by receiving rank d on that rank's
+// device and stream: each ONE reduce-copy with one source and one destination (uint8, Sum: a caller's fn sees
+// every copy). each(d, copy) names rank d's copies in order, as copy(src, dst, bytes); copy answers false from the
+// first error on, and nothing more is issued. The call returns with the outputs complete.
+template <typename Each>
+nexrResult_t blockCopies(nexrRingComm* c, Each each) {
   const bool device = c->cfg.memMode == nexrRingDeviceMemory;
-  bool oneGpu = device && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() && c->streams[0];
-  for (int i = 0; oneGpu && i < n; i++)
-    if (c->devices[i] != c->devices[0]) oneGpu = false;
-  if (n == 1) {
-    nexrDevRedOpFull red;
-    const nexrResult_t e = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
-    return e != nexrSuccess ? e : oneRank(c, 0, sendbuffs[0], recvbuffs[0], count, datatype, red, esz);
-  }
-  if (oneGpu)
-    return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
-      return nexrFlatAllToAll(nr, sendbuffs, recvbuffs, count * esz, 0, stream);
-    });
-  const size_t bytes = count * esz;
   nexrResult_t res = nexrSuccess;
-  for (int d = 0; d < n && res == nexrSuccess; d++) {
+  for (int d = 0; d < c->cfg.nRanks && res == nexrSuccess; d++) {
     if (c->streams[d]) (void)hipSetDevice(c->devices[d]);
-    for (int s = 0; s < n && res == nexrSuccess; s++) {
-      const void* src = (const char*)sendbuffs[s] + (size_t)d * bytes;
-      void* dst = (char*)recvbuffs[d] + (size_t)s * bytes;
+    each(d, [&](const void* src, void* dst, size_t bytes) {
       res = c->cfg.fn(1, &src, 1, &dst, bytes, nexrUint8, nexrDevSum, 0, 0, nullptr, 0, (nexrStream_t)c->streams[d]);
-    }
+      return res == nexrSuccess;
+    });
     // also behind an error: nothing stays in flight over the caller's buffers
     if (device && c->streams[d] && hipStreamSynchronize(c->streams[d]) != hipSuccess && res == nexrSuccess)
       res = nexrUnhandledCudaError;
@@ -1545,11 +1539,14 @@ nexrResult_t allToAll(nexrRingComm* c, const void* const* sendbuffs, void* const
   return res;
 }
 
-// nexrRingAllToAll2D and nexrRingAllGather2D (gather). The checks that need no execution (a recorded call runs
-// them when it is made): the arguments as allToAllCheck's, the layouts, rows below 2^31, and the byte ranges as
-// nexrFlatAllToAll2D compares them (half-open; a send range is rows * count elements for the gather).
+// nexrRingAllToAll2D, nexrRingAllGather2D (gather) and nexrRingAllToAll, which is the first with one row and blocks
+// on both sides. The checks that need no execution (a recorded call runs them when it is made): the arguments as
+// nexrRingAllGather's, the layouts, rows below 2^31, and the byte ranges as nexrFlatAllToAll2D compares them
+// (half-open; a send range is rows * count elements for the gather). amongRecv: whether the receive ranges are
+// compared with each other too.
 nexrResult_t pitchedCheck(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs,
-                          size_t rows, size_t count, int datatype, int inLayout, int outLayout, size_t* esz) {
+                          size_t rows, size_t count, int datatype, int inLayout, int outLayout, bool amongRecv,
+                          size_t* esz) {
   if (!c) return nexrInvalidArgument;
   if (c->peer) return nexrInvalidUsage;
   nexrDevRedOpFull red;
@@ -1566,46 +1563,18 @@ nexrResult_t pitchedCheck(nexrRingComm* c, bool gather, const void* const* sendb
   const uintptr_t out = (uintptr_t)n * rows * count * *esz, in = gather ? (uintptr_t)(rows * count * *esz) : out;
   for (int i = 0; i < n; i++)
     if (!sendbuffs[i] || !recvbuffs[i]) return nexrInvalidArgument;
-  for (int d = 0; d < n && n > 1; d++) {
-    for (int s = 0; s < n; s++)
-      if ((uintptr_t)recvbuffs[d] < (uintptr_t)sendbuffs[s] + in && (uintptr_t)sendbuffs[s] < (uintptr_t)recvbuffs[d] + out)
-        return nexrInvalidArgument;
-    for (int e = 0; e < d; e++)
-      if ((uintptr_t)recvbuffs[d] < (uintptr_t)recvbuffs[e] + out && (uintptr_t)recvbuffs[e] < (uintptr_t)recvbuffs[d] + out)
-        return nexrInvalidArgument;
-  }
-  return nexrSuccess;
+  const bool ranges = n == 1 || nexr_exchange_v::fixedRangesOk(n, sendbuffs, recvbuffs, in, out, amongRecv);
+  return ranges ? nexrSuccess : nexrInvalidArgument;
 }
 
-// Routed as allToAll. Thread ranks in device memory on one GPU: ONE nexrFlatAllToAll2D / nexrFlatAllGather2D launch
-// on the first stream through symCollective and its wait. Any other thread-rank communicator: the block rows in
-// (d, s, r) order, each ONE reduce-copy with one source and one destination on the receiving rank (uint8, Sum); where
-// the rows of a pair are contiguous on both sides (blocks in and blocks out, or one row) they go as one copy. The
-// call returns with the outputs complete.
-nexrResult_t pitched(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs, size_t rows,
-                     size_t count, int datatype, int inLayout, int outLayout) {
-  size_t esz = 0;
-  const nexrResult_t r = pitchedCheck(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout, &esz);
-  if (r != nexrSuccess || rows == 0 || count == 0) return r;
-  const int n = c->cfg.nRanks;
-  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
-  bool oneGpu = device && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() && c->streams[0];
-  for (int i = 0; oneGpu && i < n; i++)
-    if (c->devices[i] != c->devices[0]) oneGpu = false;
-  if (n == 1) {  // both layouts of one rank are the rows in order
-    nexrDevRedOpFull red;
-    const nexrResult_t e = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
-    return e != nexrSuccess ? e : oneRank(c, 0, sendbuffs[0], recvbuffs[0], rows * count, datatype, red, esz);
-  }
-  size_t B = count * esz;
-  if (oneGpu)
-    return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
-      return gather ? nexrFlatAllGather2D(nr, sendbuffs, recvbuffs, rows, B, 0, stream)
-                    : nexrFlatAllToAll2D(nr, sendbuffs, recvbuffs, rows, B, inLayout, outLayout, 0, stream);
-    });
+// The call on a communicator that has no one launch for it: the block rows in (d, s, r) order through blockCopies;
+// where the rows of a pair are contiguous on both sides (blocks in and blocks out, or one row) they go as one copy.
+// B: the bytes of a block row.
+nexrResult_t pitchedCopies(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs,
+                           size_t rows, size_t B, int inLayout, int outLayout) {
   // the strides of nexr_flat_pitched.hip: run (s, r) of rank d is read at d * inBlock + r * inPitch and written at
   // s * outBlock + r * outPitch
-  const size_t nn = (size_t)n;
+  const size_t nn = (size_t)c->cfg.nRanks;
   const size_t inBlock = gather ? 0 : inLayout == nexrLayoutBlocks ? rows * B : B;
   size_t inPitch = gather || inLayout == nexrLayoutBlocks ? B : nn * B;
   const size_t outBlock = outLayout == nexrLayoutBlocks ? rows * B : B;  // the gather is written rows out
@@ -1615,38 +1584,83 @@ nexrResult_t pitched(nexrRingComm* c, bool gather, const void* const* sendbuffs,
     rows = 1;
     inPitch = outPitch = B;
   }
-  nexrResult_t res = nexrSuccess;
-  for (int d = 0; d < n && res == nexrSuccess; d++) {
-    if (c->streams[d]) (void)hipSetDevice(c->devices[d]);
-    for (int s = 0; s < n && res == nexrSuccess; s++)
-      for (size_t row = 0; row < rows && res == nexrSuccess; row++) {
-        const void* src = (const char*)sendbuffs[s] + (size_t)d * inBlock + row * inPitch;
-        void* dst = (char*)recvbuffs[d] + (size_t)s * outBlock + row * outPitch;
-        res = c->cfg.fn(1, &src, 1, &dst, B, nexrUint8, nexrDevSum, 0, 0, nullptr, 0, (nexrStream_t)c->streams[d]);
-      }
-    // also behind an error: nothing stays in flight over the caller's buffers
-    if (device && c->streams[d] && hipStreamSynchronize(c->streams[d]) != hipSuccess && res == nexrSuccess)
-      res = nexrUnhandledCudaError;
-  }
-  return res;
+  return blockCopies(c, [&](int d, auto copy) {
+    for (size_t s = 0; s < nn; s++)
+      for (size_t row = 0; row < rows; row++)
+        if (!copy((const char*)sendbuffs[s] + (size_t)d * inBlock + row * inPitch,
+                  (char*)recvbuffs[d] + s * outBlock + row * outPitch, B))
+          return;
+  });
 }
 
-// nexrRingAllToAllv. The checks that need no execution and no value of the matrix (they run when a call is
-// recorded): the datatype as nexrRingAllGather's, the arrays, the residence, and the capacity ranges as
-// nexrFlatAllToAllv compares them (half-open; an empty range meets nothing).
-nexrResult_t allToAllVCheck(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs,
-                            const uint64_t* counts, int residence, int datatype, const size_t* sendElts,
-                            const size_t* recvElts, const uint32_t* status, size_t* esz) {
+// Thread ranks in device memory on one GPU: ONE nexrFlatAllToAll2D / nexrFlatAllGather2D launch on the first stream
+// through symCollective and its wait. Any other thread-rank communicator: pitchedCopies.
+nexrResult_t pitched(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs, size_t rows,
+                     size_t count, int datatype, int inLayout, int outLayout) {
+  size_t esz = 0;
+  const nexrResult_t r =
+      pitchedCheck(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout, true, &esz);
+  if (r != nexrSuccess || rows == 0 || count == 0) return r;
+  // both layouts of one rank are the rows in order
+  if (c->cfg.nRanks == 1) return oneRankCopy(c, sendbuffs[0], recvbuffs[0], rows * count, datatype);
+  const size_t B = count * esz;
+  if (deviceRanksOnOneGpu(c))
+    return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
+      return gather ? nexrFlatAllGather2D(nr, sendbuffs, recvbuffs, rows, B, 0, stream)
+                    : nexrFlatAllToAll2D(nr, sendbuffs, recvbuffs, rows, B, inLayout, outLayout, 0, stream);
+    });
+  return pitchedCopies(c, gather, sendbuffs, recvbuffs, rows, B, inLayout, outLayout);
+}
+
+// nexrRingAllToAll's checks (groupRecord runs them for a recorded call): the all-to-all of one row, whose receive
+// ranges are not compared with each other.
+nexrResult_t allToAllCheck(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                           int datatype, size_t* esz) {
+  return pitchedCheck(c, false, sendbuffs, recvbuffs, 1, count, datatype, nexrLayoutBlocks, nexrLayoutBlocks, false,
+                      esz);
+}
+
+// As pitched, with ONE nexrFlatAllToAll launch; a block is count * esz bytes.
+nexrResult_t allToAll(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
+                      int datatype) {
+  size_t esz = 0;
+  const nexrResult_t r = allToAllCheck(c, sendbuffs, recvbuffs, count, datatype, &esz);
+  if (r != nexrSuccess || count == 0) return r;
+  if (c->cfg.nRanks == 1) return oneRankCopy(c, sendbuffs[0], recvbuffs[0], count, datatype);
+  if (deviceRanksOnOneGpu(c))
+    return symCollective(c, sendbuffs, recvbuffs, count, datatype, [&](int nr, nexrStream_t stream) {
+      return nexrFlatAllToAll(nr, sendbuffs, recvbuffs, count * esz, 0, stream);
+    });
+  return pitchedCopies(c, false, sendbuffs, recvbuffs, 1, count * esz, nexrLayoutBlocks, nexrLayoutBlocks);
+}
+
+// The counted entries: nexrRingAllToAllv (kEntAllToAllV, n * n counts), nexrRingReduceScatterv and
+// nexrRingAllGatherv (n counts).
+size_t countWords(const nexrRingComm* c, int entry) {
+  const size_t n = (size_t)c->cfg.nRanks;
+  return entry == kEntAllToAllV ? n * n : n;
+}
+
+// Their checks that need no execution and no value of the counts (they run when a call is recorded): the op as
+// nexrRingReduce's (the reduce-scatter; readResident: whether a user op's device-resident scalars are read, which
+// a recording does not do; *ops is its alone) or the datatype as nexrRingAllGather's, the arrays, the residence, and
+// the capacity ranges as the nexrFlat* entry compares them (half-open; an empty range meets nothing).
+nexrResult_t countedCheck(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs,
+                          const uint64_t* counts, int residence, int datatype, int op, const size_t* sendElts,
+                          const size_t* recvElts, const uint32_t* status, bool readResident, size_t* esz,
+                          RedOps* ops) {
   if (!c) return nexrInvalidArgument;
   if (c->peer) return nexrInvalidUsage;
   nexrDevRedOpFull red;
-  const nexrResult_t r = prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
+  const nexrResult_t r = entry == kEntReduceScatterV ? prepareOps(c, datatype, op, esz, ops, readResident)
+                                                     : prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum
   if (r != nexrSuccess) return r;
   if (!sendbuffs || !recvbuffs || !counts || !sendElts || !recvElts) return nexrInvalidArgument;
   if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
   const bool dev = residence == nexrScalarDevice;
   if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
-  const bool ok = nexr_exchange_v::buffersOk(c->cfg.nRanks, sendbuffs, recvbuffs, sendElts, recvElts, *esz, counts, status, dev);
+  const bool ok = nexr_exchange_v::buffersOk(c->cfg.nRanks, sendbuffs, recvbuffs, sendElts, recvElts, *esz, counts,
+                                             status, dev, countWords(c, entry));
   return ok ? nexrSuccess : nexrInvalidArgument;
 }
 
@@ -1661,88 +1675,93 @@ nexrResult_t allToAllVStatus(nexrRingComm* c, uint32_t* status, uint32_t v) {
   return hipMemcpy(status, &v, sizeof(v), hipMemcpyDefault) == hipSuccess ? nexrSuccess : nexrUnhandledCudaError;
 }
 
-// Whether host counts keep inside the capacities (nexr_exchange_v::countsFit, at any rank count).
-bool allToAllVFits(int n, const uint64_t* counts, const size_t* sendElts, const size_t* recvElts) {
-  std::vector<uint64_t> col((size_t)n);
-  return nexr_exchange_v::countsFit(n, counts, sendElts, recvElts, col.data());
+// Whether host counts keep inside the capacities (nexr_exchange_v, at any rank count), with the report: a violation
+// is nexrInvalidArgument and 1 in *status; a fit is written as 0 where reportFit says so (a recording leaves that to
+// the run). *total: the elements of the n pieces, for the entries with a count per rank.
+nexrResult_t countsFitReport(nexrRingComm* c, int entry, const uint64_t* counts, const size_t* sendElts,
+                             const size_t* recvElts, uint32_t* status, bool reportFit, uint64_t* total) {
+  const int n = c->cfg.nRanks;
+  bool fits;
+  if (entry == kEntAllToAllV) {
+    std::vector<uint64_t> col((size_t)n);
+    fits = nexr_exchange_v::countsFit(n, counts, sendElts, recvElts, col.data());
+  } else {
+    fits = nexr_exchange_v::piecesFit(n, counts, sendElts, recvElts, entry == kEntReduceScatterV, total);
+  }
+  if (fits && !reportFit) return nexrSuccess;
+  const nexrResult_t r = allToAllVStatus(c, status, fits ? 0u : 1u);
+  return fits ? r : nexrInvalidArgument;
 }
 
-// Thread ranks in device memory on one GPU: ONE nexrFlatAllToAllv launch on the first stream and symCollective's
-// wait (not symCollective itself: it refuses a null buffer, which a capacity of 0 allows here), refused as there on
-// a broken communicator; device counts are read by that kernel alone, and so is *status written. Any other thread-rank
-// communicator: device counts are read to the host behind the streams' work (the host's own memory where the
-// communicator never touches HIP), checked as host counts, and the non-empty blocks go in (d, s) order, each ONE
-// reduce-copy through the communicator's fn, as allToAll.
+// Device counts read to the host, once per call, behind what the ranks' streams hold (the host's own memory where
+// the communicator never touches HIP).
+nexrResult_t readCounts(nexrRingComm* c, const uint64_t* counts, size_t words, std::vector<uint64_t>* read) {
+  read->resize(words);
+  if (!c->needHip) {
+    memcpy(read->data(), counts, words * 8);
+    return nexrSuccess;
+  }
+  for (int i = 0; i < c->cfg.nRanks; i++)
+    if (c->streams[i] && (hipSetDevice(c->devices[i]) != hipSuccess || hipStreamSynchronize(c->streams[i]) != hipSuccess))
+      return nexrUnhandledCudaError;
+  if (hipMemcpy(read->data(), counts, words * 8, hipMemcpyDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    return nexrUnhandledCudaError;
+  }
+  return nexrSuccess;
+}
+
+// The one launch of a counted call and its wait: call(stream) is one nexrFlat* call on the first rank's device and
+// stream. symCollective's wait, not symCollective itself: it refuses a null buffer, which a capacity of 0 allows here.
+template <typename Call>
+nexrResult_t launchAndWait(nexrRingComm* c, Call call) {
+  if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
+  const nexrResult_t r = call((nexrStream_t)c->streams[0]);
+  return r != nexrSuccess ? r : symWait(c, c->streams[0]);
+}
+
+// nexrRingAllToAllv. Thread ranks in device memory on one GPU: ONE nexrFlatAllToAllv launch (launchAndWait), refused
+// as symCollective refuses on a broken communicator; device counts are read by that kernel alone, and so is *status
+// written. Any other thread-rank communicator: device counts are read to the host, checked as host counts, and the
+// non-empty blocks go in (d, s) order through blockCopies.
 nexrResult_t allToAllV(nexrRingComm* c, const void* const* sendbuffs, void* const* recvbuffs, const uint64_t* counts,
                        int residence, int datatype, const size_t* sendElts, const size_t* recvElts,
                        uint32_t* status) {
   size_t esz = 0;
-  nexrResult_t res = allToAllVCheck(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status, &esz);
+  nexrResult_t res = countedCheck(c, kEntAllToAllV, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum,
+                                  sendElts, recvElts, status, true, &esz, nullptr);
   if (res != nexrSuccess) return res;
   const int n = c->cfg.nRanks;
-  const bool dev = residence == nexrScalarDevice;
-  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
-  bool oneGpu = device && n >= 2 && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() &&
-                c->streams[0];
-  for (int i = 0; oneGpu && i < n; i++)
-    if (c->devices[i] != c->devices[0]) oneGpu = false;
+  const bool oneGpu = n >= 2 && deviceRanksOnOneGpu(c);
   if (oneGpu && c->broken) return nexrInvalidUsage;
-  if (oneGpu && dev) {
-    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
-    res = nexrFlatAllToAllv(n, sendbuffs, recvbuffs, counts, residence, esz, sendElts, recvElts, status, 0,
-                            (nexrStream_t)c->streams[0]);
-    return res != nexrSuccess ? res : symWait(c, c->streams[0]);
-  }
+  auto launch = [&](const uint64_t* cnt, int where, uint32_t* word) {
+    return launchAndWait(c, [&](nexrStream_t s) {
+      return nexrFlatAllToAllv(n, sendbuffs, recvbuffs, cnt, where, esz, sendElts, recvElts, word, 0, s);
+    });
+  };
+  if (oneGpu && residence == nexrScalarDevice) return launch(counts, residence, status);
   std::vector<uint64_t> read;
-  if (dev) {  // once per call, behind what the ranks' streams hold
-    read.resize((size_t)n * n);
-    if (!c->needHip) {
-      memcpy(read.data(), counts, read.size() * 8);
-    } else {
-      for (int i = 0; i < n; i++)
-        if (c->streams[i] && (hipSetDevice(c->devices[i]) != hipSuccess || hipStreamSynchronize(c->streams[i]) != hipSuccess))
-          return nexrUnhandledCudaError;
-      if (hipMemcpy(read.data(), counts, read.size() * 8, hipMemcpyDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nexrUnhandledCudaError;
-      }
-    }
+  if (residence == nexrScalarDevice) {
+    if ((res = readCounts(c, counts, countWords(c, kEntAllToAllV), &read)) != nexrSuccess) return res;
     counts = read.data();
   }
-  const bool fits = allToAllVFits(n, counts, sendElts, recvElts);
-  res = allToAllVStatus(c, status, fits ? 0u : 1u);
-  if (!fits) return nexrInvalidArgument;
+  res = countsFitReport(c, kEntAllToAllV, counts, sendElts, recvElts, status, true, nullptr);
   if (res != nexrSuccess) return res;
-  if (n == 1) {
-    if (counts[0] == 0) return nexrSuccess;
-    nexrDevRedOpFull red;
-    const nexrResult_t e = nexrHostToDevRedOp(&red, nexrSum, datatype, 1);
-    return e != nexrSuccess ? e : oneRank(c, 0, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype, red, esz);
-  }
-  if (oneGpu) {  // host counts: the launch reports nothing, the verdict is above
-    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
-    res = nexrFlatAllToAllv(n, sendbuffs, recvbuffs, counts, nexrScalarHostImmediate, esz, sendElts, recvElts, nullptr,
-                            0, (nexrStream_t)c->streams[0]);
-    return res != nexrSuccess ? res : symWait(c, c->streams[0]);
-  }
+  if (n == 1) return counts[0] ? oneRankCopy(c, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype) : nexrSuccess;
+  // host counts: the launch reports nothing, the verdict is above. With every count 0 it still runs: the flat entry
+  // answers that, and the wait follows.
+  if (oneGpu) return launch(counts, nexrScalarHostImmediate, nullptr);
   std::vector<size_t> sendOff((size_t)n, 0);  // bytes of sendbuffs[s] already sent, to ranks below d
-  for (int d = 0; d < n && res == nexrSuccess; d++) {
-    if (c->streams[d]) (void)hipSetDevice(c->devices[d]);
+  return blockCopies(c, [&](int d, auto copy) {
     size_t recvOff = 0;
-    for (int s = 0; s < n && res == nexrSuccess; s++) {
+    for (int s = 0; s < n; s++) {
       const size_t bytes = (size_t)counts[(size_t)s * n + d] * esz;
       if (bytes == 0) continue;
-      const void* src = (const char*)sendbuffs[s] + sendOff[(size_t)s];
-      void* dst = (char*)recvbuffs[d] + recvOff;
-      res = c->cfg.fn(1, &src, 1, &dst, bytes, nexrUint8, nexrDevSum, 0, 0, nullptr, 0, (nexrStream_t)c->streams[d]);
+      if (!copy((const char*)sendbuffs[s] + sendOff[(size_t)s], (char*)recvbuffs[d] + recvOff, bytes)) return;
       sendOff[(size_t)s] += bytes;
       recvOff += bytes;
     }
-    // also behind an error: nothing stays in flight over the caller's buffers
-    if (device && c->streams[d] && hipStreamSynchronize(c->streams[d]) != hipSuccess && res == nexrSuccess)
-      res = nexrUnhandledCudaError;
-  }
-  return res;
+  });
 }
 
 // nexrRingCommSetFlat: whether the plain ring all-reduce, reduce-scatter and reduce of this communicator run
@@ -1750,15 +1769,11 @@ nexrResult_t allToAllV(nexrRingComm* c, const void* const* sendbuffs, void* cons
 // fn / llFn / ll128Fn computes what it likes), and no more ranks than a flat launch takes; or thread ranks in
 // host memory that flatHostEligible takes.
 bool flatRouted(const nexrRingComm* c, int bit = NEXR_FLAT_RING) {
-  if (!c || !(c->flat & bit) || c->peer || c->broken || c->streams.empty() || !c->streams[0] ||
-      c->cfg.nRanks > NEXR_SYM_MAX_RANKS || (int)c->devices.size() < c->cfg.nRanks)
+  if (!c || !(c->flat & bit) || c->peer || c->broken || !hasFirstStream(c) || c->cfg.nRanks > NEXR_SYM_MAX_RANKS)
     return false;
   if (c->cfg.memMode != nexrRingDeviceMemory) return flatHostEligible(c);  // host memory: one launch on devices[0]
-  const bool ownFn = c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
-                     : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
-                                                      : c->cfg.fn == defaultDeviceFn;
-  if (!ownFn) return false;
-  for (int d : c->devices)
+  if (!ownStepFn(c)) return false;
+  for (int d : c->devices)  // every entry, not ranksShareGpu's first nRanks
     if (d != c->devices[0]) return false;
   return true;
 }
@@ -1894,190 +1909,84 @@ nexrResult_t symLLAllGather(nexrRingComm* c, const void* const* sendbuffs, void*
 }
 
 // ---- nexrRingGroupStart / nexrRingGroupEnd --------------------------------------------------------------------
-// Every collective entry of include/nexr_ring.h by number: what a recorded call remembers, and what runEntry runs.
-enum RingEntry {
-  kEntAllReduce, kEntReduceScatter, kEntAllGather, kEntReduce, kEntBroadcast, kEntTree,
-  kEntSymAllReduce, kEntSymReduceScatter, kEntSymAllGather,
-  kEntFlatAllReduce, kEntFlatReduceScatter, kEntFlatReduce, kEntFlatTree, kEntFlatBroadcast, kEntFlatAllGather,
-  kEntSymLLAllReduce, kEntSymLLReduceScatter, kEntSymLLAllGather,
-  kEntAllToAll,
-  kEntAllToAllV,  // recorded by nexrRingAllToAllv itself; groupExecute runs it, not runEntry
-  kEntReduceScatterV, kEntAllGatherV,  // likewise, by nexrRingReduceScatterv / nexrRingAllGatherv (scatterVRecord)
-  kEntAllToAll2D, kEntAllGather2D      // likewise, by nexrRingAllToAll2D / nexrRingAllGather2D (pitchedOrRecord)
-};
+// Whether an entry's run is wrapped in a DeviceGuard: it may move the thread's current device, on a communicator
+// that touches HIP at all. The symmetric entries launch in device memory only, the explicit flat ones also where
+// flatHostEligible takes the communicator.
+bool entryGuards(const nexrRingComm* c, int entry) {
+  if (!c || !c->needHip) return false;
+  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
+  if (entry >= kEntFlatAllReduce && entry <= kEntFlatAllGather) return device || flatHostEligible(c);
+  if (entry >= kEntSymAllReduce && entry <= kEntSymLLAllGather) return device;
+  return true;
+}
 
-// The entry as it runs alone.
+// An entry whose arguments are one count (every entry up to kEntAllToAll), as it runs alone.
 nexrResult_t runEntry(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
                       int datatype, int op, int root, int nBlocks) {
-  const bool dev = c && c->needHip && c->cfg.memMode == nexrRingDeviceMemory;
-  const bool flatDev = c && c->needHip && (c->cfg.memMode == nexrRingDeviceMemory || flatHostEligible(c));
+  DeviceGuard dg(entryGuards(c, entry));
   switch (entry) {
-    case kEntAllReduce: {
-      DeviceGuard dg(c && c->needHip);
-      return ringOrFlat(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
-    }
-    case kEntReduceScatter: {
-      DeviceGuard dg(c && c->needHip);
-      return ringOrFlat(c, kReduceScatter, sendbuffs, recvbuffs, count, datatype, op, 0);
-    }
-    case kEntAllGather: {
-      DeviceGuard dg(c && c->needHip);
-      return copyOrFlat(c, kAllGather, sendbuffs, recvbuffs, count, datatype, 0);  // ncclAllGather: ncclSum
-    }
-    case kEntReduce: {
-      DeviceGuard dg(c && c->needHip);
-      return ringOrFlat(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
-    }
-    case kEntBroadcast: {
-      DeviceGuard dg(c && c->needHip);
-      return copyOrFlat(c, kBroadcast, sendbuffs, recvbuffs, count, datatype, root);  // ncclBroadcast: ncclSum
-    }
-    case kEntTree: {
-      DeviceGuard dg(c && c->needHip);
-      return treeOrFlat(c, sendbuffs, recvbuffs, count, datatype, op);
-    }
-    case kEntSymAllReduce: {
-      DeviceGuard dg(dev);
-      return symAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
-    }
-    case kEntSymReduceScatter: {
-      DeviceGuard dg(dev);
-      return symReduceScatter(c, sendbuffs, recvbuffs, count, datatype, op);
-    }
-    case kEntSymAllGather: {
-      DeviceGuard dg(dev);
-      return symAllGather(c, sendbuffs, recvbuffs, count, datatype);
-    }
-    case kEntFlatAllReduce: {
-      DeviceGuard dg(flatDev);
-      return flatCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
-    }
-    case kEntFlatReduceScatter: {
-      DeviceGuard dg(flatDev);
-      return flatCollective(c, kReduceScatter, sendbuffs, recvbuffs, count, datatype, op, 0);
-    }
-    case kEntFlatReduce: {
-      DeviceGuard dg(flatDev);
-      return flatCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
-    }
-    case kEntFlatTree: {
-      DeviceGuard dg(flatDev);
-      return flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
-    }
-    case kEntFlatBroadcast: {
-      DeviceGuard dg(flatDev);
-      return flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
-    }
-    case kEntFlatAllGather: {
-      DeviceGuard dg(flatDev);
-      return flatAllGather(c, sendbuffs, recvbuffs, count, datatype);
-    }
-    case kEntSymLLAllReduce: {
-      DeviceGuard dg(dev);
-      return symLLAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
-    }
-    case kEntSymLLReduceScatter: {
-      DeviceGuard dg(dev);
-      return symLLReduceScatter(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
-    }
-    case kEntSymLLAllGather: {
-      DeviceGuard dg(dev);
-      return symLLAllGather(c, sendbuffs, recvbuffs, count, datatype, nBlocks);
-    }
-    case kEntAllToAll: {
-      DeviceGuard dg(c && c->needHip);
-      return allToAll(c, sendbuffs, recvbuffs, count, datatype);
-    }
+    case kEntAllReduce: return ringOrFlat(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+    case kEntReduceScatter: return ringOrFlat(c, kReduceScatter, sendbuffs, recvbuffs, count, datatype, op, 0);
+    case kEntAllGather: return copyOrFlat(c, kAllGather, sendbuffs, recvbuffs, count, datatype, 0);  // ncclSum
+    case kEntReduce: return ringOrFlat(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+    case kEntBroadcast: return copyOrFlat(c, kBroadcast, sendbuffs, recvbuffs, count, datatype, root);  // ncclSum
+    case kEntTree: return treeOrFlat(c, sendbuffs, recvbuffs, count, datatype, op);
+    case kEntSymAllReduce: return symAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+    case kEntSymReduceScatter: return symReduceScatter(c, sendbuffs, recvbuffs, count, datatype, op);
+    case kEntSymAllGather: return symAllGather(c, sendbuffs, recvbuffs, count, datatype);
+    case kEntFlatAllReduce: return flatCollective(c, kAllReduce, sendbuffs, recvbuffs, count, datatype, op, 0);
+    case kEntFlatReduceScatter: return flatCollective(c, kReduceScatter, sendbuffs, recvbuffs, count, datatype, op, 0);
+    case kEntFlatReduce: return flatCollective(c, kReduce, sendbuffs, recvbuffs, count, datatype, op, root);
+    case kEntFlatTree: return flatTreeAllReduce(c, sendbuffs, recvbuffs, count, datatype, op);
+    case kEntFlatBroadcast: return flatBroadcast(c, sendbuffs, recvbuffs, count, datatype, root);
+    case kEntFlatAllGather: return flatAllGather(c, sendbuffs, recvbuffs, count, datatype);
+    case kEntSymLLAllReduce: return symLLAllReduce(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+    case kEntSymLLReduceScatter: return symLLReduceScatter(c, sendbuffs, recvbuffs, count, datatype, op, nBlocks);
+    case kEntSymLLAllGather: return symLLAllGather(c, sendbuffs, recvbuffs, count, datatype, nBlocks);
+    case kEntAllToAll: return allToAll(c, sendbuffs, recvbuffs, count, datatype);
   }
   return nexrInvalidArgument;
 }
 
-// nexrRingReduceScatterv (scatter) and nexrRingAllGatherv. The checks that need no execution and no value of the
-// counts (they run when a call is recorded; readResident: whether a user op's device-resident scalars are read,
-// which a recording does not do): the op as nexrRingReduce's or the datatype as nexrRingAllGather's, the arrays,
-// the residence, and the capacity ranges as nexrFlatReduceScatterv compares them.
-nexrResult_t scatterVCheck(nexrRingComm* c, bool scatter, const void* const* sendbuffs, void* const* recvbuffs,
-                           const uint64_t* counts, int residence, int datatype, int op, const size_t* sendElts,
-                           const size_t* recvElts, const uint32_t* status, bool readResident, size_t* esz,
-                           RedOps* ops) {
-  if (!c) return nexrInvalidArgument;
-  if (c->peer) return nexrInvalidUsage;
-  nexrDevRedOpFull red;
-  const nexrResult_t r = scatter ? prepareOps(c, datatype, op, esz, ops, readResident)
-                                 : prepare(c, datatype, nexrSum, esz, &red);  // a copy: ncclSum, as the all-gather
-  if (r != nexrSuccess) return r;
-  if (!sendbuffs || !recvbuffs || !counts || !sendElts || !recvElts) return nexrInvalidArgument;
-  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
-  const bool dev = residence == nexrScalarDevice;
-  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
-  const int n = c->cfg.nRanks;
-  const bool ok = nexr_exchange_v::buffersOk(n, sendbuffs, recvbuffs, sendElts, recvElts, *esz, counts, status, dev,
-                                             (size_t)n);
-  return ok ? nexrSuccess : nexrInvalidArgument;
-}
-
-// Thread ranks in device memory on one GPU with the library's own step functions, and an op that one redOpArg
-// serves: ONE nexrFlatReduceScatterv / nexrFlatAllGatherv launch on the first stream and symCollective's wait, as
-// allToAllV; device counts are read by that kernel alone, and so is *status written. Any other thread-rank
-// communicator, and a user op whose ranks' scalars differ: device counts are read to the host behind the streams'
-// work, checked as host counts, and the non-empty pieces run in rank order as the communicator's own
-// nexrRingReduce (root d) / nexrRingBroadcast (root r) on the piece, whose bytes the one launch's are.
+// nexrRingReduceScatterv (scatter) and nexrRingAllGatherv. Thread ranks in device memory on one GPU with the
+// library's own step functions, and an op that one redOpArg serves: ONE nexrFlatReduceScatterv / nexrFlatAllGatherv
+// launch (launchAndWait); device counts are read by that kernel alone, and so is *status written. Any other
+// thread-rank communicator, and a user op whose ranks' scalars differ: device counts are read to the host, checked
+// as host counts, and the non-empty pieces run in rank order as the communicator's own nexrRingReduce (root d) /
+// nexrRingBroadcast (root r) on the piece, whose bytes the one launch's are.
 nexrResult_t scatterV(nexrRingComm* c, bool scatter, const void* const* sendbuffs, void* const* recvbuffs,
                       const uint64_t* counts, int residence, int datatype, int op, const size_t* sendElts,
                       const size_t* recvElts, uint32_t* status) {
+  const int entry = scatter ? kEntReduceScatterV : kEntAllGatherV;
   size_t esz = 0;
   RedOps ops;
-  nexrResult_t res = scatterVCheck(c, scatter, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
-                                   recvElts, status, true, &esz, &ops);
+  nexrResult_t res = countedCheck(c, entry, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts, recvElts,
+                                  status, true, &esz, &ops);
   if (res != nexrSuccess) return res;
   const int n = c->cfg.nRanks;
-  const bool dev = residence == nexrScalarDevice;
-  const bool device = c->cfg.memMode == nexrRingDeviceMemory;
-  bool one = device && n >= 2 && n <= NEXR_SYM_MAX_RANKS && (int)c->devices.size() >= n && !c->streams.empty() &&
-             c->streams[0] && !(scatter && ops.perRank(true));
-  one = one && (c->proto == nexrRingProtoLL      ? c->cfg.llFn == defaultLLFn
-                : c->proto == nexrRingProtoLL128 ? c->cfg.ll128Fn == defaultLL128Fn
-                                                 : c->cfg.fn == defaultDeviceFn);
-  for (int i = 0; one && i < n; i++)
-    if (c->devices[i] != c->devices[0]) one = false;
-  auto launch = [&](const uint64_t* cnt, int where, uint32_t* word) -> nexrResult_t {
-    if (hipSetDevice(c->devices[0]) != hipSuccess) return nexrUnhandledCudaError;
-    const nexrStream_t s = (nexrStream_t)c->streams[0];
-    const nexrResult_t r =
-        scatter ? nexrFlatReduceScatterv(n, sendbuffs, recvbuffs, cnt, where, datatype, ops.rank[0].op,
-                                         ops.rank[0].scalarArg, c->proto == nexrRingProtoSimple ? 1 : 0, sendElts,
-                                         recvElts, word, 0, s)
-                : nexrFlatAllGatherv(n, sendbuffs, recvbuffs, cnt, where, esz, sendElts, recvElts, word, 0, s);
-    return r != nexrSuccess ? r : symWait(c, c->streams[0]);
+  // allToAllV asks for a broken communicator here; this call does not (countedCheck has refused one)
+  const bool one = n >= 2 && deviceRanksOnOneGpu(c) && !(scatter && ops.perRank(true)) && ownStepFn(c);
+  auto launch = [&](const uint64_t* cnt, int where, uint32_t* word) {
+    return launchAndWait(c, [&](nexrStream_t s) {
+      return scatter ? nexrFlatReduceScatterv(n, sendbuffs, recvbuffs, cnt, where, datatype, ops.rank[0].op,
+                                              ops.rank[0].scalarArg, c->proto == nexrRingProtoSimple ? 1 : 0,
+                                              sendElts, recvElts, word, 0, s)
+                     : nexrFlatAllGatherv(n, sendbuffs, recvbuffs, cnt, where, esz, sendElts, recvElts, word, 0, s);
+    });
   };
-  if (one && dev) return launch(counts, residence, status);
+  if (one && residence == nexrScalarDevice) return launch(counts, residence, status);
   std::vector<uint64_t> read;
-  if (dev) {  // once per call, behind what the ranks' streams hold
-    read.resize((size_t)n);
-    if (!c->needHip) {
-      memcpy(read.data(), counts, read.size() * 8);
-    } else {
-      for (int i = 0; i < n; i++)
-        if (c->streams[i] && (hipSetDevice(c->devices[i]) != hipSuccess || hipStreamSynchronize(c->streams[i]) != hipSuccess))
-          return nexrUnhandledCudaError;
-      if (hipMemcpy(read.data(), counts, read.size() * 8, hipMemcpyDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return nexrUnhandledCudaError;
-      }
-    }
+  if (residence == nexrScalarDevice) {
+    if ((res = readCounts(c, counts, countWords(c, entry), &read)) != nexrSuccess) return res;
     counts = read.data();
   }
   uint64_t total = 0;
-  const bool fits = nexr_exchange_v::piecesFit(n, counts, sendElts, recvElts, scatter, &total);
-  res = allToAllVStatus(c, status, fits ? 0u : 1u);
-  if (!fits) return nexrInvalidArgument;
+  res = countsFitReport(c, entry, counts, sendElts, recvElts, status, true, &total);
   if (res != nexrSuccess) return res;
   if (n == 1) {
     if (counts[0] == 0) return nexrSuccess;
-    nexrDevRedOpFull red;
-    if (scatter) red = ops.rank[0];
-    else if ((res = nexrHostToDevRedOp(&red, nexrSum, datatype, 1)) != nexrSuccess) return res;
-    return oneRank(c, 0, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype, red, esz);
+    if (!scatter) return oneRankCopy(c, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype);
+    return oneRank(c, 0, sendbuffs[0], recvbuffs[0], (size_t)counts[0], datatype, ops.rank[0], esz);
   }
   if (one) return total ? launch(counts, nexrScalarHostImmediate, nullptr) : nexrSuccess;  // the verdict is above
   std::vector<const void*> ins((size_t)n);
@@ -2096,37 +2005,52 @@ nexrResult_t scatterV(nexrRingComm* c, bool scatter, const void* const* sendbuff
   return res;
 }
 
-// A nexrRingReduceScatterv / nexrRingAllGatherv call inside a group: checked and recorded, host arrays by value,
-// with nexrRingAllToAllv's rules (host counts above a capacity are refused now, with their report).
-nexrResult_t scatterVRecord(nexrRingComm* c, int entry, bool scatter, const void* const* sendbuffs,
-                            void* const* recvbuffs, const uint64_t* counts, int residence, int datatype, int op,
-                            const size_t* sendElts, const size_t* recvElts, uint32_t* status) {
-  size_t esz = 0;
-  RedOps ops;
-  const nexrResult_t r = scatterVCheck(c, scatter, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
-                                       recvElts, status, false, &esz, &ops);
-  if (r != nexrSuccess) return r;
+// Whether a call is made inside a group that is still recording.
+bool recording(const nexrRingComm* c) { return c && c->groupDepth > 0 && !c->groupRunning; }
+
+// A checked call joins the group: the fields every record shares; the caller fills in its entry's own.
+nexrRingComm::GroupCall& groupPush(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs,
+                                   int datatype) {
   const size_t n = (size_t)c->cfg.nRanks;
-  uint64_t total = 0;
-  if (residence == nexrScalarHostImmediate &&
-      !nexr_exchange_v::piecesFit((int)n, counts, sendElts, recvElts, scatter, &total)) {
-    (void)allToAllVStatus(c, status, 1u);
-    return nexrInvalidArgument;
-  }
-  nexrRingComm::GroupCall g;
+  c->groupCalls.push_back(nexrRingComm::GroupCall());
+  nexrRingComm::GroupCall& g = c->groupCalls.back();
   g.entry = entry;
   g.send.assign(sendbuffs, sendbuffs + n);
   g.recv.assign(recvbuffs, recvbuffs + n);
   g.datatype = datatype;
+  c->groupStats.calls++;
+  return g;
+}
+
+// A counted entry: inside a group it is checked and recorded, host arrays by value, else it runs. Host counts are
+// there when the call is recorded: a violation is refused then, as the call alone answers it, and not at the End.
+nexrResult_t countedOrRecord(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs,
+                             const uint64_t* counts, int residence, int datatype, int op, const size_t* sendElts,
+                             const size_t* recvElts, uint32_t* status) {
+  if (!recording(c)) {
+    DeviceGuard dg(entryGuards(c, entry));
+    if (entry == kEntAllToAllV)
+      return allToAllV(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status);
+    return scatterV(c, entry == kEntReduceScatterV, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
+                    recvElts, status);
+  }
+  size_t esz = 0;
+  RedOps ops;
+  uint64_t total = 0;
+  nexrResult_t r = countedCheck(c, entry, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts, recvElts,
+                                status, false, &esz, &ops);
+  if (r == nexrSuccess && residence == nexrScalarHostImmediate)
+    r = countsFitReport(c, entry, counts, sendElts, recvElts, status, false, &total);
+  if (r != nexrSuccess) return r;
+  const size_t n = (size_t)c->cfg.nRanks;
+  nexrRingComm::GroupCall& g = groupPush(c, entry, sendbuffs, recvbuffs, datatype);
   g.op = op;
   g.residence = residence;
   g.status = status;
   g.sendElts.assign(sendElts, sendElts + n);
   g.recvElts.assign(recvElts, recvElts + n);
   if (residence == nexrScalarDevice) g.countsPtr = counts;
-  else g.counts.assign(counts, counts + n);
-  c->groupCalls.push_back(std::move(g));
-  c->groupStats.calls++;
+  else g.counts.assign(counts, counts + countWords(c, entry));
   return nexrSuccess;
 }
 
@@ -2162,11 +2086,8 @@ nexrResult_t groupRecord(nexrRingComm* c, int entry, const void* const* sendbuff
   if (count > (size_t)-1 / esz / (size_t)n) return nexrInvalidArgument;
   if (entryNeedsOneGpu(entry)) {
     const bool host = entry >= kEntFlatAllReduce && entry <= kEntFlatAllGather && flatHostEligible(c);
-    if ((c->cfg.memMode != nexrRingDeviceMemory && !host) || (int)c->devices.size() < n || c->streams.empty() ||
-        !c->streams[0])
-      return nexrInvalidUsage;
-    for (int i = 0; i < n && !host; i++)
-      if (c->devices[i] != c->devices[0]) return nexrInvalidUsage;
+    if ((c->cfg.memMode != nexrRingDeviceMemory && !host) || !hasFirstStream(c)) return nexrInvalidUsage;
+    if (!host && !ranksShareGpu(c)) return nexrInvalidUsage;
     if (n > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
   }
   for (int i = 0; i < n && count != 0; i++) {
@@ -2174,62 +2095,59 @@ nexrResult_t groupRecord(nexrRingComm* c, int entry, const void* const* sendbuff
     const bool needRecv = !entryIsReduce(entry) || i == root;
     if ((needSend && !sendbuffs[i]) || (needRecv && !recvbuffs[i])) return nexrInvalidArgument;
   }
-  nexrRingComm::GroupCall g;
-  g.entry = entry;
-  g.send.assign(sendbuffs, sendbuffs + n);
-  g.recv.assign(recvbuffs, recvbuffs + n);
+  nexrRingComm::GroupCall& g = groupPush(c, entry, sendbuffs, recvbuffs, datatype);
   g.count = count;
-  g.datatype = datatype;
   g.op = op;
   g.root = root;
   g.nBlocks = nBlocks;
-  c->groupCalls.push_back(std::move(g));
-  c->groupStats.calls++;
   return nexrSuccess;
 }
 
 nexrResult_t groupOrRun(nexrRingComm* c, int entry, const void* const* sendbuffs, void* const* recvbuffs, size_t count,
                         int datatype, int op, int root, int nBlocks) {
-  if (c && c->groupDepth > 0 && !c->groupRunning)
-    return groupRecord(c, entry, sendbuffs, recvbuffs, count, datatype, op, root, nBlocks);
+  if (recording(c)) return groupRecord(c, entry, sendbuffs, recvbuffs, count, datatype, op, root, nBlocks);
   return runEntry(c, entry, sendbuffs, recvbuffs, count, datatype, op, root, nBlocks);
 }
 
 // A nexrRingAllToAll2D / nexrRingAllGather2D call: inside a group it is checked and recorded, else it runs.
 nexrResult_t pitchedOrRecord(nexrRingComm* c, bool gather, const void* const* sendbuffs, void* const* recvbuffs,
                              size_t rows, size_t count, int datatype, int inLayout, int outLayout) {
-  if (c && c->groupDepth > 0 && !c->groupRunning) {
-    size_t esz = 0;
-    const nexrResult_t r =
-        pitchedCheck(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout, &esz);
-    if (r != nexrSuccess) return r;
-    const size_t n = (size_t)c->cfg.nRanks;
-    nexrRingComm::GroupCall g;
-    g.entry = gather ? kEntAllGather2D : kEntAllToAll2D;
-    g.send.assign(sendbuffs, sendbuffs + n);
-    g.recv.assign(recvbuffs, recvbuffs + n);
-    g.count = count;
-    g.datatype = datatype;
-    g.rows = rows;
-    g.inLayout = inLayout;
-    g.outLayout = outLayout;
-    c->groupCalls.push_back(std::move(g));
-    c->groupStats.calls++;
-    return nexrSuccess;
+  const int entry = gather ? kEntAllGather2D : kEntAllToAll2D;
+  if (!recording(c)) {
+    DeviceGuard dg(entryGuards(c, entry));
+    return pitched(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout);
   }
-  DeviceGuard dg(c && c->needHip);
-  return pitched(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout);
+  size_t esz = 0;
+  const nexrResult_t r =
+      pitchedCheck(c, gather, sendbuffs, recvbuffs, rows, count, datatype, inLayout, outLayout, true, &esz);
+  if (r != nexrSuccess) return r;
+  nexrRingComm::GroupCall& g = groupPush(c, entry, sendbuffs, recvbuffs, datatype);
+  g.count = count;
+  g.rows = rows;
+  g.inLayout = inLayout;
+  g.outLayout = outLayout;
+  return nexrSuccess;
+}
+
+// A recorded call as it runs alone, whatever its entry.
+nexrResult_t runCall(nexrRingComm* c, const nexrRingComm::GroupCall& g) {
+  const uint64_t* counts = g.countsPtr ? g.countsPtr : g.counts.data();
+  switch (g.entry) {
+    case kEntAllToAllV: case kEntReduceScatterV: case kEntAllGatherV:
+      return countedOrRecord(c, g.entry, g.send.data(), g.recv.data(), counts, g.residence, g.datatype, g.op,
+                             g.sendElts.data(), g.recvElts.data(), g.status);
+    case kEntAllToAll2D: case kEntAllGather2D:
+      return pitchedOrRecord(c, g.entry == kEntAllGather2D, g.send.data(), g.recv.data(), g.rows, g.count, g.datatype,
+                             g.inLayout, g.outLayout);
+    default:
+      return runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
+  }
 }
 
 // Whether a recorded call becomes work records: it would run flat, as a ring all-reduce, reduce-scatter, reduce,
 // all-gather or broadcast, on a device-memory communicator of 2+ ranks on one GPU, with one redOpArg.
 bool groupTakes(nexrRingComm* c, const nexrRingComm::GroupCall& g, RedOps* ops, size_t* esz) {
-  const int n = c->cfg.nRanks;
-  if (c->peer || c->broken || c->cfg.memMode != nexrRingDeviceMemory || n < 2 || n > NEXR_SYM_MAX_RANKS ||
-      (int)c->devices.size() < n || c->streams.empty() || !c->streams[0])
-    return false;
-  for (int i = 0; i < n; i++)
-    if (c->devices[i] != c->devices[0]) return false;
+  if (c->peer || c->broken || c->cfg.nRanks < 2 || !deviceRanksOnOneGpu(c)) return false;
   switch (g.entry) {
     case kEntAllReduce: case kEntReduceScatter: case kEntReduce:
       if (!flatRouted(c, NEXR_FLAT_RING)) return false;
@@ -2357,22 +2275,7 @@ nexrResult_t groupExecute(nexrRingComm* c) {
     if (res == nexrSuccess) res = wait();
     if (res != nexrSuccess) break;
     c->groupStats.singles++;
-    if (g.entry == kEntAllToAllV) {
-      DeviceGuard dg(c->needHip);
-      res = allToAllV(c, g.send.data(), g.recv.data(), g.countsPtr ? g.countsPtr : g.counts.data(), g.residence,
-                      g.datatype, g.sendElts.data(), g.recvElts.data(), g.status);
-    } else if (g.entry == kEntReduceScatterV || g.entry == kEntAllGatherV) {
-      DeviceGuard dg(c->needHip);
-      res = scatterV(c, g.entry == kEntReduceScatterV, g.send.data(), g.recv.data(),
-                     g.countsPtr ? g.countsPtr : g.counts.data(), g.residence, g.datatype, g.op, g.sendElts.data(),
-                     g.recvElts.data(), g.status);
-    } else if (g.entry == kEntAllToAll2D || g.entry == kEntAllGather2D) {
-      DeviceGuard dg(c->needHip);
-      res = pitched(c, g.entry == kEntAllGather2D, g.send.data(), g.recv.data(), g.rows, g.count, g.datatype,
-                    g.inLayout, g.outLayout);
-    } else {
-      res = runEntry(c, g.entry, g.send.data(), g.recv.data(), g.count, g.datatype, g.op, g.root, g.nBlocks);
-    }
+    res = runCall(c, g);
     if (res != nexrSuccess) break;
   }
   if (res == nexrSuccess) res = flush();
@@ -2574,54 +2477,22 @@ NEXR_API nexrResult_t nexrRingAllGather2D(nexrRingComm_t c, const void* const* s
 NEXR_API nexrResult_t nexrRingAllToAllv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                         const uint64_t* counts, int residence, int datatype, const size_t* sendElts,
                                         const size_t* recvElts, uint32_t* status) {
-  if (c && c->groupDepth > 0 && !c->groupRunning) {  // checked and recorded: host arrays by value
-    size_t esz = 0;
-    const nexrResult_t r =
-        allToAllVCheck(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status, &esz);
-    if (r != nexrSuccess) return r;
-    // host counts are here already: a violation is refused now, as the call alone answers it, and not at the End
-    if (residence == nexrScalarHostImmediate && !allToAllVFits(c->cfg.nRanks, counts, sendElts, recvElts)) {
-      (void)allToAllVStatus(c, status, 1u);
-      return nexrInvalidArgument;
-    }
-    const size_t n = (size_t)c->cfg.nRanks;
-    nexrRingComm::GroupCall g;
-    g.entry = kEntAllToAllV;
-    g.send.assign(sendbuffs, sendbuffs + n);
-    g.recv.assign(recvbuffs, recvbuffs + n);
-    g.datatype = datatype;
-    g.residence = residence;
-    g.status = status;
-    g.sendElts.assign(sendElts, sendElts + n);
-    g.recvElts.assign(recvElts, recvElts + n);
-    if (residence == nexrScalarDevice) g.countsPtr = counts;
-    else g.counts.assign(counts, counts + n * n);
-    c->groupCalls.push_back(std::move(g));
-    c->groupStats.calls++;
-    return nexrSuccess;
-  }
-  DeviceGuard dg(c && c->needHip);
-  return allToAllV(c, sendbuffs, recvbuffs, counts, residence, datatype, sendElts, recvElts, status);
+  return countedOrRecord(c, kEntAllToAllV, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum, sendElts,
+                         recvElts, status);
 }
 
 NEXR_API nexrResult_t nexrRingReduceScatterv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                              const uint64_t* counts, int residence, int datatype, int op,
                                              const size_t* sendElts, const size_t* recvElts, uint32_t* status) {
-  if (c && c->groupDepth > 0 && !c->groupRunning)
-    return scatterVRecord(c, kEntReduceScatterV, true, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
-                          recvElts, status);
-  DeviceGuard dg(c && c->needHip);
-  return scatterV(c, true, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts, recvElts, status);
+  return countedOrRecord(c, kEntReduceScatterV, sendbuffs, recvbuffs, counts, residence, datatype, op, sendElts,
+                         recvElts, status);
 }
 
 NEXR_API nexrResult_t nexrRingAllGatherv(nexrRingComm_t c, const void* const* sendbuffs, void* const* recvbuffs,
                                          const uint64_t* counts, int residence, int datatype,
                                          const size_t* sendElts, const size_t* recvElts, uint32_t* status) {
-  if (c && c->groupDepth > 0 && !c->groupRunning)
-    return scatterVRecord(c, kEntAllGatherV, false, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum,
-                          sendElts, recvElts, status);
-  DeviceGuard dg(c && c->needHip);
-  return scatterV(c, false, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum, sendElts, recvElts, status);
+  return countedOrRecord(c, kEntAllGatherV, sendbuffs, recvbuffs, counts, residence, datatype, nexrSum, sendElts,
+                         recvElts, status);
 }
 
 NEXR_API nexrResult_t nexrRingGroupStart(nexrRingComm_t c) {

@@ -413,6 +413,140 @@ def test_ring_group_usage(ring, nexr, oracle, fns):
             comm.group_end()
 
 
+class Recorder:
+    """A nexrReduceCopyFn that notes every call and forwards it to the oracle's."""
+    _ARGS = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+             ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+
+    def __init__(self, ring, oracle):
+        self.target = oracle.lib().oracle_reduce_copy_fn
+        self.target.argtypes, self.target.restype = self._ARGS, ctypes.c_int
+        self.seen = []
+        self.cb = ring.REDUCE_COPY_FN(self._call)
+        self.address = ctypes.cast(self.cb, ctypes.c_void_p).value
+
+    def _call(self, n_srcs, srcs, n_dsts, dsts, n_elts, datatype, op, arg, n_pre, pre, post, stream):
+        self.seen.append((tuple(srcs[i] for i in range(n_srcs)), tuple(dsts[i] for i in range(n_dsts)), n_elts,
+                          datatype, op))
+        cast = lambda p: ctypes.cast(p, ctypes.c_void_p)  # noqa: E731
+        return self.target(n_srcs, cast(srcs), n_dsts, cast(dsts), n_elts, datatype, op, arg, n_pre, cast(pre), post,
+                           stream)
+
+
+class EightCalls:
+    """Three ranks' buffers (float32, seeded inputs, zeroed outputs) for one call of each shape a record takes, and
+    the calls in the order of the list: a plain one, nexrRingAllToAll, the three counted entries (the all-to-all-v
+    under both residences; device counts are host memory here) and the two pitched ones."""
+    N = 3
+    MATRIX = (1, 0, 2, 3, 1, 0, 2, 2, 4)     # [s * 3 + d]: a zero, unequal rows and columns
+    PIECES = (2, 0, 3)
+
+    def __init__(self, nexr):
+        F32 = int(nexr.DataType.Float32)
+        self.rows_in_blocks_out = (nexr.LAYOUT_ROWS, nexr.LAYOUT_BLOCKS)
+        n, rng = self.N, np.random.default_rng(rm.SEED)
+        m = np.asarray(self.MATRIX).reshape(n, n)
+        sizes = {"all_reduce": ([5] * n, [5] * n), "all_to_all": ([9] * n, [9] * n),
+                 "all_to_all_v host": (m.sum(axis=1), m.sum(axis=0)), "all_to_all_v device": (m.sum(axis=1), m.sum(axis=0)),
+                 "reduce_scatter_v": ([5] * n, self.PIECES), "all_gather_v": (self.PIECES, [5] * n),
+                 "all_to_all_2d": ([18] * n, [18] * n), "all_gather_2d": ([6] * n, [18] * n)}
+        self.ins = {k: [rng.integers(1, 50, int(e) + 1).astype(np.float32) for e in s[0]] for k, s in sizes.items()}
+        self.outs = {k: [np.zeros(int(e) + 1, np.float32) for e in s[1]] for k, s in sizes.items()}
+        self.device_counts = np.asarray(self.MATRIX, np.uint64)
+        self.status = np.full(1, 7, np.uint32)
+        self.F32 = F32
+
+    def issue(self, comm, name):
+        F32, (s, r) = self.F32, ([a.ctypes.data for a in b[name]] for b in (self.ins, self.outs))
+        caps = [[a.size for a in b[name]] for b in (self.ins, self.outs)]
+        {"all_reduce": lambda: comm.all_reduce(s, r, 5, F32, rm.SUM),
+         "all_to_all": lambda: comm.all_to_all(s, r, 3, F32),
+         "all_to_all_v host": lambda: comm.all_to_all_v(s, r, self.MATRIX, F32, *caps),
+         "all_to_all_v device": lambda: comm.all_to_all_v(s, r, self.device_counts.ctypes.data, F32, *caps,
+                                                          self.status.ctypes.data),
+         "reduce_scatter_v": lambda: comm.reduce_scatter_v(s, r, self.PIECES, F32, rm.SUM, *caps),
+         "all_gather_v": lambda: comm.all_gather_v(s, r, self.PIECES, F32, *caps),
+         "all_to_all_2d": lambda: comm.all_to_all_2d(s, r, 2, 3, F32, *self.rows_in_blocks_out),
+         "all_gather_2d": lambda: comm.all_gather_2d(s, r, 2, 3, F32)}[name]()
+
+    def named(self, seen):
+        """Recorded calls with every address inside a user buffer as (buffer, offset) and any other as None: the
+        FIFO slots that a step reads or writes follow the communicator's step counters, not the call."""
+        spans = [(a.ctypes.data, a.nbytes, (side, name, i)) for side, bufs in (("in", self.ins), ("out", self.outs))
+                 for name, arrays in bufs.items() for i, a in enumerate(arrays)]
+
+        def where(p):
+            return next(((tag, p - base) for base, size, tag in spans if base <= p < base + size), None)
+
+        return [(tuple(map(where, srcs)), tuple(map(where, dsts)), n_elts, datatype, op)
+                for srcs, dsts, n_elts, datatype, op in seen]
+
+
+def test_ring_group_records_and_runs_every_entry_shape(ring, nexr, oracle, fns):
+    """One call of each shape inside one group on a host-memory communicator with a caller's fn: every output is the
+    single call's on fresh buffers, fn sees the single calls' sequences one after the other, and each counts as one
+    of `singles`. A step of the ring runs on its rank's thread, so the calls that run as ring collectives (the first,
+    and the pieces of the two with a count per rank) are compared as multisets; the block copies in order."""
+    F32 = int(nexr.DataType.Float32)
+    rec = Recorder(ring, oracle)
+    alone, grouped = EightCalls(nexr), EightCalls(nexr)
+    names = list(alone.ins)
+    threaded = {"all_reduce", "reduce_scatter_v", "all_gather_v"}
+    with ring.RingComm(3, ring.HOST_MEMORY, rm.BUFF["simple"], rec.address, 20000, rm.PROTO_ID["simple"], fns[1], fns[2],
+                       rm.tree_per_node(3), 0, 1) as comm:
+        single = {}
+        for name in names:
+            rec.seen = []
+            alone.issue(comm, name)
+            single[name] = alone.named(rec.seen)
+            assert single[name], name
+        assert alone.status[0] == 0
+        rec.seen = []
+        comm.group_stats(reset=True)
+        with comm.group():
+            for name in names:
+                grouped.issue(comm, name)
+            assert not rec.seen and not any(a.any() for arrays in grouped.outs.values() for a in arrays)
+            assert comm.group_stats() == {"calls": 8, "group_launches": 0, "fill_launches": 0, "singles": 0, "cuts": 0}
+        assert comm.group_stats() == {"calls": 8, "group_launches": 0, "fill_launches": 0, "singles": 8, "cuts": 0}
+        assert grouped.status[0] == 0
+        for name in names:
+            for got, want in zip(grouped.outs[name], alone.outs[name]):
+                np.testing.assert_array_equal(got, want, err_msg=name)
+            assert any(a.any() for a in alone.outs[name]), name
+        seen, at = grouped.named(rec.seen), 0
+        assert len(seen) == sum(len(s) for s in single.values())
+        for name in names:
+            part = seen[at:at + len(single[name])]
+            at += len(part)
+            if name in threaded:
+                assert sorted(part, key=repr) == sorted(single[name], key=repr), name
+            else:
+                assert part == single[name], name
+
+        # a host count above its capacity is refused when it is recorded, with its report, and the group goes on
+        comm.group_stats(reset=True)
+        bad = nexr.Result.InvalidArgument
+        with comm.group():
+            grouped.issue(comm, "all_reduce")
+            s, r = ([a.ctypes.data for a in b["all_to_all_v host"]] for b in (grouped.ins, grouped.outs))
+            caps = [[a.size for a in b["all_to_all_v host"]] for b in (grouped.ins, grouped.outs)]
+            over = list(EightCalls.MATRIX)
+            over[1] = caps[1][1] + 1                  # rank 0 to rank 1: above recvElts[1]
+            grouped.status[0] = 7
+            with pytest.raises(nexr.NexrError) as e:
+                comm.all_to_all_v(s, r, over, F32, *caps, grouped.status.ctypes.data)
+            assert e.value.code == bad and grouped.status[0] == 1
+            s, r = ([a.ctypes.data for a in b["all_gather_v"]] for b in (grouped.ins, grouped.outs))
+            caps = [[a.size for a in b["all_gather_v"]] for b in (grouped.ins, grouped.outs)]
+            grouped.status[0] = 7
+            with pytest.raises(nexr.NexrError) as e:
+                comm.all_gather_v(s, r, (caps[0][0] + 1, 0, 3), F32, *caps, grouped.status.ctypes.data)
+            assert e.value.code == bad and grouped.status[0] == 1
+            assert comm.group_stats()["calls"] == 1
+        assert comm.group_stats() == {"calls": 1, "group_launches": 0, "fill_launches": 0, "singles": 1, "cuts": 0}
+
+
 def test_the_group_kernels_are_46_and_two_without_scratch():
     """flat_group_kernel has one instance per (datatype, device op) as flat_kernel, beside flat_group_copy_kernel and
     flat_group_fill_kernel; none has a private segment, a spilled vector register or a dynamic stack (read out of the

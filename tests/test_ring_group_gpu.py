@@ -175,6 +175,76 @@ def test_tree_and_per_rank_ops_run_singly_at_their_place(ring, oracle):
         comm.destroy_op(user)
 
 
+class CountedAndPitched:
+    """Three ranks' device buffers (float32, seeded inputs, zeroed outputs, one element of slack) for an all-reduce, an
+    all-to-all-v and a reduce-scatter-v with device counts, a last-dim all-gather and a second all-reduce."""
+    MATRIX = (1, 0, 2, 3, 1, 0, 2, 2, 4)     # [s * 3 + d]: a zero, and blocks of one element (4 bytes)
+    PIECES = (2, 0, 3)
+
+    def __init__(self):
+        m = np.asarray(self.MATRIX).reshape(3, 3)
+        sizes = {"first": ([5] * 3, [5] * 3), "all_to_all_v": (m.sum(axis=1), m.sum(axis=0)),
+                 "reduce_scatter_v": ([5] * 3, self.PIECES), "all_gather_2d": ([6] * 3, [18] * 3),
+                 "second": ([5] * 3, [5] * 3)}
+        rng = np.random.default_rng(SEED)
+        dev = lambda a: torch.from_numpy(a).to("cuda")  # noqa: E731
+        self.ins = {k: [dev(rng.integers(1, 50, int(e) + 1).astype(np.float32)) for e in s[0]] for k, s in sizes.items()}
+        self.outs = {k: [dev(np.zeros(int(e) + 1, np.float32)) for e in s[1]] for k, s in sizes.items()}
+        self.matrix, self.pieces = dev(np.asarray(self.MATRIX, np.int64)), dev(np.asarray(self.PIECES, np.int64))
+        self.status = dev(np.full(2, 7, np.int32))
+        torch.cuda.synchronize()
+
+    def issue(self, comm, name):
+        s, r = ([t.data_ptr() for t in b[name]] for b in (self.ins, self.outs))
+        caps = [[t.numel() for t in b[name]] for b in (self.ins, self.outs)]
+        word = self.status.data_ptr()
+        if name == "all_to_all_v":
+            comm.all_to_all_v(s, r, self.matrix.data_ptr(), ae.F32, *caps, word)
+        elif name == "reduce_scatter_v":
+            comm.reduce_scatter_v(s, r, self.pieces.data_ptr(), ae.F32, rm.SUM, *caps, word + 4)
+        elif name == "all_gather_2d":
+            comm.all_gather_2d(s, r, 2, 3, ae.F32)
+        else:
+            comm.all_reduce(s, r, 5, ae.F32, rm.SUM)
+
+    def results(self):
+        torch.cuda.synchronize()
+        return {k: [t.cpu().numpy() for t in ts] for k, ts in self.outs.items()}, self.status.cpu().numpy()
+
+
+def test_counted_and_pitched_calls_run_singly_between_group_launches(ring, oracle):
+    """The entries with a record of their own (device counts by their address, rows and layouts) inside a group with
+    flat all-reduces around them: each ends the run of flat works and executes alone with the bytes of the call made
+    alone, and the two all-reduces go out as the launches that two groups of one all-reduce take."""
+    with make_comm(ring, "simple", 3, 1) as comm:
+        comm.set_flat(True)
+        alone, pair, grouped = CountedAndPitched(), CountedAndPitched(), CountedAndPitched()
+        for name in alone.ins:
+            alone.issue(comm, name)
+        want, want_status = alone.results()
+        comm.group_stats(reset=True)
+        for name in ("first", "second"):
+            with comm.group():
+                pair.issue(comm, name)
+        two_runs = comm.group_stats(reset=True)
+        assert two_runs["calls"] == 2 and two_runs["singles"] == 0 and two_runs["group_launches"] >= 2, two_runs
+        with comm.group():
+            for name in grouped.ins:
+                grouped.issue(comm, name)
+        stats = comm.group_stats()
+        got, got_status = grouped.results()
+        assert stats["calls"] == 5 and stats["singles"] == 3, stats
+        assert stats["group_launches"] == two_runs["group_launches"], (stats, two_runs)
+        assert comm.queued() == 5
+        assert list(want_status) == [0, 0] and list(got_status) == [0, 0]
+        for name in want:
+            for g, w in zip(got[name], want[name]):
+                np.testing.assert_array_equal(g, w, err_msg=name)
+            assert any(w.any() for w in want[name]), name
+        for g, w in zip(pair.results()[0]["second"], want["second"]):
+            np.testing.assert_array_equal(g, w)
+
+
 def test_set_flat_between_groups_and_calls_after_a_group(ring, oracle):
     n, protocol = 2, "ll"
     calls = mixed_calls(protocol, n, 1, 6)
