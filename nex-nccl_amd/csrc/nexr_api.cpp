@@ -18,24 +18,20 @@
 #include <type_traits>
 #include <vector>
 
-#include "nexr_internal.h"
-#include "nexr_exchange_v_checks.h"
+#include "nexr_host.h"
 
+// What nexr_host.h declares is defined here outside the unnamed namespace, each with its one definition.
 namespace nexr {
 namespace {
-
 thread_local int tLastHipError = 0;
+}  // namespace
 
-inline nexrResult_t hipFail(hipError_t e) {
+nexrResult_t hipFail(hipError_t e) {
   tLastHipError = (int)e;
   return nexrUnhandledCudaError;
 }
-#define NEXR_HIP(call)                          \
-  do {                                          \
-    hipError_t e_ = (call);                     \
-    if (e_ != hipSuccess) return hipFail(e_);   \
-  } while (0)
 
+namespace {
 // ---- host-path counters (nexrGetHostPathStats): where a nexrReduceCopyHost call spends its time
 std::atomic<uint64_t> gHpCalls{0}, gHpZeroCopy{0}, gHpRegHits{0}, gHpQueries{0};
 std::atomic<uint64_t> gHpClassifyNs{0}, gHpCopyNs{0}, gHpLaunchNs{0}, gHpWaitNs{0};
@@ -44,7 +40,7 @@ inline uint64_t nowNs() {
              std::chrono::steady_clock::now().time_since_epoch())
       .count();
 }
-
+}  // namespace
 
 size_t typeSize(int dt) {
   switch (dt) {
@@ -56,7 +52,6 @@ size_t typeSize(int dt) {
   return 0;
 }
 bool isInteger(int dt) { return dt >= nexrInt8 && dt <= nexrUint64; }
-bool isSignedInt(int dt) { return dt == nexrInt8 || dt == nexrInt32 || dt == nexrInt64; }
 
 long envLong(const char* name, long dflt) {
   const char* v = getenv(name);
@@ -64,9 +59,13 @@ long envLong(const char* name, long dflt) {
   return strtol(v, nullptr, 0);
 }
 
+namespace {
+bool isSignedInt(int dt) { return dt == nexrInt8 || dt == nexrInt32 || dt == nexrInt64; }
+
 // Reduction semantics (include/nexr.h, nexrSetSemantics): process-wide, like an NCCL parameter; the
 // initial value comes from NEXR_SEMANTICS the first time a call needs it.
 std::atomic<int> gSemantics{-1};
+}  // namespace
 
 int semantics() {
   int s = gSemantics.load(std::memory_order_relaxed);
@@ -79,6 +78,7 @@ int semantics() {
   return gSemantics.load(std::memory_order_relaxed);
 }
 
+namespace {
 // The fork's kernel dispatch (equivalent_primary, generate.py:128-136): signed Min/Max run on the
 // unsigned kernel, whose FuncMinMax never applies the sign xormask hostToDevRedOp encodes.
 int forkDispatchType(int dt, int op) {
@@ -129,6 +129,8 @@ void routeKernel(CallShape& c, size_t* nElts) {
   if (c.op != nexrDevMinMax) c.dt = unsignedOf(c.dt);
 }
 
+}  // namespace
+
 // The same for an LL / LL128 step (after validation): shipped → every reduce returns its first operand,
 // the peer (prims_ll.h:288-294, prims_ll128.h:225-255), with no pre-op and no post-op.
 void llSemantics(int* dt, int* op, int* srcIsInput, int* postOp, int* firstWins) {
@@ -143,6 +145,8 @@ void llSemantics(int* dt, int* op, int* srcIsInput, int* postOp, int* firstWins)
     *firstWins = 1;
   }
 }
+
+namespace {
 
 // Cache policy by the bytes a call streams (every src read once, every dst written once): plain below
 // NEXR_NT_LOAD_MIN_BYTES (64 MiB: the data likely sits in L2/MALL and the consumer wants the output
@@ -170,10 +174,14 @@ int pickPolicy(uint64_t streamBytes, int nSrcs = 0, int nDsts = 0) {
   return streamBytes >= (uint64_t)ntStoreMin ? 3 : (streamBytes >= (uint64_t)ntLoadMin ? 1 : 0);
 }
 
+}  // namespace
+
 // Grid: one workgroup per kTripPacks-pack trip ("one-shot"), capped so that grid x block stays
 // within HIP's 2^32 - 1 work-item limit (2^24 workgroups of 256 lanes, 2^22 of 1024); beyond the
 // cap the kernel grid-strides. NEXR_GRID overrides the grid for sweeps.
 uint64_t gridCap(int block) { return 0xffffffffull / (uint64_t)block; }
+
+namespace {
 
 nexrResult_t pickGeometry(uint64_t workgroups, int pol, int block, Geometry* g) {
   static const long gridOverride = envLong("NEXR_GRID", 0);
@@ -407,6 +415,8 @@ nexrResult_t launchSingle(const RCParams& p, int dt, int op, int nSrcs, hipStrea
   return nexrSuccess;
 }
 
+}  // namespace
+
 // maxGrid > 0 caps the grid (the kernel grid-strides): launches that read or write host memory over
 // PCIe use hostGrid() workgroups. With a one-shot grid every workgroup's loads are interleaved over the
 // whole transfer, so every workgroup's last load lands near its end and the writes start only then;
@@ -417,6 +427,8 @@ uint64_t hostGrid() {
   static const long g = envLong("NEXR_HOST_GRID", 32);
   return g > 0 ? (uint64_t)g : 0;
 }
+
+namespace {
 
 nexrResult_t reduceCopyDevice(int nSrcs, const void* const* srcs, int nDsts, void* const* dsts,
                               size_t nElts, int datatype, int op, uint64_t redOpArg, int nPreOpSrcs,
@@ -571,37 +583,28 @@ nexrResult_t reduceCopyMultiDevice(const nexrReduceCopyWork* works, const int* d
 // pool holds, per device, as many rings as host calls have ever run there at once. (The emulated
 // collectives run each call's ranks on fresh threads: a ring cached per thread would be a new device
 // allocation and stream per thread, never freed.)
-struct HostStage {
-  int device = -1;
-  char* buf = nullptr;
-  size_t slotBytes = 0;  // bytes per slot
-  hipStream_t out = nullptr;
-  hipEvent_t kernelDone[2] = {nullptr, nullptr};
-  hipEvent_t outDone[2] = {nullptr, nullptr};
-};
+// (HostStage and StageLease: nexr_host.h.)
 std::mutex gStageMu;
 std::vector<HostStage*> gStageIdle;
 uint64_t gStagesCreated = 0;  // under gStageMu (nexrGetPoolStats)
+
+}  // namespace
 
 // Checks a ring out for the current device (the largest idle one, or a new one) and hands it back
 // when the call ends. Release drains the ring's stream and the caller's stream first, so that no
 // copy of this call still targets the slots when another call takes the ring; a ring whose streams
 // report an error is dropped rather than reused.
-struct StageLease {
-  HostStage* st = nullptr;
-  hipStream_t caller = nullptr;
-  ~StageLease() {
-    if (!st) return;
-    bool ok = hipStreamSynchronize(st->out) == hipSuccess;
-    ok = hipStreamSynchronize(caller) == hipSuccess && ok;
-    if (!ok) {
-      (void)hipGetLastError();
-      return;
-    }
-    std::lock_guard<std::mutex> g(gStageMu);
-    gStageIdle.push_back(st);
+StageLease::~StageLease() {
+  if (!st) return;
+  bool ok = hipStreamSynchronize(st->out) == hipSuccess;
+  ok = hipStreamSynchronize(caller) == hipSuccess && ok;
+  if (!ok) {
+    (void)hipGetLastError();
+    return;
   }
-};
+  std::lock_guard<std::mutex> g(gStageMu);
+  gStageIdle.push_back(st);
+}
 
 nexrResult_t stageFor(size_t slotBytes, hipStream_t caller, StageLease* lease) {
   int dev = 0;
@@ -676,6 +679,8 @@ hipError_t hostCopyPieces(char* dev, char* host, size_t bytes, bool toDevice, hi
   }
   return hipSuccess;
 }
+
+namespace {
 
 // ---- host-staged variant, large pageable calls: a CPU copy team and pinned zero-copy slots -------
 // The runtime's pageable hipMemcpyAsync copies through its own staging buffer with one CPU memcpy
@@ -998,6 +1003,8 @@ uintptr_t pageSize() {
 uintptr_t pageFloor(uintptr_t a) { return a & ~(pageSize() - 1); }
 uintptr_t pageCeil(uintptr_t a) { return (a + pageSize() - 1) & ~(pageSize() - 1); }
 
+}  // namespace
+
 // The device address of [p, p + bytes) when the whole range lies inside one entry.
 bool regLookup(const void* p, size_t bytes, void** dev) {
   const uintptr_t a = (uintptr_t)p;
@@ -1009,6 +1016,8 @@ bool regLookup(const void* p, size_t bytes, void** dev) {
   *dev = r->dev + (a - r->beg);
   return true;
 }
+
+namespace {
 
 // Index of the entry containing [a, a + n), -1 if none; overlap: some entry intersects it; sharesPage:
 // some entry shares a page with it.
@@ -2158,1787 +2167,6 @@ NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const n
                                                            size_t workspaceBytes, nexrStream_t stream) {
   return simpleStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, workgroupsPerMember, direct,
                           status, timeoutUs, workspace, workspaceBytes, stream);
-}
-
-// The ownership plan of nexrSymAllReduce from rank 0's pointers (include/nexr.h; reference
-// src/device/symmetric/all_reduce.hh:199-252): the two passes' piece counts and where the ends lie.
-static void symPlan(uintptr_t in0, uintptr_t out0, uint64_t nElts, uint64_t esz, uint64_t nRanksBlocks,
-                    nexr::SymParams* p) {
-  const uint64_t nBytes = nElts * esz;
-  const uint64_t pre = std::min<uint64_t>((16u - in0) % 16u, nBytes);  // nPreBytes (:207-208)
-  const uint64_t d = (in0 - out0) % 16u;
-  uint64_t cursor = pre;
-  p->p1Off = cursor;
-  p->p1Pieces = 0;
-  if (d == 0) {  // 16-byte packs: chunks of 4 warps x 4 packs x 32 lanes (:213-228)
-    uint64_t chunks = (nBytes - cursor) / 8192;
-    chunks -= chunks % nRanksBlocks;
-    p->p1Pieces = chunks * 4;
-    cursor += chunks * 8192;
-  }
-  p->p2Off = cursor;
-  p->p2Pieces = 0;
-  if (esz == 4 || d % 4 == 0) {  // 4-byte packs (:230-245)
-    uint64_t chunks = (nBytes - cursor) / 2048;
-    chunks -= chunks % nRanksBlocks;
-    p->p2Pieces = chunks * 4;
-    cursor += chunks * 2048;
-  }
-  p->preElts = pre / esz;  // the ends (:249-251): nPreElts, then nSufElts from the cursor
-  p->sufOff = cursor;
-  p->nEnds = p->preElts + (nBytes - cursor) / esz;
-}
-
-NEXR_API nexrResult_t nexrSymAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
-                                       int datatype, int devRedOp, uint64_t redOpArg, int nBlocks,
-                                       nexrStream_t stream) {
-  (void)redOpArg;
-  if (!inputs || !outputs) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS || nBlocks < 0 || nBlocks > 64) return nexrInvalidArgument;
-  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
-  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
-  const uint64_t esz = typeSize(datatype);
-  SymParams p;
-  memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
-    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-  }
-  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
-  if (nElts == 0) return nexrSuccess;
-  symPlan((uintptr_t)inputs[0], (uintptr_t)outputs[0], nElts, esz, (uint64_t)nRanks * (uint64_t)(nBlocks ? nBlocks : 1),
-          &p);
-  p.nRanks = nRanks;
-  p.nFold = semantics() == nexrSemanticsShipped ? 1 : nRanks;  // SKIP_COMP: every add returns its first operand
-  // One-shot: a wave per piece or group of 32 end elements, four waves per workgroup; beyond the cap the
-  // kernel strides.
-  const uint64_t items = p.p1Pieces + p.p2Pieces + (p.nEnds + 31) / 32;
-  const uint64_t grid = std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
-  NEXR_HIP(launch_sym_all_reduce(datatype, p, (unsigned)grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// The one-shot grid of the symmetric reduce-scatter and all-gather: every chunk of chunkBytes is whole
-// 2048-byte pieces, groups of 64 16-byte packs and one tail item; a wave per item and rank, four waves per
-// workgroup; beyond the cap the kernels stride.
-static unsigned symChunkGrid(uint64_t chunkBytes, uint64_t esz, int nRanks) {
-  const uint64_t rem = chunkBytes % 2048;
-  const uint64_t perRank = chunkBytes / 2048 + (rem / 16 + 63) / 64 + (rem % 16 / esz ? 1 : 0);
-  const uint64_t items = perRank * (uint64_t)nRanks;
-  return (unsigned)std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
-}
-
-NEXR_API nexrResult_t nexrSymReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
-                                           size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                           nexrStream_t stream) {
-  (void)redOpArg;
-  if (!inputs || !outputs) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
-  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
-  const uint64_t esz = typeSize(datatype);
-  SymRsParams p;
-  memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
-    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-  }
-  if (nElts > (size_t)-1 / esz / (size_t)nRanks) return nexrInvalidArgument;  // an input's nRanks * nElts * esz bytes
-  if (nElts == 0) return nexrSuccess;
-  p.chunkBytes = (uint64_t)nElts * esz;
-  p.nRanks = nRanks;
-  p.nFold = semantics() == nexrSemanticsShipped ? 1 : nRanks;  // SKIP_COMP: every add returns its first operand
-  NEXR_HIP(launch_sym_reduce_scatter(datatype, p, symChunkGrid(p.chunkBytes, esz, nRanks), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrSymAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
-                                       nexrStream_t stream) {
-  if (!inputs || !outputs) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (nBytes > (size_t)-1 / (size_t)nRanks) return nexrInvalidArgument;  // an output's nRanks * nBytes bytes
-  SymAgParams p;
-  memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-    // the reference's inPlace, per rank
-    if ((uintptr_t)inputs[r] == (uintptr_t)outputs[r] + (uintptr_t)r * nBytes) p.inPlace |= 1ull << r;
-  }
-  if (nBytes == 0) return nexrSuccess;
-  p.nBytes = nBytes;
-  p.nRanks = nRanks;
-  NEXR_HIP(launch_sym_all_gather(p, symChunkGrid(nBytes, 1, nRanks), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// ---- nexrFlatAllReduce, nexrFlatReduceScatter, nexrFlatReduce -----------------------------------------------
-// The checks the three share, then what the semantics make of the call (as simpleStepsGroup hands them to
-// launch_simple_group: fork changes the dispatch type; shipped folds nothing, and what survives is the first
-// operand of the chain's last step).
-namespace {
-// The rank count, datatype and op that a flat reduction takes.
-nexrResult_t flatOpCheck(int nRanks, int datatype, int devRedOp, uint64_t redOpArg) {
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
-    return nexrInvalidArgument;
-  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    if ((int8_t)divisor == 0) return nexrInvalidArgument;
-  }
-  return nexrSuccess;
-}
-
-// What the semantics make of a checked call: the dispatch and the fields that flat_fold reads (FlatParams' names).
-struct FlatSemantics {
-  int dt, op, nFold, shift, preOp, postOp;
-};
-FlatSemantics flatSemantics(int nRanks, int datatype, int devRedOp, int userFirst) {
-  int srcIsInput = 1, postOp = 1, firstWins = 0;
-  FlatSemantics m;
-  m.dt = datatype;
-  m.op = devRedOp;
-  llSemantics(&m.dt, &m.op, &srcIsInput, &postOp, &firstWins);
-  m.nFold = firstWins ? 1 : nRanks;
-  m.shift = firstWins && userFirst ? nRanks - 1 : 0;
-  m.preOp = srcIsInput;
-  m.postOp = postOp;
-  return m;
-}
-
-nexrResult_t flatPrepare(int nRanks, const void* const* inputs, int datatype, int devRedOp, uint64_t redOpArg,
-                         int userFirst, FlatParams* p, int* dt, int* op) {
-  if (!inputs) return nexrInvalidArgument;
-  const nexrResult_t res = flatOpCheck(nRanks, datatype, devRedOp, redOpArg);
-  if (res != nexrSuccess) return res;
-  const uint64_t esz = typeSize(datatype);
-  memset((void*)p, 0, sizeof(*p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || ((uintptr_t)inputs[r] & (esz - 1))) return nexrInvalidArgument;
-    p->in[r] = (const char*)inputs[r];
-  }
-  const FlatSemantics m = flatSemantics(nRanks, datatype, devRedOp, userFirst);
-  *dt = m.dt;
-  *op = m.op;
-  p->nRanks = nRanks;
-  p->redArg = redOpArg;
-  p->userFirst = userFirst ? 1 : 0;
-  p->nFold = m.nFold;
-  p->shift = m.shift;
-  p->preOp = m.preOp;
-  p->postOp = m.postOp;
-  return nexrSuccess;
-}
-
-// One-shot: a wave per 2048-byte piece of every region, four waves per workgroup; beyond the cap the kernel
-// strides.
-unsigned flatGrid(uint64_t regionBytes, int nRegions, uint64_t maxGrid = 0) {
-  const uint64_t items = (regionBytes + 2047) / 2048 * (uint64_t)nRegions;
-  const uint64_t grid = std::min<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
-  return (unsigned)(maxGrid > 0 && grid > maxGrid ? maxGrid : grid);  // maxGrid: the host forms' cap (hostGrid)
-}
-}  // namespace
-
-// The checks of nexrFlatAllReduce, and the launch's parameters over the pointers as given (no device call).
-namespace {
-nexrResult_t flatAllReduceCheck(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
-                                int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
-                                const nexrFlatPart* parts, int nParts, FlatParams* pp, int* dtp, int* opp) {
-  FlatParams& p = *pp;
-  int& dt = *dtp;
-  int& op = *opp;
-  if (!outputs) return nexrInvalidArgument;
-  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess) return res;
-  const uint64_t esz = typeSize(datatype), epp = 16 / esz;
-  for (int r = 0; r < nRanks; r++) {
-    if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
-    p.out[r] = (char*)outputs[r];
-  }
-  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
-  if (nParts < 0 || (nParts > 0 && !parts)) return nexrInvalidArgument;
-  uint64_t at = 0;
-  for (int k = 0; k < nParts; k++) {  // ascending, gapless, from 0
-    const nexrFlatPart& q = parts[k];
-    if (q.offset != at || q.count == 0 || q.count > (uint64_t)nElts - at) return nexrInvalidArgument;
-    if (q.offset % epp || q.chunkCount == 0 || q.chunkCount % epp) return nexrInvalidArgument;
-    if (q.chunkCount > (uint64_t)-1 / (uint64_t)nRanks) return nexrInvalidArgument;
-    at += q.count;
-  }
-  if (at != (uint64_t)nElts) return nexrInvalidArgument;
-  p.coll = kFlatAllReduce;
-  p.regionBytes = p.winEnd = (uint64_t)nElts * esz;
-  p.nParts = nParts;
-  p.nOut = nRanks;
-  return nexrSuccess;
-}
-
-// A part list too long for a launch's arguments, in a stream-ordered workspace: the parts travel by value in
-// short launches ahead of the one, so nothing is read after return. The caller frees *ws behind its launch.
-nexrResult_t flatPartsWorkspace(const nexrFlatPart* parts, int nParts, hipStream_t s, nexrFlatPart** ws) {
-  NEXR_HIP(hipMallocAsync((void**)ws, (size_t)nParts * sizeof(nexrFlatPart), s));
-  FlatPartsFill f;
-  for (int k = 0; k < nParts; k += kFlatInlineParts) {
-    f.dst = *ws + k;
-    f.n = std::min(kFlatInlineParts, nParts - k);
-    f.pad = 0;
-    memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatPart));
-    const hipError_t e = launch_flat_parts(f, s);
-    if (e != hipSuccess) {
-      (void)hipFreeAsync(*ws, s);
-      *ws = nullptr;
-      return hipFail(e);
-    }
-  }
-  return nexrSuccess;
-}
-
-// One launch of a checked all-reduce over the window that p holds; gridCap > 0 caps the grid.
-nexrResult_t flatAllReduceLaunch(FlatParams& p, int dt, int op, const nexrFlatPart* parts, int nParts,
-                                 uint64_t gridCapWgs, hipStream_t s) {
-  nexrFlatPart* ws = nullptr;
-  if (nParts <= kFlatInlineParts) {
-    memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatPart));
-  } else {
-    const nexrResult_t res = flatPartsWorkspace(parts, nParts, s, &ws);
-    if (res != nexrSuccess) return res;
-    p.ext = ws;
-  }
-  const hipError_t e = launch_flat(dt, op, p, flatGrid(p.winEnd - p.winBeg, 1, gridCapWgs), s);
-  if (ws) (void)hipFreeAsync(ws, s);
-  NEXR_HIP(e);
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
-                                        int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
-                                        const nexrFlatPart* parts, int nParts, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  const nexrResult_t res = flatAllReduceCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
-                                              parts, nParts, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  return flatAllReduceLaunch(p, dt, op, parts, nParts, 0, (hipStream_t)stream);
-}
-
-namespace {
-nexrResult_t flatReduceScatterCheck(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
-                                    int datatype, int devRedOp, uint64_t redOpArg, int userFirst, FlatParams* pp,
-                                    int* dtp, int* opp) {
-  FlatParams& p = *pp;
-  int& dt = *dtp;
-  int& op = *opp;
-  if (!outputs) return nexrInvalidArgument;
-  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess) return res;
-  const uint64_t esz = typeSize(datatype);
-  for (int r = 0; r < nRanks; r++) {
-    if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
-    p.out[r] = (char*)outputs[r];
-  }
-  if (nElts > (size_t)-1 / esz / (size_t)nRanks) return nexrInvalidArgument;  // an input's nRanks * nElts * esz bytes
-  p.coll = kFlatReduceScatter;
-  p.regionBytes = p.winEnd = (uint64_t)nElts * esz;
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
-                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                            int userFirst, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  const nexrResult_t res =
-      flatReduceScatterCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-namespace {
-nexrResult_t flatReduceCheck(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
-                             int datatype, int devRedOp, uint64_t redOpArg, int userFirst, FlatParams* pp, int* dtp,
-                             int* opp) {
-  FlatParams& p = *pp;
-  int& dt = *dtp;
-  int& op = *opp;
-  if (!output) return nexrInvalidArgument;
-  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess) return res;
-  const uint64_t esz = typeSize(datatype);
-  if (root < 0 || root >= nRanks || ((uintptr_t)output & (esz - 1))) return nexrInvalidArgument;
-  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
-  p.out[root] = (char*)output;
-  p.root = root;
-  p.coll = kFlatReduce;
-  p.regionBytes = p.winEnd = (uint64_t)nElts * esz;
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
-                                     int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
-                                     nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  const nexrResult_t res =
-      flatReduceCheck(nRanks, inputs, output, root, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// ---- nexrFlatTreeAllReduce, nexrFlatBroadcast ---------------------------------------------------------------
-namespace {
-// One tree's links as a program (include/nexr.h): from the root, down[0]'s value first, then the rank's own
-// input, then for every further child PUSH, the child, MERGE. `need` is the most values alive at once (the
-// accumulator and the saved ones). False: the links are not one spanning tree with packed children.
-bool flatTreeCompile(const nexrFlatTreeLinks* links, int n, std::vector<uint8_t>* code, int* need, int* root) {
-  int nRoots = 0, slots = 0;
-  *root = -1;
-  for (int r = 0; r < n; r++) {
-    const nexrFlatTreeLinks& l = links[r];
-    if (l.up < -1 || l.up >= n || l.up == r) return false;
-    if (l.up == -1) {
-      nRoots++;
-      *root = r;
-    } else {  // every up matched by its parent's down, once
-      const nexrFlatTreeLinks& p = links[l.up];
-      if ((p.down[0] == r) + (p.down[1] == r) + (p.down[2] == r) != 1) return false;
-    }
-    bool ended = false;
-    for (int k = 0; k < 3; k++) {
-      const int d = l.down[k];
-      if (d < -1 || d >= n) return false;
-      if (d == -1) {
-        ended = true;
-        continue;
-      }
-      if (ended || links[d].up != r) return false;  // packed first; every down matched by its child's up
-      slots++;
-    }
-  }
-  // one parent each and n - 1 child slots, every one its child's up: every rank but the root is some rank's
-  // child exactly once
-  if (nRoots != 1 || slots != n - 1) return false;
-  code->clear();
-  int depth = 0, most = 1;
-  // iterative walk: (rank, next child) frames; a rank has one parent, so what the root reaches is a tree
-  std::vector<std::pair<int, int>> stack{{*root, 0}};
-  int seen = 0;
-  while (!stack.empty()) {
-    const int r = stack.back().first, k = stack.back().second;
-    const nexrFlatTreeLinks& l = links[r];
-    const int nd = l.down[0] < 0 ? 0 : l.down[1] < 0 ? 1 : l.down[2] < 0 ? 2 : 3;
-    if (nd == 0) {
-      code->push_back((uint8_t)(kFlatTreeLeaf << 6 | r));
-      seen++;
-      stack.pop_back();
-      continue;
-    }
-    if (k == 1) {  // behind down[0]
-      code->push_back((uint8_t)(kFlatTreeJoin << 6 | r));
-      seen++;
-    } else if (k > 1) {  // behind a further child
-      code->push_back((uint8_t)(kFlatTreeMerge << 6));
-      depth--;
-    }
-    if (k == nd) {
-      stack.pop_back();
-      continue;
-    }
-    if (k >= 1) {
-      code->push_back((uint8_t)(kFlatTreePush << 6));
-      depth++;
-      most = std::max(most, depth + 1);
-    }
-    stack.back().second = k + 1;
-    stack.push_back({l.down[k], 0});
-  }
-  if (seen != n) return false;  // ranks the root does not reach: a cycle among them
-  *need = most;
-  return true;
-}
-}  // namespace
-
-namespace {
-nexrResult_t flatTreeCheck(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts, int datatype,
-                           int devRedOp, uint64_t redOpArg, int userFirst, const nexrFlatTreeLinks* const* trees,
-                           int nTrees, const nexrFlatTreePart* parts, int nParts, FlatTreeParams* pp, int* dtp,
-                           int* opp) {
-  FlatTreeParams& p = *pp;
-  int& dt = *dtp;
-  int& op = *opp;
-  FlatParams fp;  // the shared checks and what the semantics make of the call
-  if (!outputs) return nexrInvalidArgument;
-  nexrResult_t res = flatPrepare(nRanks, inputs, datatype, devRedOp, redOpArg, userFirst, &fp, &dt, &op);
-  if (res != nexrSuccess) return res;
-  const uint64_t esz = typeSize(datatype), epp = 16 / esz;
-  memset((void*)&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!outputs[r] || ((uintptr_t)outputs[r] & (esz - 1))) return nexrInvalidArgument;
-    p.in[r] = fp.in[r];
-    p.out[r] = (char*)outputs[r];
-  }
-  if (nElts > (size_t)-1 / esz) return nexrInvalidArgument;
-  if (!trees || nTrees < 1 || nTrees > 2) return nexrInvalidArgument;
-  if (nParts < 0 || (nParts > 0 && !parts)) return nexrInvalidArgument;
-  const bool firstWins = fp.nFold == 1;
-  for (int t = 0; t < nTrees; t++) {
-    if (!trees[t]) return nexrInvalidArgument;
-    std::vector<uint8_t> code;
-    int need = 0, root = -1;
-    if (!flatTreeCompile(trees[t], nRanks, &code, &need, &root)) return nexrInvalidArgument;
-    if (need > kFlatTreeSlots || code.size() > (size_t)kFlatTreeProgBytes) return nexrInvalidArgument;
-    if (firstWins) {  // every reduce returns its first operand: one rank's input survives
-      int r = root;
-      if (!userFirst)
-        while (trees[t][r].down[0] >= 0) {  // the peer is first, the last child's last
-          const nexrFlatTreeLinks& l = trees[t][r];
-          r = l.down[2] >= 0 ? l.down[2] : l.down[1] >= 0 ? l.down[1] : l.down[0];
-        }
-      code.assign(1, (uint8_t)(kFlatTreeLeaf << 6 | r));
-    }
-    uint8_t order[NEXR_SYM_MAX_RANKS] = {0};
-    int nIn = 0;
-    for (uint8_t ins : code)
-      if ((ins >> 6) <= kFlatTreeJoin) order[nIn++] = ins & 63;
-    FlatTreeProgram& g = p.prog[t];
-    memcpy(g.code, code.data(), code.size());
-    memcpy(g.order, order, sizeof(order));
-    g.nCode = (int)code.size();
-    g.nIn = nIn;
-  }
-  uint64_t at = 0;
-  for (int k = 0; k < nParts; k++) {  // ascending, gapless, from 0
-    const nexrFlatTreePart& q = parts[k];
-    if (q.offset != at || q.count == 0 || q.count > (uint64_t)nElts - at) return nexrInvalidArgument;
-    if (q.offset % epp || q.tree >= (uint32_t)nTrees) return nexrInvalidArgument;
-    at += q.count;
-  }
-  if (at != (uint64_t)nElts) return nexrInvalidArgument;
-  p.nBytes = p.winEnd = (uint64_t)nElts * esz;
-  p.redArg = fp.redArg;
-  p.nRanks = p.nOut = nRanks;
-  p.userFirst = fp.userFirst;
-  p.preOp = fp.preOp;
-  p.postOp = fp.postOp;
-  p.nParts = nParts;
-  return nexrSuccess;
-}
-
-// flatPartsWorkspace for a tree's parts.
-nexrResult_t flatTreePartsWorkspace(const nexrFlatTreePart* parts, int nParts, hipStream_t s, nexrFlatTreePart** ws) {
-  NEXR_HIP(hipMallocAsync((void**)ws, (size_t)nParts * sizeof(nexrFlatTreePart), s));
-  FlatTreePartsFill f;
-  for (int k = 0; k < nParts; k += kFlatTreeInlineParts) {
-    f.dst = *ws + k;
-    f.n = std::min(kFlatTreeInlineParts, nParts - k);
-    f.pad = 0;
-    memcpy(f.parts, parts + k, (size_t)f.n * sizeof(nexrFlatTreePart));
-    const hipError_t e = launch_flat_tree_parts(f, s);
-    if (e != hipSuccess) {
-      (void)hipFreeAsync(*ws, s);
-      *ws = nullptr;
-      return hipFail(e);
-    }
-  }
-  return nexrSuccess;
-}
-
-// One launch of a checked tree all-reduce over the window that p holds; gridCapWgs > 0 caps the grid.
-nexrResult_t flatTreeLaunch(FlatTreeParams& p, int dt, int op, const nexrFlatTreePart* parts, int nParts,
-                            uint64_t gridCapWgs, hipStream_t s) {
-  nexrFlatTreePart* ws = nullptr;
-  if (nParts <= kFlatTreeInlineParts) {
-    memcpy(p.parts, parts, (size_t)nParts * sizeof(nexrFlatTreePart));
-  } else {
-    const nexrResult_t res = flatTreePartsWorkspace(parts, nParts, s, &ws);
-    if (res != nexrSuccess) return res;
-    p.ext = ws;
-  }
-  const hipError_t e = launch_flat_tree(dt, op, p, flatGrid(p.winEnd - p.winBeg, 1, gridCapWgs), s);
-  if (ws) (void)hipFreeAsync(ws, s);
-  NEXR_HIP(e);
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
-                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                            int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
-                                            const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
-  FlatTreeParams p;
-  int dt, op;
-  const nexrResult_t res = flatTreeCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
-                                         trees, nTrees, parts, nParts, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  return flatTreeLaunch(p, dt, op, parts, nParts, 0, (hipStream_t)stream);
-}
-
-// ---- nexrFlat*PreMul: PreMulSum with a scalar per rank --------------------------------------------------------
-// The plain entry's checks run with nexrDevPreMulSum and make the plain launch's parameters; the scalars are
-// checked; then the fields move into the per-rank kernels' block. Under nexrSemanticsShipped the checks turn the
-// op into a bit copy without a pre-op: that is the plain kernel's launch, and no scalar is read.
-namespace {
-nexrResult_t flatScalarsCheck(int nRanks, const uint64_t* scalars, int arePtrs, int datatype) {
-  if (!scalars) return nexrInvalidArgument;
-  const uint64_t esz = typeSize(datatype);
-  for (int r = 0; arePtrs && r < nRanks; r++)
-    if (!scalars[r] || (scalars[r] & (esz - 1))) return nexrInvalidArgument;
-  return nexrSuccess;
-}
-
-void flatPreMulFrom(const FlatParams& p, const uint64_t* scalars, int arePtrs, FlatPreMulParams* q) {
-  memset((void*)q, 0, sizeof(*q));
-  memcpy(q->in, p.in, sizeof(q->in));
-  memcpy(q->out, p.out, sizeof(q->out));
-  memcpy(q->scalars, scalars, (size_t)p.nRanks * sizeof(uint64_t));
-  q->regionBytes = p.regionBytes;
-  q->winBeg = p.winBeg;
-  q->winEnd = p.winEnd;
-  q->coll = p.coll;
-  q->nRanks = p.nRanks;
-  q->nFold = p.nFold;
-  q->shift = p.shift;
-  q->userFirst = p.userFirst;
-  q->preOp = p.preOp;
-  q->postOp = p.postOp;
-  q->root = p.root;
-  q->nParts = p.nParts;
-  q->nOut = p.nOut;
-  q->scalarsArePtrs = arePtrs ? 1 : 0;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatAllReducePreMul(int nRanks, const void* const* inputs, void* const* outputs,
-                                              size_t nElts, int datatype, const uint64_t* scalars,
-                                              int scalarsArePtrs, int userFirst, const nexrFlatPart* parts,
-                                              int nParts, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  nexrResult_t res = flatAllReduceCheck(nRanks, inputs, outputs, nElts, datatype, nexrDevPreMulSum, 0, userFirst, parts,
-                                        nParts, &p, &dt, &op);
-  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
-  if (res != nexrSuccess || nElts == 0) return res;
-  hipStream_t s = (hipStream_t)stream;
-  if (op != nexrDevPreMulSum) return flatAllReduceLaunch(p, dt, op, parts, nParts, 0, s);
-  FlatPreMulParams q;
-  flatPreMulFrom(p, scalars, scalarsArePtrs, &q);
-  nexrFlatPart* ws = nullptr;
-  if (nParts <= kFlatPreMulInlineParts) {
-    memcpy(q.parts, parts, (size_t)nParts * sizeof(nexrFlatPart));
-  } else {
-    res = flatPartsWorkspace(parts, nParts, s, &ws);
-    if (res != nexrSuccess) return res;
-    q.ext = ws;
-  }
-  const hipError_t e = launch_flat_premul(dt, q, flatGrid(q.regionBytes, 1), s);
-  if (ws) (void)hipFreeAsync(ws, s);
-  NEXR_HIP(e);
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrFlatReduceScatterPreMul(int nRanks, const void* const* inputs, void* const* outputs,
-                                                  size_t nElts, int datatype, const uint64_t* scalars,
-                                                  int scalarsArePtrs, int userFirst, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  nexrResult_t res = flatReduceScatterCheck(nRanks, inputs, outputs, nElts, datatype, nexrDevPreMulSum, 0, userFirst,
-                                            &p, &dt, &op);
-  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
-  if (res != nexrSuccess || nElts == 0) return res;
-  if (op != nexrDevPreMulSum) {
-    NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks), (hipStream_t)stream));
-    return nexrSuccess;
-  }
-  FlatPreMulParams q;
-  flatPreMulFrom(p, scalars, scalarsArePtrs, &q);
-  NEXR_HIP(launch_flat_premul(dt, q, flatGrid(q.regionBytes, nRanks), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrFlatReducePreMul(int nRanks, const void* const* inputs, void* output, int root,
-                                           size_t nElts, int datatype, const uint64_t* scalars, int scalarsArePtrs,
-                                           int userFirst, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  nexrResult_t res = flatReduceCheck(nRanks, inputs, output, root, nElts, datatype, nexrDevPreMulSum, 0, userFirst, &p,
-                                     &dt, &op);
-  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
-  if (res != nexrSuccess || nElts == 0) return res;
-  if (op != nexrDevPreMulSum) {
-    NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, 1), (hipStream_t)stream));
-    return nexrSuccess;
-  }
-  FlatPreMulParams q;
-  flatPreMulFrom(p, scalars, scalarsArePtrs, &q);
-  NEXR_HIP(launch_flat_premul(dt, q, flatGrid(q.regionBytes, 1), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrFlatTreeAllReducePreMul(int nRanks, const void* const* inputs, void* const* outputs,
-                                                  size_t nElts, int datatype, const uint64_t* scalars,
-                                                  int scalarsArePtrs, int userFirst,
-                                                  const nexrFlatTreeLinks* const* trees, int nTrees,
-                                                  const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
-  FlatTreeParams p;
-  int dt, op;
-  nexrResult_t res = flatTreeCheck(nRanks, inputs, outputs, nElts, datatype, nexrDevPreMulSum, 0, userFirst, trees,
-                                   nTrees, parts, nParts, &p, &dt, &op);
-  if (res == nexrSuccess) res = flatScalarsCheck(nRanks, scalars, scalarsArePtrs, datatype);
-  if (res != nexrSuccess || nElts == 0) return res;
-  hipStream_t s = (hipStream_t)stream;
-  if (op != nexrDevPreMulSum) return flatTreeLaunch(p, dt, op, parts, nParts, 0, s);
-  FlatTreePreMulParams q;
-  memset((void*)&q, 0, sizeof(q));
-  memcpy(q.in, p.in, sizeof(q.in));
-  memcpy(q.out, p.out, sizeof(q.out));
-  memcpy(q.scalars, scalars, (size_t)nRanks * sizeof(uint64_t));
-  q.nBytes = p.nBytes;
-  q.winBeg = p.winBeg;
-  q.winEnd = p.winEnd;
-  q.nRanks = p.nRanks;
-  q.userFirst = p.userFirst;
-  q.preOp = p.preOp;
-  q.postOp = p.postOp;
-  q.nParts = p.nParts;
-  q.nOut = p.nOut;
-  q.scalarsArePtrs = scalarsArePtrs ? 1 : 0;
-  q.prog[0] = p.prog[0];
-  q.prog[1] = p.prog[1];
-  nexrFlatTreePart* ws = nullptr;
-  if (nParts <= kFlatTreePreMulInlineParts) {
-    memcpy(q.parts, parts, (size_t)nParts * sizeof(nexrFlatTreePart));
-  } else {
-    res = flatTreePartsWorkspace(parts, nParts, s, &ws);
-    if (res != nexrSuccess) return res;
-    q.ext = ws;
-  }
-  const hipError_t e = launch_flat_tree_premul(dt, q, flatGrid(q.nBytes, 1), s);
-  if (ws) (void)hipFreeAsync(ws, s);
-  NEXR_HIP(e);
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrFlatBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
-                                        nexrStream_t stream) {
-  if (!input || !outputs) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  FlatBcastParams p;
-  memset((void*)&p, 0, sizeof(p));
-  bool any = false;
-  for (int r = 0; r < nRanks; r++) {
-    if (!outputs[r]) return nexrInvalidArgument;
-    if (outputs[r] != input) {
-      p.out[r] = (char*)outputs[r];
-      any = true;
-    }
-  }
-  if (nBytes == 0 || !any) return nexrSuccess;
-  p.in = (const char*)input;
-  p.nBytes = p.winEnd = nBytes;
-  p.nRanks = nRanks;
-  NEXR_HIP(launch_flat_bcast(p, flatGrid(nBytes, 1), (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// ---- nexrFlatAllToAll -------------------------------------------------------------------------------------------
-namespace {
-// The grid of the exchanges below: a wave per item, four waves per workgroup, at least `least` (0 or 1) and at most
-// `cap` workgroups, then maxWorkgroups where it is set. Beyond the grid the waves stride.
-unsigned waveGrid(uint64_t items, uint64_t cap, uint64_t least, int maxWorkgroups) {
-  uint64_t grid = std::min<uint64_t>(std::max<uint64_t>((items + kBlock / 64 - 1) / (kBlock / 64), least), cap);
-  if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
-  return (unsigned)grid;
-}
-}  // namespace
-
-// Every check before any device call; the ranges are half-open, as nexrFlatGroupPlan compares them. The host
-// picks the instance: packs where no pack can straddle two blocks (nBytes % 16 == 0), bytes otherwise.
-NEXR_API nexrResult_t nexrFlatAllToAll(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
-                                       int maxWorkgroups, nexrStream_t stream) {
-  if (!inputs || !outputs || maxWorkgroups < 0) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (nBytes > (size_t)-1 / (size_t)nRanks) return nexrInvalidArgument;  // a buffer's nRanks * nBytes bytes
-  const uintptr_t row = (uintptr_t)nRanks * nBytes;
-  FlatAllToAllParams p;
-  memset((void*)&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-  }
-  if (!nexr_exchange_v::fixedRangesOk(nRanks, inputs, outputs, row, row, true)) return nexrInvalidArgument;
-  if (nBytes == 0) return nexrSuccess;
-  const bool bytes = (nBytes & 15u) != 0;
-  p.blockBytes = nBytes;
-  p.nRanks = nRanks;
-  p.piecesPer = ((bytes ? (uint64_t)nBytes : (uint64_t)row) + 2047) / 2048;
-  p.nItems = p.piecesPer * (uint64_t)nRanks * (bytes ? (uint64_t)nRanks : 1);
-  const unsigned grid = waveGrid(p.nItems, gridCap(kBlock), 0, maxWorkgroups);
-  NEXR_HIP(launch_flat_alltoall(p, bytes, grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// ---- nexrFlatAllToAll2D, nexrFlatAllGather2D ----------------------------------------------------------------------
-namespace {
-// Every check before any device call, then the launch. A side's two strides follow from its layout; the gather is
-// the exchange whose source has no block stride and the input's own row pitch, written rows out. The host picks the
-// access width so that no unit can straddle two block rows.
-nexrResult_t flatPitched(int nRanks, const void* const* inputs, void* const* outputs, size_t rows, size_t nBytes,
-                         int inLayout, int outLayout, bool gather, int maxWorkgroups, nexrStream_t stream) {
-  if (!inputs || !outputs || maxWorkgroups < 0) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if ((inLayout != nexrLayoutBlocks && inLayout != nexrLayoutRows) ||
-      (outLayout != nexrLayoutBlocks && outLayout != nexrLayoutRows))
-    return nexrInvalidArgument;
-  if (rows > (size_t)0x7fffffff) return nexrInvalidArgument;
-  const size_t n = (size_t)nRanks;
-  if (rows && nBytes > (size_t)-1 / n / rows) return nexrInvalidArgument;  // a buffer's n * rows * nBytes bytes
-  const uintptr_t outLen = (uintptr_t)(n * rows * nBytes), inLen = gather ? (uintptr_t)(rows * nBytes) : outLen;
-  FlatPitchedParams p;
-  memset((void*)&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-  }
-  if (!nexr_exchange_v::fixedRangesOk(nRanks, inputs, outputs, inLen, outLen, true)) return nexrInvalidArgument;
-  if (outLen == 0) return nexrSuccess;
-  if (!gather && (rows == 1 || (inLayout == nexrLayoutBlocks && outLayout == nexrLayoutBlocks)))
-    return nexrFlatAllToAll(nRanks, inputs, outputs, rows * nBytes, maxWorkgroups, stream);
-  const uint64_t B = nBytes;
-  const int width = (B & 15u) == 0 ? 16 : (B & 3u) == 0 ? 4 : 1;
-  p.runBytes = B;
-  p.inBlock = gather ? 0 : inLayout == nexrLayoutBlocks ? (uint64_t)rows * B : B;
-  p.inPitch = gather || inLayout == nexrLayoutBlocks ? B : (uint64_t)n * B;
-  p.outBlock = outLayout == nexrLayoutBlocks ? (uint64_t)rows * B : B;
-  p.outPitch = outLayout == nexrLayoutBlocks ? B : (uint64_t)n * B;
-  p.inner = outLayout == nexrLayoutBlocks ? (uint32_t)rows : (uint32_t)n;
-  p.outBytes = outLen;
-  p.nRuns = (uint64_t)n * rows;
-  p.nRanks = nRanks;
-  const uint64_t piece = (uint64_t)128 * (uint64_t)width;
-  p.piecesPer = p.outBytes / piece + (p.outBytes % piece ? 1 : 0);
-  p.nItems = p.piecesPer * (uint64_t)n;
-  const unsigned grid = waveGrid(p.nItems, gridCap(kBlock), 0, maxWorkgroups);
-  NEXR_HIP(launch_flat_pitched(p, width, grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatAllToAll2D(int nRanks, const void* const* inputs, void* const* outputs, size_t rows,
-                                         size_t nBytes, int inLayout, int outLayout, int maxWorkgroups,
-                                         nexrStream_t stream) {
-  return flatPitched(nRanks, inputs, outputs, rows, nBytes, inLayout, outLayout, false, maxWorkgroups, stream);
-}
-
-NEXR_API nexrResult_t nexrFlatAllGather2D(int nRanks, const void* const* inputs, void* const* outputs, size_t rows,
-                                          size_t nBytes, int maxWorkgroups, nexrStream_t stream) {
-  return flatPitched(nRanks, inputs, outputs, rows, nBytes, nexrLayoutRows, nexrLayoutRows, true, maxWorkgroups,
-                     stream);
-}
-
-// ---- nexrFlatAllToAllv ------------------------------------------------------------------------------------------
-namespace {
-// Workgroups of flat_exchange_v_kernel the current device keeps resident, the default cap of its grid: per CU eight
-// (what the kernel's registers admit at 256 threads), or as many as find their 16 * n * n bytes of LDS in a CU's
-// 160 KiB where that is fewer (36 ranks and more: two at 64). 2,048 on the 256 CUs of an MI355X up to 35 ranks, which
-// is what DESIGN 8.13 measured; nothing above 16 ranks has been measured.
-// n == 0: a kernel without LDS (nexr_flat_scatter_v.hip), eight per CU at any rank count.
-nexrResult_t flatExchangeVResident(int n, uint64_t* resident) {
-  constexpr int kDevs = 16;
-  static std::atomic<int> cusOf[kDevs];
-  int dev = 0;
-  NEXR_HIP(hipGetDevice(&dev));
-  const bool cached = dev >= 0 && dev < kDevs;
-  int cus = cached ? cusOf[dev].load(std::memory_order_relaxed) : 0;
-  if (cus <= 0) {
-    NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (cached && cus > 0) cusOf[dev].store(cus, std::memory_order_relaxed);
-  }
-  const uint64_t perCu = n ? std::min<uint64_t>(8, (uint64_t)(160 << 10) / ((uint64_t)16 * n * n)) : 8;
-  *resident = std::max<uint64_t>(perCu * (uint64_t)std::max(cus, 1), 1);
-  return nexrSuccess;
-}
-
-// The grid of the counted launches: waveGrid up to the workgroups the device keeps resident (ldsRanks: what
-// flatExchangeVResident takes), so that a workgroup's prologue serves many pieces and not four. Device counts with
-// no capacity at all still launch one workgroup: the verdict is the kernel's.
-nexrResult_t flatCountedGrid(int ldsRanks, uint64_t items, int maxWorkgroups, unsigned* grid) {
-  uint64_t resident = 0;
-  const nexrResult_t res = flatExchangeVResident(ldsRanks, &resident);
-  if (res != nexrSuccess) return res;
-  *grid = waveGrid(items, resident, 1, maxWorkgroups);
-  return nexrSuccess;
-}
-
-// What the counted entries share once the rank count and the element size are checked: the arrays, the residence,
-// device counts' alignment and status word, the capacities and ranges (countWords counts), and the fields that
-// FlatExchangeVParams and FlatScatterVParams have in common.
-extern "C++" template <typename Params>
-nexrResult_t flatCountedPrelude(int n, const void* const* inputs, void* const* outputs, const uint64_t* counts,
-                                int residence, size_t esz, const size_t* inElts, const size_t* outElts,
-                                uint32_t* status, int maxWorkgroups, size_t countWords, Params* p) {
-  if (!inputs || !outputs || !counts || !inElts || !outElts || maxWorkgroups < 0) return nexrInvalidArgument;
-  if (residence != nexrScalarDevice && residence != nexrScalarHostImmediate) return nexrInvalidArgument;
-  const bool dev = residence == nexrScalarDevice;
-  if (dev && (!status || ((uintptr_t)counts & 7u))) return nexrInvalidArgument;
-  if (!nexr_exchange_v::buffersOk(n, inputs, outputs, inElts, outElts, esz, counts, status, dev, countWords))
-    return nexrInvalidArgument;
-  for (int r = 0; r < n; r++) {
-    p->in[r] = (const char*)inputs[r];
-    p->out[r] = (char*)outputs[r];
-    p->inElts[r] = inElts[r];
-    p->outElts[r] = outElts[r];
-  }
-  p->status = status;
-  p->nRanks = n;
-  return nexrSuccess;
-}
-
-int eszShift(size_t esz) { return esz == 1 ? 0 : esz == 2 ? 1 : esz == 4 ? 2 : 3; }
-}  // namespace
-
-// Every check before any device call. Host counts are summed here and size the grid exactly; device counts are
-// never read here, and the grid comes from the capacities (the kernel derives the true item count itself).
-NEXR_API nexrResult_t nexrFlatAllToAllv(int nRanks, const void* const* inputs, void* const* outputs,
-                                        const uint64_t* counts, int residence, size_t esz, const size_t* inElts,
-                                        const size_t* outElts, uint32_t* status, int maxWorkgroups,
-                                        nexrStream_t stream) {
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return nexrInvalidArgument;
-  const int n = nRanks;
-  const bool dev = residence == nexrScalarDevice;
-  FlatExchangeVParams p;
-  memset((void*)&p, 0, sizeof(p));
-  nexrResult_t res = flatCountedPrelude(n, inputs, outputs, counts, residence, esz, inElts, outElts, status,
-                                        maxWorkgroups, (size_t)n * n, &p);
-  if (res != nexrSuccess) return res;
-  uint64_t items = 0;
-  if (dev) {
-    for (int d = 0; d < n; d++) items += ((uint64_t)outElts[d] * esz + 2047) / 2048;
-  } else {
-    uint64_t col[NEXR_SYM_MAX_RANKS];
-    if (!nexr_exchange_v::countsFit(n, counts, inElts, outElts, col)) return nexrInvalidArgument;
-    for (int d = 0; d < n; d++) items += (col[d] * esz + 2047) / 2048;
-    if (items == 0) return nexrSuccess;
-  }
-  p.shift = eszShift(esz);
-  unsigned grid = 0;
-  res = flatCountedGrid(n, items, maxWorkgroups, &grid);
-  if (res != nexrSuccess) return res;
-  hipStream_t s = (hipStream_t)stream;
-  uint64_t* ws = nullptr;
-  const int words = n * n;
-  if (dev) {
-    p.ext = counts;
-  } else if (n <= kFlatExchangeVInlineRanks) {
-    memcpy(p.inl, counts, (size_t)words * 8);
-  } else {  // by value in short launches ahead of the one, as nexrFlatGroup's table: nothing is read after return
-    NEXR_HIP(hipMallocAsync((void**)&ws, (size_t)words * 8, s));
-    FlatGroupFill f;
-    for (int at = 0; at < words; at += kFlatGroupFillWords) {
-      f.dst = ws + at;
-      f.n = std::min(kFlatGroupFillWords, words - at);
-      f.pad = 0;
-      memcpy(f.words, counts + at, (size_t)f.n * 8);
-      const hipError_t e = launch_flat_group_fill(f, s);
-      if (e != hipSuccess) {
-        (void)hipFreeAsync(ws, s);
-        return hipFail(e);
-      }
-    }
-    p.ext = ws;
-  }
-  const hipError_t e = launch_flat_exchange_v(p, grid, s);
-  if (ws) (void)hipFreeAsync(ws, s);
-  NEXR_HIP(e);
-  return nexrSuccess;
-}
-
-// ---- nexrFlatReduceScatterv, nexrFlatAllGatherv -----------------------------------------------------------------
-namespace {
-// The checks the two share with nexrFlatAllToAllv (arrays, residence, capacities, ranges), the host counts' fit,
-// and the launch's parameters but for what the reduction adds. *items: the 2048-byte pieces that size the grid,
-// exact under host counts (0: nothing to do), those of the capacities under device counts.
-nexrResult_t flatScatterVCheck(int n, const void* const* inputs, void* const* outputs, const uint64_t* counts,
-                               int residence, size_t esz, const size_t* inElts, const size_t* outElts,
-                               uint32_t* status, int maxWorkgroups, bool scatter, FlatScatterVParams* pp,
-                               uint64_t* items) {
-  FlatScatterVParams& p = *pp;
-  const nexrResult_t res = flatCountedPrelude(n, inputs, outputs, counts, residence, esz, inElts, outElts, status,
-                                              maxWorkgroups, (size_t)n, pp);
-  if (res != nexrSuccess) return res;
-  const size_t* own = scatter ? outElts : inElts;  // the capacities of the buffers that hold one piece
-  *items = 0;
-  if (residence == nexrScalarDevice) {
-    for (int d = 0; d < n; d++) *items += ((uint64_t)own[d] * esz + 2047) / 2048;
-    p.ext = counts;
-  } else {
-    uint64_t total = 0;
-    if (!nexr_exchange_v::piecesFit(n, counts, inElts, outElts, scatter, &total)) return nexrInvalidArgument;
-    for (int d = 0; d < n; d++) *items += (counts[d] * esz + 2047) / 2048;
-    memcpy(p.counts, counts, (size_t)n * 8);
-  }
-  p.eszShift = eszShift(esz);
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatReduceScatterv(int nRanks, const void* const* inputs, void* const* outputs,
-                                             const uint64_t* counts, int residence, int datatype, int devRedOp,
-                                             uint64_t redOpArg, int userFirst, const size_t* inElts,
-                                             const size_t* outElts, uint32_t* status, int maxWorkgroups,
-                                             nexrStream_t stream) {
-  nexrResult_t res = flatOpCheck(nRanks, datatype, devRedOp, redOpArg);
-  if (res != nexrSuccess) return res;
-  const size_t esz = typeSize(datatype);
-  FlatScatterVParams p;
-  memset((void*)&p, 0, sizeof(p));
-  uint64_t items = 0;
-  res = flatScatterVCheck(nRanks, inputs, outputs, counts, residence, esz, inElts, outElts, status, maxWorkgroups,
-                          true, &p, &items);
-  if (res != nexrSuccess) return res;
-  for (int r = 0; r < nRanks; r++)
-    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
-  if (residence == nexrScalarHostImmediate && items == 0) return nexrSuccess;
-  const FlatSemantics m = flatSemantics(nRanks, datatype, devRedOp, userFirst);
-  p.redArg = redOpArg;
-  p.userFirst = userFirst ? 1 : 0;
-  p.nFold = m.nFold;
-  p.shift = m.shift;
-  p.preOp = m.preOp;
-  p.postOp = m.postOp;
-  unsigned grid = 0;
-  res = flatCountedGrid(0, items, maxWorkgroups, &grid);
-  if (res != nexrSuccess) return res;
-  NEXR_HIP(launch_flat_scatter_v(m.dt, m.op, p, grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrFlatAllGatherv(int nRanks, const void* const* inputs, void* const* outputs,
-                                         const uint64_t* counts, int residence, size_t esz, const size_t* inElts,
-                                         const size_t* outElts, uint32_t* status, int maxWorkgroups,
-                                         nexrStream_t stream) {
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (esz != 1 && esz != 2 && esz != 4 && esz != 8) return nexrInvalidArgument;
-  FlatScatterVParams p;
-  memset((void*)&p, 0, sizeof(p));
-  uint64_t items = 0;
-  nexrResult_t res = flatScatterVCheck(nRanks, inputs, outputs, counts, residence, esz, inElts, outElts, status,
-                                       maxWorkgroups, false, &p, &items);
-  if (res != nexrSuccess) return res;
-  if (residence == nexrScalarHostImmediate && items == 0) return nexrSuccess;
-  unsigned grid = 0;
-  res = flatCountedGrid(0, items, maxWorkgroups, &grid);
-  if (res != nexrSuccess) return res;
-  NEXR_HIP(launch_flat_gather_v(p, grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// ---- nexrFlatGroup, nexrFlatGroupPlan: several flat collectives as group launches -----------------------------
-// The plan (no device call): every work through its single entry's checks, then the walk of include/nexr.h: one
-// open launch per key, a conflict with a work of any open launch closes them all. Launches are queued in the
-// order they were opened, at a cut and at the end alike, so a launch's number is its place in `launches`.
-namespace {
-struct GroupRange {
-  uintptr_t beg, end;
-};
-struct GroupWork {  // a checked work with nElts > 0
-  int index;        // in works[]
-  int coll, key;
-  int dt, op;       // the dispatch, after the semantics
-  int root, isMin;
-  int nFold, shift, preOp, postOp;
-  uint64_t regionBytes, redArg, items;
-  std::vector<GroupRange> rd, wr;
-};
-struct GroupLaunch {
-  int key;
-  std::vector<int> members;  // indices into the GroupWork list, in call order
-  int maxOut = 0;            // copies: the longest destination list
-  uint64_t nParts = 0, items = 0, tableBytes = 0;
-  unsigned grid = 0;
-  int fills = 0;
-};
-constexpr int kGroupCopyKey = -1;
-
-bool groupHit(const std::vector<GroupRange>& a, const std::vector<GroupRange>& b) {
-  for (const GroupRange& x : a)
-    for (const GroupRange& y : b)
-      if (x.beg < y.end && y.beg < x.end) return true;
-  return false;
-}
-bool groupConflict(const GroupWork& a, const GroupWork& b) {
-  return groupHit(a.wr, b.rd) || groupHit(a.wr, b.wr) || groupHit(b.wr, a.rd);
-}
-
-nexrResult_t groupPlan(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst, int maxWorkgroups,
-                       int* launchOf, nexrFlatGroupInfo* info, std::vector<GroupWork>* gwp,
-                       std::vector<GroupLaunch>* lp) {
-  std::vector<GroupWork>& gw = *gwp;
-  std::vector<GroupLaunch>& launches = *lp;
-  if (!works || nWorks < 0 || maxWorkgroups < 0) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  std::vector<int> placed((size_t)nWorks, -1);  // work -> its GroupWork
-  FlatParams p;
-  for (int i = 0; i < nWorks; i++) {
-    const nexrFlatGroupWork& w = works[i];
-    GroupWork g;
-    g.index = i;
-    g.coll = w.coll;
-    g.root = 0;
-    g.isMin = 0;
-    g.dt = g.op = 0;
-    g.nFold = g.shift = g.preOp = g.postOp = 0;
-    g.redArg = w.redOpArg;
-    nexrResult_t res = nexrSuccess;
-    if (w.coll == NEXR_FLAT_GROUP_COPY) {
-      if (!w.inputs || !w.inputs[0] || !w.outputs) return nexrInvalidArgument;
-      if (w.nOutputs < 1 || w.nOutputs > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-      for (int r = 0; r < w.nOutputs; r++)
-        if (!w.outputs[r]) return nexrInvalidArgument;
-      g.key = kGroupCopyKey;
-      g.regionBytes = w.nElts;
-      g.items = ((uint64_t)w.nElts + 2047) / 2048;
-      if (w.nElts) {
-        const uintptr_t src = (uintptr_t)w.inputs[0];
-        g.rd.push_back({src, src + w.nElts});
-        for (int r = 0; r < w.nOutputs; r++)
-          if ((uintptr_t)w.outputs[r] != src) g.wr.push_back({(uintptr_t)w.outputs[r], (uintptr_t)w.outputs[r] + w.nElts});
-      }
-    } else {
-      if (w.coll == NEXR_FLAT_GROUP_ALL_REDUCE) {
-        res = flatAllReduceCheck(nRanks, w.inputs, w.outputs, w.nElts, w.datatype, w.devRedOp, w.redOpArg, userFirst,
-                                 w.parts, w.nParts, &p, &g.dt, &g.op);
-      } else if (w.coll == NEXR_FLAT_GROUP_REDUCE_SCATTER) {
-        res = flatReduceScatterCheck(nRanks, w.inputs, w.outputs, w.nElts, w.datatype, w.devRedOp, w.redOpArg,
-                                     userFirst, &p, &g.dt, &g.op);
-      } else if (w.coll == NEXR_FLAT_GROUP_REDUCE) {
-        if (!w.outputs || w.root < 0 || w.root >= nRanks) return nexrInvalidArgument;
-        res = flatReduceCheck(nRanks, w.inputs, w.outputs[w.root], w.root, w.nElts, w.datatype, w.devRedOp,
-                              w.redOpArg, userFirst, &p, &g.dt, &g.op);
-      } else {
-        return nexrInvalidArgument;
-      }
-      if (res != nexrSuccess) return res;
-      const bool minMax = w.devRedOp == nexrDevMinMax;
-      g.isMin = minMax && (w.redOpArg & 1) == 0;
-      g.key = w.datatype << 8 | w.devRedOp << 1 | (minMax ? (int)(w.redOpArg & 1) : 0);
-      g.root = p.root;
-      g.nFold = p.nFold;
-      g.shift = p.shift;
-      g.preOp = p.preOp;
-      g.postOp = p.postOp;
-      g.regionBytes = p.regionBytes;
-      const int nRegions = w.coll == NEXR_FLAT_GROUP_REDUCE_SCATTER ? nRanks : 1;
-      g.items = (p.regionBytes + 2047) / 2048 * (uint64_t)nRegions;
-      const uint64_t inBytes = p.regionBytes * (uint64_t)nRegions;
-      for (int r = 0; r < nRanks && w.nElts; r++) {
-        g.rd.push_back({(uintptr_t)w.inputs[r], (uintptr_t)w.inputs[r] + inBytes});
-        if (w.coll != NEXR_FLAT_GROUP_REDUCE || r == w.root)
-          g.wr.push_back({(uintptr_t)w.outputs[r], (uintptr_t)w.outputs[r] + p.regionBytes});
-      }
-    }
-    if (w.nElts == 0 || g.wr.empty()) continue;  // nothing to do: no launch, launchOf -1
-    placed[i] = (int)gw.size();
-    gw.push_back(std::move(g));
-  }
-
-  std::vector<int> open;         // open launches, in the order they were opened
-  int cuts = 0;
-  std::vector<int> launchOfGw(gw.size(), -1);
-  for (size_t k = 0; k < gw.size(); k++) {
-    bool cut = false;
-    for (size_t o = 0; o < open.size() && !cut; o++)
-      for (int m : launches[open[o]].members)
-        if (groupConflict(gw[m], gw[k])) {
-          cut = true;
-          break;
-        }
-    if (cut) {
-      open.clear();
-      cuts++;
-    }
-    int at = -1;
-    for (int o : open)
-      if (launches[o].key == gw[k].key) at = o;
-    if (at < 0) {
-      at = (int)launches.size();
-      launches.emplace_back();
-      launches[at].key = gw[k].key;
-      open.push_back(at);
-    }
-    GroupLaunch& L = launches[at];
-    L.members.push_back((int)k);
-    L.items += gw[k].items;
-    const nexrFlatGroupWork& w = works[gw[k].index];
-    if (gw[k].key == kGroupCopyKey) L.maxOut = std::max(L.maxOut, w.nOutputs);
-    else if (gw[k].coll == NEXR_FLAT_GROUP_ALL_REDUCE) L.nParts += (uint64_t)w.nParts;
-    launchOfGw[k] = at;
-  }
-
-  nexrFlatGroupInfo inf;
-  memset(&inf, 0, sizeof(inf));
-  inf.works = (int)gw.size();
-  inf.launches = (int)launches.size();
-  inf.cuts = cuts;
-  for (GroupLaunch& L : launches) {
-    const uint64_t W = L.members.size();
-    L.tableBytes = L.key == kGroupCopyKey
-                       ? W * (kFlatGroupCopyRecBytes + 8ull * (uint64_t)L.maxOut)
-                       : W * (kFlatGroupRecBytes + 16ull * (uint64_t)nRanks) + L.nParts * sizeof(nexrFlatPart);
-    if (L.tableBytes > 0xffffffffull) return nexrInvalidArgument;  // the pool's offset is 32 bits
-    L.fills = L.tableBytes <= (uint64_t)kFlatGroupInlineBytes
-                  ? 0
-                  : (int)((L.tableBytes / 8 + kFlatGroupFillWords - 1) / kFlatGroupFillWords);
-    uint64_t grid = std::min<uint64_t>((L.items + kBlock / 64 - 1) / (kBlock / 64), gridCap(kBlock));
-    if (maxWorkgroups > 0 && grid > (uint64_t)maxWorkgroups) grid = (uint64_t)maxWorkgroups;
-    L.grid = (unsigned)grid;
-    inf.fillLaunches += L.fills;
-    inf.tableBytes += L.tableBytes;
-    inf.workgroups += grid;
-  }
-  if (launchOf)
-    for (int i = 0; i < nWorks; i++) launchOf[i] = placed[i] < 0 ? -1 : launchOfGw[placed[i]];
-  if (info) *info = inf;
-  return nexrSuccess;
-}
-
-// The table of one launch, as nexr_internal.h lays it out.
-void groupTable(const GroupLaunch& L, const std::vector<GroupWork>& gw, const nexrFlatGroupWork* works, int nRanks,
-                std::vector<uint64_t>* tp, uint32_t* poolAt) {
-  std::vector<uint64_t>& t = *tp;
-  t.assign(L.tableBytes / 8, 0);
-  uint64_t items = 0;
-  if (L.key == kGroupCopyKey) {
-    const size_t stride = (kFlatGroupCopyRecBytes + 8u * (size_t)L.maxOut) / 8;
-    for (size_t k = 0; k < L.members.size(); k++) {
-      const GroupWork& g = gw[L.members[k]];
-      const nexrFlatGroupWork& w = works[g.index];
-      uint64_t* rec = t.data() + k * stride;
-      items += g.items;
-      rec[0] = items;
-      rec[1] = g.regionBytes;
-      rec[2] = (uint64_t)(uintptr_t)w.inputs[0];
-      for (int r = 0; r < w.nOutputs; r++) rec[3 + r] = w.outputs[r] == w.inputs[0] ? 0 : (uint64_t)(uintptr_t)w.outputs[r];
-    }
-    *poolAt = 0;
-    return;
-  }
-  const size_t stride = (kFlatGroupRecBytes + 16u * (size_t)nRanks) / 8;
-  const size_t pool = L.members.size() * stride;
-  *poolAt = (uint32_t)(pool * 8);
-  uint32_t partsAt = 0;
-  for (size_t k = 0; k < L.members.size(); k++) {
-    const GroupWork& g = gw[L.members[k]];
-    const nexrFlatGroupWork& w = works[g.index];
-    uint64_t* rec = t.data() + k * stride;
-    items += g.items;
-    const uint32_t nParts = g.coll == NEXR_FLAT_GROUP_ALL_REDUCE ? (uint32_t)w.nParts : 0u;
-    rec[0] = items;
-    rec[1] = g.regionBytes;
-    rec[2] = g.redArg;
-    rec[3] = (uint64_t)(uint32_t)g.coll | (uint64_t)(uint32_t)g.root << 32;
-    rec[4] = (uint64_t)nParts | (uint64_t)partsAt << 32;
-    for (int r = 0; r < nRanks; r++) {
-      rec[5 + r] = (uint64_t)(uintptr_t)w.inputs[r];
-      if (g.coll != NEXR_FLAT_GROUP_REDUCE || r == g.root) rec[5 + nRanks + r] = (uint64_t)(uintptr_t)w.outputs[r];
-    }
-    if (nParts) memcpy(t.data() + pool + (size_t)partsAt * 3, w.parts, (size_t)nParts * sizeof(nexrFlatPart));
-    partsAt += nParts;
-  }
-}
-static_assert(sizeof(nexrFlatPart) == 24, "the pool's entries are three words");
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatGroupPlan(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst,
-                                        int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info) {
-  std::vector<GroupWork> gw;
-  std::vector<GroupLaunch> launches;
-  return groupPlan(nRanks, works, nWorks, userFirst, maxWorkgroups, launchOf, info, &gw, &launches);
-}
-
-NEXR_API nexrResult_t nexrFlatGroup(int nRanks, const nexrFlatGroupWork* works, int nWorks, int userFirst,
-                                    int maxWorkgroups, int* launchOf, nexrFlatGroupInfo* info, nexrStream_t stream) {
-  std::vector<GroupWork> gw;
-  std::vector<GroupLaunch> launches;
-  const nexrResult_t res = groupPlan(nRanks, works, nWorks, userFirst, maxWorkgroups, launchOf, info, &gw, &launches);
-  if (res != nexrSuccess) return res;
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<uint64_t> table;
-  for (const GroupLaunch& L : launches) {
-    uint32_t poolAt = 0;
-    groupTable(L, gw, works, nRanks, &table, &poolAt);
-    uint64_t* ws = nullptr;
-    if (L.fills) {  // the table by value in short launches ahead of the one: nothing is read after return
-      NEXR_HIP(hipMallocAsync((void**)&ws, L.tableBytes, s));
-      FlatGroupFill f;
-      for (size_t at = 0; at < table.size(); at += kFlatGroupFillWords) {
-        f.dst = ws + at;
-        f.n = (int)std::min<size_t>(kFlatGroupFillWords, table.size() - at);
-        f.pad = 0;
-        memcpy(f.words, table.data() + at, (size_t)f.n * 8);
-        const hipError_t e = launch_flat_group_fill(f, s);
-        if (e != hipSuccess) {
-          (void)hipFreeAsync(ws, s);
-          return hipFail(e);
-        }
-      }
-    }
-    hipError_t e;
-    if (L.key == kGroupCopyKey) {
-      FlatGroupCopyParams p;
-      memset((void*)&p, 0, sizeof(p));
-      p.ext = (const char*)ws;
-      p.nItems = L.items;
-      p.nWorks = (int)L.members.size();
-      p.maxOut = L.maxOut;
-      if (!ws) memcpy(p.inl, table.data(), L.tableBytes);
-      e = launch_flat_group_copy(p, L.grid, s);
-    } else {
-      const GroupWork& g0 = gw[L.members[0]];
-      FlatGroupParams p;
-      memset((void*)&p, 0, sizeof(p));
-      p.ext = (const char*)ws;
-      p.nItems = L.items;
-      p.nWorks = (int)L.members.size();
-      p.nRanks = nRanks;
-      p.nFold = g0.nFold;
-      p.shift = g0.shift;
-      p.userFirst = userFirst ? 1 : 0;
-      p.preOp = g0.preOp;
-      p.postOp = g0.postOp;
-      p.isMin = g0.isMin;
-      p.poolAt = poolAt;
-      if (!ws) memcpy(p.inl, table.data(), L.tableBytes);
-      e = launch_flat_group(g0.dt, g0.op, p, L.grid, s);
-    }
-    if (ws) (void)hipFreeAsync(ws, s);
-    NEXR_HIP(e);
-  }
-  return nexrSuccess;
-}
-
-// ---- nexrFlatHost*: the flat entries over host memory -------------------------------------------------------
-// The device entries' checks, then one helper for all six (flatHostRun). Every DISTINCT (address, length) among
-// the call's buffers is classified once, as nexrReduceCopyHost classifies a buffer: the registration cache
-// (regLookup, no HIP call), else the runtime's pointer query, trusted only when the whole buffer lies inside
-// the pinned range it reports; a buffer that begins inside such a range and runs past its end is `cut`: never
-// read in place, and copied only in pieces (hostCopyPieces). NEXR_HOST_ZERO_COPY=0 stages everything.
-//   - Every buffer pinned: one launch over the device-mapped addresses, the grid capped at hostGrid().
-//   - Otherwise a pageable input is copied into a device slot before the launch and a pageable output out of one
-//     behind it; pinned buffers are still read and written in place. A host address always maps to the same
-//     device address (pinned) or, as an input, to the same slot, so an input that appears twice is copied once.
-//     Outputs that receive the same bytes (the all-reduces, the broadcast, the all-gather) share ONE staged
-//     output, copied out once per distinct pageable output address. Every copy-in of a launch's bytes precedes
-//     the launch and every copy-out follows it, and a lane stores a position only after it has read it from every
-//     input, so the device entries' aliasing rules hold for host addresses as they stand.
-//   - Calls whose inputs and outputs are one region (ring and tree all-reduce, reduce, broadcast) and that hold
-//     more than one chunk (NEXR_FLAT_HOST_CHUNK_BYTES, 32 MiB, cut to a multiple of the 2048-byte piece) run as
-//     a two-slot window pipeline on a pooled staging ring (stageFor): window w is copied in and launched on the
-//     caller's stream while window w - 1 is copied out on the ring's stream. A staged window holds only its own
-//     bytes, so its pointer is biased by -winBeg. The reduce-scatter and the all-gather stage whole: their
-//     chunks are strided through the inputs and the outputs.
-namespace {
-std::atomic<uint64_t> gFhCalls{0}, gFhZeroCopy{0}, gFhStaged{0}, gFhRegHits{0}, gFhQueries{0}, gFhWindows{0};
-
-struct FlatHostIo {
-  int nIn = 0, nOut = 0;
-  const void* in[NEXR_SYM_MAX_RANKS];  // host inputs, slot by slot
-  void* out[NEXR_SYM_MAX_RANKS];       // host outputs, slot by slot; null: the slot has none
-  size_t inBytes = 0, outBytes = 0;
-  bool sharedOut = false;  // every output receives the same bytes: one staged output serves the pageable ones
-  bool compact = false;    // the launch takes the distinct device outputs as a list, not slot by slot
-  bool windowed = false;   // inputs and outputs are one region and the launch takes a byte window of it
-};
-// (device inputs by slot, device outputs by slot or as the compact list, their number, winBeg, winEnd, the
-// grid's cap or 0, stream)
-using FlatHostLaunch = std::function<nexrResult_t(const char* const*, char* const*, int, uint64_t, uint64_t,
-                                                  uint64_t, hipStream_t)>;
-
-struct FlatHostBuf {
-  uintptr_t host;
-  size_t bytes;
-  bool pin, cut;
-  char* dev;    // pinned: the device address of the buffer
-  int stageIn;  // pageable, used as an input: its slot among the staged inputs, else -1
-  int stageOut; // pageable, used as an output: its slot among the staged outputs, else -1
-};
-
-// 32 MiB: with pageable buffers fewer windows were faster at every point measured (a 64 MiB all-reduce at 2 ranks:
-// 6.18 ms in 4 MiB windows, 5.61 in 8, 5.21 in 16, 5.05 in 32, 5.02 whole; profiles/r19e_flat_host_chunk_sweep_64mib.json),
-// so the chunk is what bounds the staging ring's memory, set where the loss to staging whole is 0.5 %.
-size_t flatHostChunk() {
-  static const long v = envLong("NEXR_FLAT_HOST_CHUNK_BYTES", 32l << 20);
-  const size_t c = (size_t)(v > 2048 ? v : 2048);
-  return c / 2048 * 2048;
-}
-
-int flatHostClassify(std::vector<FlatHostBuf>& bufs, const void* hp, size_t bytes, bool zeroCopy) {
-  for (size_t i = 0; i < bufs.size(); i++)
-    if (bufs[i].host == (uintptr_t)hp && bufs[i].bytes == bytes) return (int)i;
-  FlatHostBuf b{(uintptr_t)hp, bytes, false, false, nullptr, -1, -1};
-  void* dev = nullptr;
-  if (!zeroCopy) {
-    b.cut = true;  // what the runtime knows of the range is not asked: every copy goes in pieces
-  } else if (regLookup(hp, bytes, &dev)) {
-    b.pin = true;
-    gFhRegHits.fetch_add(1, std::memory_order_relaxed);
-  } else {
-    gFhQueries.fetch_add(1, std::memory_order_relaxed);
-    hipPointerAttribute_t a;
-    b.pin = hipPointerGetAttributes(&a, hp) == hipSuccess && a.type == hipMemoryTypeHost && a.devicePointer != nullptr;
-    if (b.pin) {
-      dev = a.devicePointer;
-      uintptr_t beg = 0;
-      size_t size = 0;
-      if (hipPointerGetAttribute(&beg, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, (hipDeviceptr_t)hp) != hipSuccess ||
-          hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, (hipDeviceptr_t)hp) != hipSuccess ||
-          (uintptr_t)hp < beg || (uintptr_t)hp + bytes > beg + size) {
-        b.pin = false;  // the device mapping ends before the buffer does
-        b.cut = true;
-      }
-    }
-    (void)hipGetLastError();  // pageable memory reports an error: not a failure of this call
-  }
-  b.dev = b.pin ? (char*)dev : nullptr;
-  bufs.push_back(b);
-  return (int)bufs.size() - 1;
-}
-
-nexrResult_t flatHostRun(const FlatHostIo& io, hipStream_t s, const FlatHostLaunch& launch) {
-  static const long zeroCopy = envLong("NEXR_HOST_ZERO_COPY", 1);
-  gFhCalls.fetch_add(1, std::memory_order_relaxed);
-  std::vector<FlatHostBuf> bufs;
-  int inIx[NEXR_SYM_MAX_RANKS], outIx[NEXR_SYM_MAX_RANKS];
-  int nStageIn = 0, nStageOut = 0, nPinned = 0;
-  for (int r = 0; r < io.nIn; r++) {
-    inIx[r] = flatHostClassify(bufs, io.in[r], io.inBytes, zeroCopy != 0);
-    FlatHostBuf& b = bufs[inIx[r]];
-    if (!b.pin && b.stageIn < 0) b.stageIn = nStageIn++;
-  }
-  for (int r = 0; r < io.nOut; r++) {
-    outIx[r] = -1;
-    if (!io.out[r]) continue;
-    outIx[r] = flatHostClassify(bufs, io.out[r], io.outBytes, zeroCopy != 0);
-    FlatHostBuf& b = bufs[outIx[r]];
-    if (!b.pin && b.stageOut < 0) b.stageOut = io.sharedOut ? 0 : nStageOut++;
-    if (!b.pin && io.sharedOut) nStageOut = 1;
-  }
-  for (const FlatHostBuf& b : bufs) nPinned += b.pin ? 1 : 0;
-  const char* devIn[NEXR_SYM_MAX_RANKS];
-  char* devOut[NEXR_SYM_MAX_RANKS];
-  if (nStageIn + nStageOut == 0) {  // zero-copy: the kernel reads and writes the user buffers over the link
-    gFhZeroCopy.fetch_add(1, std::memory_order_relaxed);
-    gFhWindows.fetch_add(1, std::memory_order_relaxed);
-    for (int r = 0; r < io.nIn; r++) devIn[r] = bufs[inIx[r]].dev;
-    int m = 0;
-    for (int r = 0; r < io.nOut; r++) {
-      char* d = outIx[r] < 0 ? nullptr : bufs[outIx[r]].dev;
-      if (!io.compact) {
-        devOut[m++] = d;
-      } else if (d && std::find(devOut, devOut + m, d) == devOut + m) {
-        devOut[m++] = d;
-      }
-    }
-    const nexrResult_t res = launch(devIn, devOut, m, 0, io.windowed ? io.inBytes : 0, hostGrid(), s);
-    if (res != nexrSuccess) return res;
-    NEXR_HIP(hipStreamSynchronize(s));
-    return nexrSuccess;
-  }
-  gFhStaged.fetch_add((uint64_t)(nStageIn + nStageOut), std::memory_order_relaxed);
-  const size_t region = io.inBytes;
-  const size_t chunk = io.windowed ? std::min(flatHostChunk(), (region + 2047) / 2048 * 2048) : 0;
-  const size_t inStride = ((io.windowed ? chunk : io.inBytes) + 255) & ~(size_t)255;
-  const size_t outStride = ((io.windowed ? chunk : io.outBytes) + 255) & ~(size_t)255;
-  const size_t nWindows = io.windowed ? (region + chunk - 1) / chunk : 1;
-  // A ring is two slots. A call of one window (every reduce-scatter and all-gather among them) uses the ring's
-  // memory as ONE slot, so it asks for half its bytes a slot.
-  const size_t slotNeed = inStride * (size_t)nStageIn + outStride * (size_t)nStageOut;
-  StageLease lease;
-  nexrResult_t res = stageFor(nWindows > 1 ? slotNeed : (slotNeed + 1) / 2, s, &lease);
-  if (res != nexrSuccess) return res;
-  HostStage* st = lease.st;
-  gFhWindows.fetch_add(nWindows, std::memory_order_relaxed);
-  for (size_t w = 0; w < nWindows; w++) {
-    const int slot = (int)(w & 1);
-    const uint64_t wb = io.windowed ? (uint64_t)w * chunk : 0;
-    const uint64_t we = io.windowed ? std::min<uint64_t>(wb + chunk, region) : 0;
-    const size_t inLen = io.windowed ? (size_t)(we - wb) : io.inBytes;
-    const size_t outLen = io.windowed ? (size_t)(we - wb) : io.outBytes;
-    char* inBase = st->buf + (nWindows > 1 ? (size_t)slot * st->slotBytes : 0);
-    char* outBase = inBase + inStride * (size_t)nStageIn;
-    if (w >= 2) NEXR_HIP(hipStreamWaitEvent(s, st->outDone[slot], 0));  // slot drained by window w - 2's copies out
-    for (const FlatHostBuf& b : bufs) {
-      if (b.stageIn < 0) continue;
-      char* d = inBase + inStride * (size_t)b.stageIn;
-      if (b.cut)
-        NEXR_HIP(hostCopyPieces(d, (char*)b.host + wb, inLen, true, s));
-      else
-        NEXR_HIP(hipMemcpyAsync(d, (const char*)b.host + wb, inLen, hipMemcpyHostToDevice, s));
-    }
-    // a staged window holds only its own bytes: the kernel addresses `pointer + region offset`
-    for (int r = 0; r < io.nIn; r++) {
-      const FlatHostBuf& b = bufs[inIx[r]];
-      devIn[r] = b.pin ? b.dev : inBase + inStride * (size_t)b.stageIn - wb;
-    }
-    int m = 0;
-    for (int r = 0; r < io.nOut; r++) {
-      char* d = nullptr;
-      if (outIx[r] >= 0) {
-        const FlatHostBuf& b = bufs[outIx[r]];
-        d = b.pin ? b.dev : outBase + outStride * (size_t)b.stageOut - wb;
-      }
-      if (!io.compact) {
-        devOut[m++] = d;
-      } else if (d && std::find(devOut, devOut + m, d) == devOut + m) {
-        devOut[m++] = d;
-      }
-    }
-    res = launch(devIn, devOut, m, wb, we, nPinned > 0 ? hostGrid() : 0, s);
-    if (res != nexrSuccess) return res;
-    if (nStageOut == 0) continue;
-    NEXR_HIP(hipEventRecord(st->kernelDone[slot], s));
-    NEXR_HIP(hipStreamWaitEvent(st->out, st->kernelDone[slot], 0));
-    for (const FlatHostBuf& b : bufs) {
-      if (b.stageOut < 0) continue;
-      char* d = outBase + outStride * (size_t)b.stageOut;
-      if (b.cut)
-        NEXR_HIP(hostCopyPieces(d, (char*)b.host + wb, outLen, false, st->out));
-      else
-        NEXR_HIP(hipMemcpyAsync((char*)b.host + wb, d, outLen, hipMemcpyDeviceToHost, st->out));
-    }
-    NEXR_HIP(hipEventRecord(st->outDone[slot], st->out));
-  }
-  NEXR_HIP(hipStreamSynchronize(st->out));
-  NEXR_HIP(hipStreamSynchronize(s));
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrFlatHostAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
-                                            size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                            int userFirst, const nexrFlatPart* parts, int nParts,
-                                            nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  const nexrResult_t res = flatAllReduceCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
-                                              parts, nParts, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  FlatHostIo io;
-  io.nIn = io.nOut = nRanks;
-  for (int r = 0; r < nRanks; r++) {
-    io.in[r] = inputs[r];
-    io.out[r] = outputs[r];
-  }
-  io.inBytes = io.outBytes = (size_t)p.regionBytes;
-  io.sharedOut = io.compact = io.windowed = true;
-  return flatHostRun(io, (hipStream_t)stream,
-                     [&](const char* const* in, char* const* out, int nOut, uint64_t wb, uint64_t we, uint64_t cap,
-                         hipStream_t s) {
-                       for (int r = 0; r < nRanks; r++) {
-                         p.in[r] = in[r];
-                         p.out[r] = r < nOut ? out[r] : nullptr;
-                       }
-                       p.nOut = nOut;
-                       p.winBeg = wb;
-                       p.winEnd = we;
-                       return flatAllReduceLaunch(p, dt, op, parts, nParts, cap, s);
-                     });
-}
-
-NEXR_API nexrResult_t nexrFlatHostReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
-                                                size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                                int userFirst, nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  const nexrResult_t res =
-      flatReduceScatterCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  FlatHostIo io;
-  io.nIn = io.nOut = nRanks;
-  for (int r = 0; r < nRanks; r++) {
-    io.in[r] = inputs[r];
-    io.out[r] = outputs[r];
-  }
-  io.outBytes = (size_t)p.regionBytes;
-  io.inBytes = io.outBytes * (size_t)nRanks;
-  return flatHostRun(io, (hipStream_t)stream,
-                     [&](const char* const* in, char* const* out, int, uint64_t, uint64_t, uint64_t cap,
-                         hipStream_t s) {
-                       for (int r = 0; r < nRanks; r++) {
-                         p.in[r] = in[r];
-                         p.out[r] = out[r];
-                       }
-                       NEXR_HIP(launch_flat(dt, op, p, flatGrid(p.regionBytes, nRanks, cap), s));
-                       return nexrSuccess;
-                     });
-}
-
-NEXR_API nexrResult_t nexrFlatHostReduce(int nRanks, const void* const* inputs, void* output, int root, size_t nElts,
-                                         int datatype, int devRedOp, uint64_t redOpArg, int userFirst,
-                                         nexrStream_t stream) {
-  FlatParams p;
-  int dt, op;
-  const nexrResult_t res =
-      flatReduceCheck(nRanks, inputs, output, root, nElts, datatype, devRedOp, redOpArg, userFirst, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  FlatHostIo io;
-  io.nIn = nRanks;
-  io.nOut = 1;
-  for (int r = 0; r < nRanks; r++) io.in[r] = inputs[r];
-  io.out[0] = output;
-  io.inBytes = io.outBytes = (size_t)p.regionBytes;
-  io.windowed = true;
-  return flatHostRun(io, (hipStream_t)stream,
-                     [&](const char* const* in, char* const* out, int, uint64_t wb, uint64_t we, uint64_t cap,
-                         hipStream_t s) {
-                       for (int r = 0; r < nRanks; r++) p.in[r] = in[r];
-                       p.out[root] = out[0];
-                       p.winBeg = wb;
-                       p.winEnd = we;
-                       NEXR_HIP(launch_flat(dt, op, p, flatGrid(we - wb, 1, cap), s));
-                       return nexrSuccess;
-                     });
-}
-
-NEXR_API nexrResult_t nexrFlatHostTreeAllReduce(int nRanks, const void* const* inputs, void* const* outputs,
-                                                size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                                int userFirst, const nexrFlatTreeLinks* const* trees, int nTrees,
-                                                const nexrFlatTreePart* parts, int nParts, nexrStream_t stream) {
-  FlatTreeParams p;
-  int dt, op;
-  const nexrResult_t res = flatTreeCheck(nRanks, inputs, outputs, nElts, datatype, devRedOp, redOpArg, userFirst,
-                                         trees, nTrees, parts, nParts, &p, &dt, &op);
-  if (res != nexrSuccess || nElts == 0) return res;
-  FlatHostIo io;
-  io.nIn = io.nOut = nRanks;
-  for (int r = 0; r < nRanks; r++) {
-    io.in[r] = inputs[r];
-    io.out[r] = outputs[r];
-  }
-  io.inBytes = io.outBytes = (size_t)p.nBytes;
-  io.sharedOut = io.compact = io.windowed = true;
-  return flatHostRun(io, (hipStream_t)stream,
-                     [&](const char* const* in, char* const* out, int nOut, uint64_t wb, uint64_t we, uint64_t cap,
-                         hipStream_t s) {
-                       for (int r = 0; r < nRanks; r++) {
-                         p.in[r] = in[r];
-                         p.out[r] = r < nOut ? out[r] : nullptr;
-                       }
-                       p.nOut = nOut;
-                       p.winBeg = wb;
-                       p.winEnd = we;
-                       return flatTreeLaunch(p, dt, op, parts, nParts, cap, s);
-                     });
-}
-
-NEXR_API nexrResult_t nexrFlatHostBroadcast(int nRanks, const void* input, void* const* outputs, size_t nBytes,
-                                            nexrStream_t stream) {
-  if (!input || !outputs) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  FlatHostIo io;
-  bool any = false;
-  for (int r = 0; r < nRanks; r++) {
-    if (!outputs[r]) return nexrInvalidArgument;
-    io.out[r] = outputs[r] != input ? outputs[r] : nullptr;
-    any = any || io.out[r];
-  }
-  if (nBytes == 0 || !any) return nexrSuccess;
-  io.nIn = 1;
-  io.nOut = nRanks;
-  io.in[0] = input;
-  io.inBytes = io.outBytes = nBytes;
-  io.sharedOut = io.compact = io.windowed = true;
-  return flatHostRun(io, (hipStream_t)stream,
-                     [&](const char* const* in, char* const* out, int nOut, uint64_t wb, uint64_t we, uint64_t cap,
-                         hipStream_t s) {
-                       FlatBcastParams p;
-                       memset((void*)&p, 0, sizeof(p));
-                       for (int r = 0; r < nOut; r++) p.out[r] = out[r];
-                       p.in = in[0];
-                       p.nBytes = nBytes;
-                       p.winBeg = wb;
-                       p.winEnd = we;
-                       p.nRanks = nOut;
-                       NEXR_HIP(launch_flat_bcast(p, flatGrid(we - wb, 1, cap), s));
-                       return nexrSuccess;
-                     });
-}
-
-NEXR_API nexrResult_t nexrFlatHostAllGather(int nRanks, const void* const* inputs, void* const* outputs,
-                                            size_t nBytes, nexrStream_t stream) {
-  if (!inputs || !outputs) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS) return nexrInvalidArgument;
-  if (nBytes > (size_t)-1 / (size_t)nRanks) return nexrInvalidArgument;  // an output's nRanks * nBytes bytes
-  FlatHostIo io;
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r]) return nexrInvalidArgument;
-    io.in[r] = inputs[r];
-    io.out[r] = outputs[r];
-  }
-  if (nBytes == 0) return nexrSuccess;
-  io.nIn = io.nOut = nRanks;
-  io.inBytes = nBytes;
-  io.outBytes = nBytes * (size_t)nRanks;
-  io.sharedOut = true;
-  return flatHostRun(io, (hipStream_t)stream,
-                     [&](const char* const* in, char* const* out, int, uint64_t, uint64_t, uint64_t cap,
-                         hipStream_t s) {
-                       SymAgParams p;
-                       memset(&p, 0, sizeof(p));
-                       for (int r = 0; r < nRanks; r++) {
-                         p.in[r] = in[r];
-                         p.out[r] = out[r];
-                         // Pageable outputs all name the one staged output, which the kernel therefore
-                         // stores once per pageable rank (the same bytes, in device memory: up to n times
-                         // the device writes, none over the link). The reference's inPlace, per rank: a
-                         // staged buffer never lies inside another
-                         if ((uintptr_t)in[r] == (uintptr_t)out[r] + (uintptr_t)r * nBytes) p.inPlace |= 1ull << r;
-                       }
-                       p.nBytes = nBytes;
-                       p.nRanks = nRanks;
-                       unsigned grid = symChunkGrid(nBytes, 1, nRanks);
-                       if (cap > 0 && grid > cap) grid = (unsigned)cap;
-                       NEXR_HIP(launch_sym_all_gather(p, grid, s));
-                       return nexrSuccess;
-                     });
-}
-
-NEXR_API nexrResult_t nexrGetFlatHostStats(nexrFlatHostStats* stats, int reset) {
-  if (stats == nullptr) return nexrInvalidArgument;
-  auto take = [&](std::atomic<uint64_t>& a) { return reset ? a.exchange(0) : a.load(); };
-  stats->calls = take(gFhCalls);
-  stats->zeroCopyCalls = take(gFhZeroCopy);
-  stats->stagedBuffers = take(gFhStaged);
-  stats->registeredHits = take(gFhRegHits);
-  stats->pointerQueries = take(gFhQueries);
-  stats->windows = take(gFhWindows);
-  return nexrSuccess;
-}
-
-// ---- nexrSymLLAllReduce, nexrSymLLReduceScatter, nexrSymLLAllGather -----------------------------------------
-// Two things make a launch finish: its grid of nRanks * nBlocks teams is resident as a whole (the occupancy
-// check below), and every poll of its kernel is bounded (nexr_sym.hip). There is no dry run: a round needs
-// nothing from a later launch.
-NEXR_API nexrResult_t nexrSymLLWindowBytes(int nRanks, int maxBlocks, size_t* bytes) {
-  if (!bytes || nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS || maxBlocks < 1 || maxBlocks > NEXR_SYM_LL_MAX_BLOCKS)
-    return nexrInvalidArgument;
-  *bytes = (size_t)NEXR_SYM_LL_HEADER_BYTES + (size_t)maxBlocks * 2u * (size_t)nRanks * NEXR_SYM_LL_ROUND_PACKS * 16u;
-  return nexrSuccess;
-}
-
-namespace {
-// Workgroups of a symmetric LL kernel the current device keeps resident, as simpleGroupResident: the
-// occupancy query's answer, capped at 4 per CU, less one (the query over-reports by one for 256-thread
-// workgroups of kernels with many scalar registers; a surplus team would queue behind teams that poll it).
-// Test hook: NEXR_TEST_SYM_LL_RESIDENT=k makes the next calls take k as that number (read per call).
-nexrResult_t symLLResident(int coll, int dt, int64_t* resident) {
-  if (const char* e = getenv("NEXR_TEST_SYM_LL_RESIDENT"))
-    if (*e) {
-      *resident = strtoll(e, nullptr, 10);
-      return nexrSuccess;
-    }
-  constexpr int kDevs = 16;
-  static std::atomic<int64_t> cache[3][kDevs][nexrNumTypes];
-  int dev = 0;
-  NEXR_HIP(hipGetDevice(&dev));
-  const bool cached = dev >= 0 && dev < kDevs;
-  if (cached) {
-    const int64_t v = cache[coll][dev][dt].load(std::memory_order_relaxed);
-    if (v > 0) {
-      *resident = v;
-      return nexrSuccess;
-    }
-  }
-  int cus = 0, blocks = 0;
-  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  NEXR_HIP(sym_ll_blocks_per_cu(coll, dt, &blocks));
-  if (blocks > 4) blocks = 4;
-  if (blocks > 1) blocks--;
-  *resident = (int64_t)blocks * cus;
-  if (cached && *resident > 0) cache[coll][dev][dt].store(*resident, std::memory_order_relaxed);
-  return nexrSuccess;
-}
-
-// The host side of the three calls. coll: 0 all-reduce (count elements per buffer), 1 reduce-scatter (count
-// elements per chunk), 2 all-gather (count bytes, esz 1).
-nexrResult_t symLL(int coll, int nRanks, const void* const* inputs, void* const* outputs, size_t count, int datatype,
-                   void* const* windows, size_t windowBytes, int nBlocks, uint32_t* status, uint32_t timeoutUs,
-                   nexrStream_t stream) {
-  if (!inputs || !outputs || !windows) return nexrInvalidArgument;
-  if (nRanks < 2 || nRanks > NEXR_SYM_MAX_RANKS || nBlocks < 0 || nBlocks > NEXR_SYM_LL_MAX_BLOCKS)
-    return nexrInvalidArgument;
-  const int B = nBlocks ? nBlocks : 1;
-  const uint64_t esz = coll == 2 ? 1 : typeSize(datatype);
-  SymLLParams p;
-  memset(&p, 0, sizeof(p));
-  for (int r = 0; r < nRanks; r++) {
-    if (!inputs[r] || !outputs[r] || !windows[r]) return nexrInvalidArgument;
-    if (((uintptr_t)inputs[r] | (uintptr_t)outputs[r]) & (esz - 1)) return nexrInvalidArgument;
-    if ((uintptr_t)windows[r] & 15) return nexrInvalidArgument;
-    p.in[r] = (const char*)inputs[r];
-    p.out[r] = (char*)outputs[r];
-    p.win[r] = (char*)windows[r];
-  }
-  size_t need = 0;
-  if (nexrSymLLWindowBytes(nRanks, B, &need) != nexrSuccess || windowBytes < need) return nexrInvalidArgument;
-  // the reference's int nElts: a buffer (for the reduce-scatter the whole input) stays below 2^31 bytes
-  const uint64_t limit = (1ull << 31) / esz / (coll == 1 ? (uint64_t)nRanks : 1u);
-  if ((uint64_t)count >= limit) return nexrInvalidArgument;
-  if (count == 0) return nexrSuccess;
-  int64_t resident = 0;
-  const nexrResult_t rr = symLLResident(coll, coll == 2 ? nexrFloat32 : datatype, &resident);
-  if (rr != nexrSuccess) return rr;
-  if ((int64_t)nRanks * B > resident) return nexrInvalidUsage;
-  p.nBytes = (uint64_t)count * esz;
-  p.status = status;
-  p.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;  // s_memrealtime: 100 MHz
-  p.nRanks = nRanks;
-  p.nBlocks = B;
-  p.firstWins = semantics() == nexrSemanticsShipped;  // SKIP_COMP: every add returns its first operand
-  NEXR_HIP(launch_sym_ll(coll, datatype, p, (hipStream_t)stream));
-  return nexrSuccess;
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrSymLLAllReduce(int nRanks, const void* const* inputs, void* const* outputs, size_t nElts,
-                                         int datatype, int devRedOp, uint64_t redOpArg, void* const* windows,
-                                         size_t windowBytes, int nBlocks, uint32_t* status, uint32_t timeoutUs,
-                                         nexrStream_t stream) {
-  (void)redOpArg;
-  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
-  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
-  return symLL(0, nRanks, inputs, outputs, nElts, datatype, windows, windowBytes, nBlocks, status, timeoutUs, stream);
-}
-
-NEXR_API nexrResult_t nexrSymLLReduceScatter(int nRanks, const void* const* inputs, void* const* outputs,
-                                             size_t nElts, int datatype, int devRedOp, uint64_t redOpArg,
-                                             void* const* windows, size_t windowBytes, int nBlocks,
-                                             uint32_t* status, uint32_t timeoutUs, nexrStream_t stream) {
-  (void)redOpArg;
-  if (datatype != nexrFloat32 && datatype != nexrFloat16 && datatype != nexrBfloat16) return nexrInvalidArgument;
-  if (devRedOp != nexrDevSum) return nexrInvalidArgument;
-  return symLL(1, nRanks, inputs, outputs, nElts, datatype, windows, windowBytes, nBlocks, status, timeoutUs, stream);
-}
-
-NEXR_API nexrResult_t nexrSymLLAllGather(int nRanks, const void* const* inputs, void* const* outputs, size_t nBytes,
-                                         void* const* windows, size_t windowBytes, int nBlocks, uint32_t* status,
-                                         uint32_t timeoutUs, nexrStream_t stream) {
-  return symLL(2, nRanks, inputs, outputs, nBytes, nexrFloat32, windows, windowBytes, nBlocks, status, timeoutUs,
-               stream);
 }
 
 NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,

@@ -1,5 +1,5 @@
 // nexr_exchange_v_checks.h — the checks of the all-to-all with a count per pair that need no device, shared by
-// nexrFlatAllToAllv (nexr_api.cpp) and nexrRingAllToAllv (nexr_ring.cpp, at any rank count): the half-open range
+// nexrFlatAllToAllv (nexr_flat_api.cpp) and nexrRingAllToAllv (nexr_ring.cpp, at any rank count): the half-open range
 // rule and the bound on a capacity stand here and nowhere else. The reduce-scatter and the all-gather with a count
 // per rank (nexrFlatReduceScatterv, nexrFlatAllGatherv and their ring entries) share them, with n counts. The
 // exchanges of a fixed size (nexrFlatAllToAll, nexrFlatAllToAll2D, nexrFlatAllGather2D and their ring entries) take

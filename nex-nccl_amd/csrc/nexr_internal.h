@@ -190,7 +190,7 @@ hipError_t launch_simple_group_direct(int dt, int op, const SimpleDirectParams* 
 hipError_t simple_group_direct_blocks_per_cu(int dt, int op, int* blocks);
 
 // The symmetric all-reduce in one launch (nexrSymAllReduce; nexr_sym.hip): the 2n pointers and the ownership
-// plan the host derives from rank 0's pointers (symPlan, nexr_api.cpp; reference
+// plan the host derives from rank 0's pointers (symPlan, nexr_flat_api.cpp; reference
 // src/device/symmetric/all_reduce.hh:199-252). Offsets are bytes from every buffer's start.
 struct SymParams {
   const char* in[NEXR_SYM_MAX_RANKS];

@@ -193,6 +193,67 @@ def test_flat_argument_checks(nexr, L):
     assert ar(dt=u8, parts=_parts(nexr, [(0, 64, 8)])) == bad                # 16 / esz = 16 elements
 
 
+def _size_zero_cases(nexr):
+    """name -> (the argument list of a valid call of size 0, the index of the one argument then made invalid, its
+    invalid value), for every nexrFlat* entry. The invalid argument stands behind the size wherever the signature
+    has one there; the broadcasts and the host all-gather have only the stream behind it."""
+    F32, SUM = int(nexr.DataType.Float32), int(nexr.DevRedOp.Sum)
+    a = _arr([0x1000, 0x2000, 0x3000])
+    holed = _arr([0x1000, None, 0x3000])
+    u64s = lambda vals: (ctypes.c_uint64 * len(vals))(*vals)
+    sizes = lambda vals: (ctypes.c_size_t * len(vals))(*vals)
+    bits, ptrs, odd = u64s([1, 2, 3]), u64s([0x100, 0x200, 0x300]), u64s([0x100, 0x202, 0x300])
+    trees, rows = nexr.flat_tree_links([[(-1, [1]), (0, [2]), (1, [])]])
+    zeros9, zeros3, none3 = u64s([0] * 9), u64s([0] * 3), sizes([0] * 3)
+    cnt9, cnt3 = ctypes.cast(zeros9, ctypes.c_void_p), ctypes.cast(zeros3, ctypes.c_void_p)
+    work = nexr.FlatGroupWork(nexr.FLAT_GROUP_ALL_REDUCE, F32, SUM, 0, 0, ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)),
+                              ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)), 3, 0, None, 0)
+    works = (nexr.FlatGroupWork * 1)(work)
+    HOST = 1  # nexrScalarHostImmediate: the counts are read, and summed to 0, before any device call
+    all_reduce = ([3, a, a, 0, F32, SUM, 0, 1, None, 0, None], 9, -1)                # nParts
+    reduce_scatter = ([3, a, a, 0, F32, SUM, 0, 1, None], 5, -1)                     # devRedOp
+    reduce = ([3, a, 0x1000, 0, 0, F32, SUM, 0, 0, None], 5, int(nexr.DataType.Float8e4m3))
+    tree = ([3, a, a, 0, F32, SUM, 0, 1, trees, 1, None, 0, None], 9, 3)             # nTrees
+    cases = {
+        "nexrFlatAllReduce": all_reduce,
+        "nexrFlatReduceScatter": reduce_scatter,
+        "nexrFlatReduce": reduce,
+        "nexrFlatTreeAllReduce": tree,
+        "nexrFlatBroadcast": ([3, 0x1000, a, 0, None], 2, holed),
+        "nexrFlatAllReducePreMul": ([3, a, a, 0, F32, bits, 0, 1, None, 0, None], 5, None),      # no scalars
+        "nexrFlatReduceScatterPreMul": ([3, a, a, 0, F32, ptrs, 1, 1, None], 5, odd),            # a misaligned pointer
+        "nexrFlatReducePreMul": ([3, a, 0x1000, 0, 0, F32, bits, 0, 0, None], 5, 12),            # datatype
+        "nexrFlatTreeAllReducePreMul": ([3, a, a, 0, F32, bits, 0, 1, trees, 1, None, 0, None], 8, None),   # trees
+        "nexrFlatHostAllReduce": all_reduce,
+        "nexrFlatHostReduceScatter": (reduce_scatter[0], 5, 5),
+        "nexrFlatHostReduce": reduce,
+        "nexrFlatHostTreeAllReduce": (tree[0], 9, 0),
+        "nexrFlatHostBroadcast": ([3, 0x1000, a, 0, None], 2, holed),
+        "nexrFlatHostAllGather": ([3, a, a, 0, None], 2, holed),
+        "nexrFlatGroup": ([3, works, 1, 1, 0, None, None, None], 4, -1),             # maxWorkgroups
+        "nexrFlatGroupPlan": ([3, works, 1, 1, 0, None, None], 4, -1),
+        "nexrFlatAllToAll": ([3, a, a, 0, 0, None], 4, -1),
+        "nexrFlatAllToAllv": ([3, a, a, cnt9, HOST, 4, none3, none3, None, 0, None], 5, 3),       # esz
+        "nexrFlatReduceScatterv": ([3, a, a, cnt3, HOST, F32, SUM, 0, 1, none3, none3, None, 0, None], 12, -1),
+        "nexrFlatAllGatherv": ([3, a, a, cnt3, HOST, 4, none3, none3, None, 0, None], 4, 7),      # residence
+        "nexrFlatAllToAll2D": ([3, a, a, 0, 16, nexr.LAYOUT_ROWS, nexr.LAYOUT_BLOCKS, 0, None], 5, 2),   # a bad layout
+        "nexrFlatAllGather2D": ([3, a, a, 0, 16, 0, None], 0, 1),                    # nRanks
+    }
+    return cases, (rows, zeros9, zeros3)
+
+
+def test_every_check_stands_before_the_zero_size_return(nexr, L):
+    """A call of size 0 succeeds without a launch, and with one invalid argument it is still refused: no check of
+    any nexrFlat* entry stands behind its zero-size return. None of these calls reaches the device."""
+    cases, _keep = _size_zero_cases(nexr)
+    assert set(cases) == {s for s in nexr.ABI_SYMBOLS if s.startswith("nexrFlat")}
+    for name, (args, at, wrong) in cases.items():
+        assert getattr(L, name)(*args) == nexr.Result.Success, name
+        refused = list(args)
+        refused[at] = wrong
+        assert getattr(L, name)(*refused) == nexr.Result.InvalidArgument, name
+
+
 def test_set_flat_argument_checks(nexr, oracle):
     ring = importlib.import_module("nex-nccl_amd.ring")
     RL = ring.ring_lib()

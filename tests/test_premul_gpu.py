@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 import arith_edges as ae
+import flat_cases as fc
+import flat_tree_cases as ftc
 import premul_cases as pc
 import ring_modes_cases as rm
 from oracle import ring as oring
@@ -234,6 +236,55 @@ def test_flat_two_channels(ring, oracle, protocol):
             count = rm.LARGE[coll](n, chunk_of(coll, protocol, rm.esz_of(dt)))
             call = pc.make_call(oracle, oring, pc.spec(k, coll, "large", count, dt, n), n, SEED, bits, protocol, 2)
             check_both(comm, call, h, (protocol, n, 2), explicit=k % 2 == 0)
+
+
+# ---- part lists beyond the per-rank kernels' argument blocks ------------------------------------------------------------
+def _one_pack_per_part(nexr, oracle, coll, n_parts, launch, model):
+    """2 ranks, fp32, distinct scalars, `n_parts` parts of one 16-byte pack each: launch(ins, outs, count, bits) on a
+    fresh arena, checked against model(products, count, step), the rule over the oracle's Sum step on the oracle's
+    products."""
+    n, dt, pack = 2, ae.F32, 4
+    count = n_parts * pack
+    bits = pc.scalar_bits(dt, n)
+    assert len(set(bits)) == n
+    call = pc.Call(pc.spec(0, coll, "one pack per part", count, dt, n), n, SEED)
+    dev_op, arg = oracle.host_to_dev_red_op(rm.SUM, dt, n)
+
+    def step(x, vals, post):   # SIMPLE: the rank's own input first, then what it received
+        srcs = ([x] if x is not None else []) + list(vals)
+        return oracle.reduce_copy(srcs, 1, dt, dev_op, arg, [arg] if x is not None else [], post)[0]
+
+    call.set_outputs(model(pc.premultiplied(oracle, call, bits), count, step))
+    dev = torch.empty(call.arena0.size, dtype=torch.uint8, device="cuda")
+    dev.copy_(torch.from_numpy(call.arena0))
+    torch.cuda.synchronize()
+    launch([dev.data_ptr() + o for o in call.send_off], [dev.data_ptr() + o for o in call.recv_off], count, dt, bits)
+    torch.cuda.synchronize()
+    pc.check(call, dev.cpu().numpy(), (coll, n_parts, "parts"))
+
+
+def test_ring_parts_beyond_the_inline_ones_go_through_the_workspace(nexr, oracle):
+    """97 parts, one more than flat_premul_kernel's argument block holds (NEXR_FLAT_PREMUL_INLINE_PARTS)."""
+    n_parts = nexr.FLAT_PREMUL_INLINE_PARTS + 1
+    parts = [(4 * k, 4, 4) for k in range(n_parts)]
+    _one_pack_per_part(
+        nexr, oracle, "all_reduce", n_parts,
+        lambda ins, outs, count, dt, bits: nexr.flat_all_reduce_premul(ins, outs, count, dt, bits, False, True, parts),
+        lambda products, count, step: fc.model("all_reduce", products, count, 0,
+                                               lambda x, v, post: step(x, [] if v is None else [v], post), parts))
+
+
+def test_tree_parts_beyond_the_inline_ones_go_through_the_workspace(nexr, oracle):
+    """65 parts, one more than flat_tree_premul_kernel's argument block holds (NEXR_FLAT_TREE_PREMUL_INLINE_PARTS),
+    alternating between the two trees."""
+    n_parts = nexr.FLAT_TREE_PREMUL_INLINE_PARTS + 1
+    trees = [oring.tree_topology(2, rm.tree_per_node(2), t) for t in (0, 1)]
+    parts = [(4 * k, 4, k % 2) for k in range(n_parts)]
+    _one_pack_per_part(
+        nexr, oracle, "tree", n_parts,
+        lambda ins, outs, count, dt, bits: nexr.flat_tree_all_reduce_premul(ins, outs, count, dt, bits, False, True,
+                                                                            trees, parts),
+        lambda products, count, step: ftc.model(products, parts, trees, step))
 
 
 # ---- the other semantics, in a child process ---------------------------------------------------------------------------
