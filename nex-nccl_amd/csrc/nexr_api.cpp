@@ -53,6 +53,53 @@ size_t typeSize(int dt) {
 }
 bool isInteger(int dt) { return dt >= nexrInt8 && dt <= nexrUint64; }
 
+bool typeOpOk(int datatype, int devRedOp, uint64_t redOpArg) {
+  if (datatype < 0 || datatype >= nexrNumTypes) return false;
+  if (datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return false;
+  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return false;
+  // SumPostDiv kernels exist for integer types only (generate.py:108 required_cuda).
+  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return false;
+  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0) {
+    // The signed quotient (taken by bit 0 of redOpArg, whatever the datatype's own signedness:
+    // reduce_kernel.h:79-97) divides by the divisor truncated to T (:94): a divisor that
+    // truncates to 0 would divide by zero. Only a 1-byte T can truncate a non-zero divisor to 0.
+    uint32_t divisor = (uint32_t)(redOpArg >> 1);
+    if (divisor == 0) divisor = 1;
+    if (typeSize(datatype) == 1 && (int8_t)divisor == 0) return false;
+  }
+  return true;
+}
+
+uint64_t pollTicks(uint32_t timeoutUs) {
+  return (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;  // s_memrealtime: 100 MHz
+}
+
+nexrResult_t residentWorkgroups(const ResidentLookup& k, int64_t* resident) {
+  if (const char* e = getenv(k.hook))
+    if (*e) {
+      *resident = strtoll(e, nullptr, 10);
+      return nexrSuccess;
+    }
+  int dev = 0;
+  NEXR_HIP(hipGetDevice(&dev));
+  const bool cached = dev >= 0 && dev < kResidentDevs;
+  if (cached) {
+    const int64_t v = (*k.slot)[dev].load(std::memory_order_relaxed);
+    if (v > 0) {
+      *resident = v;
+      return nexrSuccess;
+    }
+  }
+  int cus = 0, blocks = 0;
+  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  NEXR_HIP(k.blocksPerCu(k.a, k.b, &blocks));
+  if (k.capPerCu && blocks > k.capPerCu) blocks = k.capPerCu;
+  if (k.lessOne && blocks > 1) blocks--;
+  *resident = (int64_t)blocks * cus;
+  if (cached && *resident > 0) (*k.slot)[dev].store(*resident, std::memory_order_relaxed);
+  return nexrSuccess;
+}
+
 long envLong(const char* name, long dflt) {
   const char* v = getenv(name);
   if (!v || !*v) return dflt;
@@ -214,20 +261,7 @@ nexrResult_t validate(int nSrcs, const void* const* srcs, int nDsts, void* const
                       int datatype, int op, uint64_t redOpArg, int nPreOpSrcs, const uint64_t* preOpArgs) {
   if (nSrcs < 1 || nSrcs > NEXR_MAX_SRCS) return nexrInvalidArgument;
   if (nDsts < 0 || nDsts > NEXR_MAX_DSTS) return nexrInvalidArgument;
-  if (datatype < 0 || datatype >= nexrNumTypes) return nexrInvalidArgument;
-  if (datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2) return nexrInvalidArgument;
-  if (op < 0 || op >= nexrNumDevRedOps) return nexrInvalidArgument;
-  // SumPostDiv kernels exist for integer types only (generate.py:108 required_cuda).
-  if (op == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (op == nexrDevSumPostDiv && (redOpArg & 1) != 0) {
-    // The signed quotient (taken by bit 0 of redOpArg, whatever the datatype's own signedness:
-    // reduce_kernel.h:79-97) divides by the divisor truncated to T (:94): a divisor that
-    // truncates to 0 would divide by zero. Only a 1-byte T can truncate a non-zero divisor to 0.
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    size_t sz = typeSize(datatype);
-    if (sz == 1 && (int8_t)divisor == 0) return nexrInvalidArgument;
-  }
+  if (!typeOpOk(datatype, op, redOpArg)) return nexrInvalidArgument;
   if (nPreOpSrcs < 0 || nPreOpSrcs > nSrcs) return nexrInvalidArgument;
   if (nPreOpSrcs > 0 && preOpArgs == nullptr) return nexrInvalidArgument;
   if (nElts == 0 || nDsts == 0) return nexrSuccess;
@@ -1454,790 +1488,6 @@ NEXR_API nexrResult_t nexrLaunchOneRank(void* dst, const void* src, size_t nElts
   const void* prePtr = redOp.scalarArgIsPtr ? (const void*)(uintptr_t)redOp.scalarArg : nullptr;
   return reduceCopyDevice(1, srcs, 1, dsts, nElts, datatype, nexrDevPreMulSum, arg, 1, &arg, prePtr,
                           /*postOp=*/1, s);
-}
-
-NEXR_API nexrResult_t nexrReduceCopyLL(const void* src, int srcIsInput, int nRecv, const void* const* recvLines,
-                                       const uint32_t* recvFlags, void* dst, int nSend, void* const* sendLines,
-                                       const uint32_t* sendFlags, size_t nElts, int datatype, int devRedOp,
-                                       uint64_t redOpArg, int postOp, uint32_t* status, uint32_t timeoutUs,
-                                       nexrStream_t stream) {
-  if (nRecv < 0 || nRecv > NEXR_MAX_SRCS || nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;
-  if (!src && nRecv == 0) return nexrInvalidArgument;   // LLGenericOp needs SRC or RECV
-  if (!dst && nSend == 0) return nexrInvalidArgument;   // ... and DST or SEND
-  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
-    return nexrInvalidArgument;
-  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    if ((int8_t)divisor == 0) return nexrInvalidArgument;
-  }
-  if ((nRecv && (!recvLines || !recvFlags)) || (nSend && (!sendLines || !sendFlags))) return nexrInvalidArgument;
-  if (nElts == 0) return nexrSuccess;
-  LLParams a;
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < nRecv; i++) {
-    if (!recvLines[i] || ((uintptr_t)recvLines[i] & 15)) return nexrInvalidArgument;
-    a.recv[i] = (const char*)recvLines[i];
-    a.recvFlag[i] = recvFlags[i];
-  }
-  for (int i = 0; i < nSend; i++) {
-    if (!sendLines[i] || ((uintptr_t)sendLines[i] & 15)) return nexrInvalidArgument;
-    a.send[i] = (char*)sendLines[i];
-    a.sendFlag[i] = sendFlags[i];
-  }
-  a.src = (const char*)src;
-  a.dst = (char*)dst;
-  a.nElts = nElts;
-  a.redArg = redOpArg;
-  a.status = status;
-  a.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;  // s_memrealtime: 100 MHz
-  a.nRecv = nRecv;
-  a.nSend = nSend;
-  a.srcIsInput = srcIsInput ? 1 : 0;
-  a.postOp = postOp ? 1 : 0;
-  llSemantics(&datatype, &devRedOp, &a.srcIsInput, &a.postOp, &a.firstWins);
-  const uint64_t nLines = (nElts * typeSize(datatype) + 7) / 8;
-  uint64_t grid = (nLines + kLLTileLines - 1) / kLLTileLines;
-  if (grid > (1u << 20)) grid = 1u << 20;
-  NEXR_HIP(launch_ll(datatype, a, devRedOp, (int)grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-// The steps run as if one at a time: a launch's workgroups walk its steps independently, which is
-// only the same when no step touches user bytes that an earlier step of the launch wrote (or, for a
-// write, read) at another element position. The same range at the same position is handled by the
-// same lanes in both steps, in order.
-namespace {
-struct UserRange {
-  uintptr_t beg, end;
-  bool write;
-};
-bool rangesConflict(const std::vector<UserRange>& seen, const UserRange& r) {
-  for (const UserRange& q : seen) {
-    if (!r.write && !q.write) continue;
-    if (r.beg < q.end && q.beg < r.end && !(r.beg == q.beg && r.end == q.end)) return true;
-  }
-  return false;
-}
-}  // namespace
-
-// A flag rule is valid for nSlots slots (include/nexr.h): flagMax 0 or a power of two, cleanMask != 0 and a
-// multiple of nSlots (the reference's static_assert, prims_ll.h), and the cleaning period
-// 2^(msb(cleanMask) + 1) within the flag period, so that every line is rewritten before its flag recurs.
-static bool llRuleValid(const nexrLLFlagRule& r, uint32_t nSlots) {
-  if (r.flagMax & (r.flagMax - 1)) return false;
-  if (r.cleanMask == 0 || nSlots == 0 || r.cleanMask % nSlots) return false;
-  const uint64_t cleanPeriod = 2ull << (31 - __builtin_clz(r.cleanMask));
-  const uint64_t flagPeriod = r.flagMax ? (uint64_t)r.flagMax : 1ull << 32;
-  return cleanPeriod <= flagPeriod;
-}
-
-NEXR_API nexrResult_t nexrReduceCopyLLSteps(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps,
-                                            int datatype, int devRedOp, uint64_t redOpArg, uint32_t* status,
-                                            uint32_t timeoutUs, nexrStream_t stream) {
-  return nexrReduceCopyLLStepsRule(cs, steps, nSteps, datatype, devRedOp, redOpArg, nullptr, status, timeoutUs,
-                                   stream);
-}
-
-// The argument checks of a run of LL steps of one Primitives (nexrReduceCopyLLStepsRule, and every member
-// of nexrReduceCopyLLStepsGroup): nothing here touches the device. rule == nullptr: LL128 steps (every
-// member of nexrReduceCopyLL128StepsGroup), whose slots are whole 2 KiB slices of 1920 data bytes and whose
-// 64-bit flags need no rule.
-static nexrResult_t llStepsValidate(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps, int datatype,
-                                    int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rule) {
-  if (!cs || nSteps < 0 || (nSteps > 0 && !steps)) return nexrInvalidArgument;
-  if (cs->nRecv < 0 || cs->nRecv > NEXR_LL_STEPS_MAX_PEERS || cs->nSend < 0 || cs->nSend > NEXR_LL_STEPS_MAX_PEERS)
-    return nexrInvalidArgument;
-  if (cs->slotBytes == 0 || cs->slotBytes % (rule ? 16 : kLL128SliceBytes) || cs->nSlots == 0) return nexrInvalidArgument;
-  if (cs->nSlots > (uint32_t)INT_MAX) return nexrInvalidArgument;  // the kernels keep it as an int
-  if (rule && !llRuleValid(*rule, cs->nSlots)) return nexrInvalidArgument;
-  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
-    return nexrInvalidArgument;
-  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    if ((int8_t)divisor == 0) return nexrInvalidArgument;
-  }
-  for (int i = 0; i < cs->nRecv; i++)
-    if (!cs->recvFifo[i] || ((uintptr_t)cs->recvFifo[i] & 15) || !cs->recvHead[i] || ((uintptr_t)cs->recvHead[i] & 7))
-      return nexrInvalidArgument;
-  for (int i = 0; i < cs->nSend; i++)
-    if (!cs->sendFifo[i] || ((uintptr_t)cs->sendFifo[i] & 15) || !cs->sendHead[i] || ((uintptr_t)cs->sendHead[i] & 7))
-      return nexrInvalidArgument;
-  const size_t esz = typeSize(datatype);
-  // 8 data bytes per 16-byte line; LL128: 1920 per 2 KiB slice
-  const uint64_t slotData = rule ? cs->slotBytes / 2 : cs->slotBytes / kLL128SliceBytes * kLL128SliceData;
-  for (int k = 0; k < nSteps; k++) {
-    const nexrLLStep& s = steps[k];
-    if (s.srcBuf < -1 || s.srcBuf > 1 || s.dstBuf < -1 || s.dstBuf > 1) return nexrInvalidArgument;
-    if ((s.recv && cs->nRecv == 0) || (s.send && cs->nSend == 0)) return nexrInvalidArgument;
-    if ((s.srcBuf == 0 && !cs->input) || (s.srcBuf == 1 && !cs->output) || (s.dstBuf == 0 && !cs->input) ||
-        (s.dstBuf == 1 && !cs->output))
-      return nexrInvalidArgument;
-    if (s.srcIx < 0 || s.dstIx < 0) return nexrInvalidArgument;
-    if (s.nElts == 0) continue;
-    if ((s.srcBuf < 0 && !s.recv) || (s.dstBuf < 0 && !s.send)) return nexrInvalidArgument;
-    if ((s.recv || s.send) && (uint64_t)s.nElts * esz > slotData) return nexrInvalidArgument;
-  }
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrReduceCopyLLStepsRule(const nexrLLConnSet* cs, const nexrLLStep* steps, int nSteps,
-                                                int datatype, int devRedOp, uint64_t redOpArg,
-                                                const nexrLLFlagRule* rulePtr, uint32_t* status, uint32_t timeoutUs,
-                                                nexrStream_t stream) {
-  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
-  const nexrResult_t valid = llStepsValidate(cs, steps, nSteps, datatype, devRedOp, redOpArg, &rule);
-  if (valid != nexrSuccess) return valid;
-  if (nSteps == 0) return nexrSuccess;
-  const size_t esz = typeSize(datatype);
-  int srcIsInput = 1, postOp = 1;
-  LLStepsParams P;
-  memset(&P, 0, sizeof(P));
-  llSemantics(&datatype, &devRedOp, &srcIsInput, &postOp, &P.firstWins);
-  P.input = (const char*)cs->input;
-  P.output = (char*)cs->output;
-  for (int i = 0; i < NEXR_LL_STEPS_MAX_PEERS; i++) {
-    P.recvFifo[i] = (const char*)cs->recvFifo[i];
-    P.recvHead[i] = cs->recvHead[i];
-    P.sendFifo[i] = (char*)cs->sendFifo[i];
-    P.sendHead[i] = cs->sendHead[i];
-  }
-  P.slotBytes = cs->slotBytes;
-  P.redArg = redOpArg;
-  P.status = status;
-  P.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;
-  P.nRecv = cs->nRecv;
-  P.nSend = cs->nSend;
-  P.nSlots = (int)cs->nSlots;
-  P.flagMask = rule.flagMax ? rule.flagMax - 1 : 0xffffffffu;
-  // One workgroup per line tile of a full slot (the same grid on both ends of every connection).
-  const uint64_t slotTiles = (cs->slotBytes / 16 + kLLTileLines - 1) / kLLTileLines;
-  const int grid = (int)(slotTiles < 1 ? 1 : slotTiles > (uint64_t)kLLStepsMaxGrid ? kLLStepsMaxGrid : slotTiles);
-  uint64_t rs[NEXR_LL_STEPS_MAX_PEERS], ss[NEXR_LL_STEPS_MAX_PEERS];
-  for (int i = 0; i < NEXR_LL_STEPS_MAX_PEERS; i++) rs[i] = cs->recvStep[i], ss[i] = cs->sendStep[i];
-  std::vector<UserRange> seen;
-  auto launch = [&]() -> nexrResult_t {
-    if (P.nSteps == 0) return nexrSuccess;
-    NEXR_HIP(launch_ll_steps(datatype, P, devRedOp, grid, (hipStream_t)stream));
-    P.nSteps = 0;
-    seen.clear();
-    return nexrSuccess;
-  };
-  for (int k = 0; k < nSteps; k++) {
-    const nexrLLStep& s = steps[k];
-    UserRange rd{0, 0, false}, wr{0, 0, true};
-    if (s.nElts && s.srcBuf >= 0) {
-      rd.beg = (uintptr_t)(s.srcBuf == 0 ? cs->input : cs->output) + (uintptr_t)s.srcIx * esz;
-      rd.end = rd.beg + (uintptr_t)s.nElts * esz;
-    }
-    if (s.nElts && s.dstBuf >= 0) {
-      wr.beg = (uintptr_t)(s.dstBuf == 0 ? cs->input : cs->output) + (uintptr_t)s.dstIx * esz;
-      wr.end = wr.beg + (uintptr_t)s.nElts * esz;
-    }
-    if (P.nSteps == kLLStepsMax || (rd.end && rangesConflict(seen, rd)) || (wr.end && rangesConflict(seen, wr))) {
-      nexrResult_t r = launch();
-      if (r != nexrSuccess) return r;
-    }
-    if (P.nSteps == 0)
-      for (int i = 0; i < NEXR_LL_STEPS_MAX_PEERS; i++) P.recvStep[i] = rs[i], P.sendStep[i] = ss[i];
-    P.step[P.nSteps++] = s;
-    if (rd.end) seen.push_back(rd);
-    if (wr.end) seen.push_back(wr);
-    // incSend's cleanup (prims_ll.h:85-93): a send step whose counter has every bit of the mask set cleans
-    // its slot, per send connection. The launch ends at such a step and its kernel cleans after its last
-    // step (nexr_ll.hip), so the step loop itself carries nothing for it.
-    uint32_t cleans = 0;
-    if (s.send)
-      for (int j = 0; j < cs->nSend; j++)
-        if (((uint32_t)ss[j] & rule.cleanMask) == rule.cleanMask) {
-          cleans |= 1u << j;
-          P.cleanStep[j] = ss[j];
-        }
-    if (s.recv)
-      for (uint64_t& v : rs) v++;
-    if (s.send)
-      for (uint64_t& v : ss) v++;
-    if (cleans) {
-      P.cleanLast = cleans;
-      nexrResult_t r = launch();
-      P.cleanLast = 0;
-      if (r != nexrSuccess) return r;
-    }
-  }
-  return launch();
-}
-
-// ---- nexrReduceCopyLLStepsGroup: the runs of several Primitives in one launch ------------------------
-// Three things make a group launch finish: its grid is resident as a whole (the occupancy
-// check below), it needs nothing a later launch would produce (the dry run), and every poll of its
-// kernel is bounded (nexr_ll.hip).
-NEXR_API nexrResult_t nexrLLGroupWorkspaceBytes(int nMembers, size_t* bytes) {
-  if (!bytes || nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS) return nexrInvalidArgument;
-  *bytes = (size_t)nMembers * kLLGroupEntryBytes * NEXR_LL_GROUP_LAUNCHES;
-  return nexrSuccess;
-}
-
-namespace {
-// Workgroups of the group kernel the current device keeps resident (blocks per CU x CUs), looked up once
-// per (device, datatype, op).
-// Test hook: NEXR_TEST_LL_GROUP_RESIDENT=k makes the next calls take k as that number, so that the
-// rejection of a grid that does not fit (and the ring's fall-back) can be tested on a GPU that fits it.
-// Read per call (tests set it between calls).
-nexrResult_t llGroupResident(bool ll128, int dt, int op, int64_t* resident) {
-  if (const char* e = getenv("NEXR_TEST_LL_GROUP_RESIDENT"))
-    if (*e) {
-      *resident = strtoll(e, nullptr, 10);
-      return nexrSuccess;
-    }
-  constexpr int kDevs = 16;
-  static std::atomic<int64_t> cache[2][kDevs][nexrNumTypes][nexrNumDevRedOps];  // [LL, LL128]: a kernel each
-  int dev = 0;
-  NEXR_HIP(hipGetDevice(&dev));
-  const bool cached = dev >= 0 && dev < kDevs;
-  if (cached) {
-    const int64_t v = cache[ll128][dev][dt][op].load(std::memory_order_relaxed);
-    if (v > 0) {
-      *resident = v;
-      return nexrSuccess;
-    }
-  }
-  int cus = 0, blocks = 0;
-  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  NEXR_HIP(ll128 ? ll128_group_blocks_per_cu(dt, op, &blocks) : ll_group_blocks_per_cu(dt, op, &blocks));
-  *resident = (int64_t)blocks * cus;
-  if (cached && *resident > 0) cache[ll128][dev][dt][op].store(*resident, std::memory_order_relaxed);
-  return nexrSuccess;
-}
-
-// The planner of the group calls (LL, LL128 and SIMPLE step lists), from the members' parameter blocks `cur`
-// as they stand at the call's counters with no steps yet: the launch cuts, the dry run, the workspace and
-// residency checks, the one copy of the tables and the launches. A recv / send step advances a
-// connection's counters by `adv` (1, or SIMPLE's stepPerSlice) and a slot is free again nSlots steps later.
-// rule: the LL flag rule, whose cleaning steps end a launch (nullptr: none).
-extern "C++" {
-// directRd(member, record): a further user range the record reads (a SIMPLE direct receive reads the member's
-// output at dstIx), end == 0 for none.
-template <typename Params, typename ResidentFn, typename LaunchFn, typename DirectRdFn>
-nexrResult_t stepsGroupPlan(int nMembers, std::vector<Params>& cur, const nexrLLStep* const* steps, const int* nSteps,
-                            int maxSteps, size_t esz, uint64_t adv, uint64_t nSlots, const nexrLLFlagRule* rule, int G,
-                            ResidentFn residentFn, LaunchFn launchFn, DirectRdFn directRd, void* workspace,
-                            size_t workspaceBytes, nexrStream_t stream) {
-  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
-  std::vector<Params> table;
-  std::vector<std::vector<UserRange>> seen((size_t)nMembers);
-  auto cut = [&]() {  // the launch is complete: its blocks go into the table, the next one starts at the counters
-    for (int m = 0; m < nMembers; m++) {
-      Params& P = cur[(size_t)m];
-      table.push_back(P);
-      for (int k = 0; k < P.nSteps; k++) {
-        const nexrLLStep& s = P.step[k];
-        for (int i = 0; i < MP; i++) P.recvStep[i] += s.recv ? adv : 0, P.sendStep[i] += s.send ? adv : 0;
-      }
-      P.nSteps = 0;
-      if constexpr (std::is_same<Params, LLStepsParams>::value) P.cleanLast = 0;
-      seen[(size_t)m].clear();
-    }
-  };
-  int inLaunch = 0;  // step indices in the current launch
-  for (int k = 0; k < maxSteps; k++) {
-    bool before = inLaunch == kLLStepsMax, cleans = false;
-    std::vector<UserRange> rd((size_t)nMembers, UserRange{0, 0, false}), wr((size_t)nMembers, UserRange{0, 0, true});
-    std::vector<UserRange> rd2((size_t)nMembers, UserRange{0, 0, false});
-    for (int m = 0; m < nMembers; m++) {
-      if (k >= nSteps[m]) continue;
-      const nexrLLStep& s = steps[m][k];
-      const Params& cs = cur[(size_t)m];
-      rd2[(size_t)m] = directRd(m, s);
-      if (s.nElts && s.srcBuf >= 0) {
-        rd[(size_t)m].beg = (uintptr_t)(s.srcBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.srcIx * esz;
-        rd[(size_t)m].end = rd[(size_t)m].beg + (uintptr_t)s.nElts * esz;
-      }
-      if (s.nElts && s.dstBuf >= 0) {
-        wr[(size_t)m].beg = (uintptr_t)(s.dstBuf == 0 ? cs.input : cs.output) + (uintptr_t)s.dstIx * esz;
-        wr[(size_t)m].end = wr[(size_t)m].beg + (uintptr_t)s.nElts * esz;
-      }
-      before = before || (rd[(size_t)m].end && rangesConflict(seen[(size_t)m], rd[(size_t)m])) ||
-               (rd2[(size_t)m].end && rangesConflict(seen[(size_t)m], rd2[(size_t)m])) ||
-               (wr[(size_t)m].end && rangesConflict(seen[(size_t)m], wr[(size_t)m]));
-    }
-    if (before && inLaunch) {
-      cut();
-      inLaunch = 0;
-    }
-    for (int m = 0; m < nMembers; m++) {
-      if (k >= nSteps[m]) continue;
-      const nexrLLStep& s = steps[m][k];
-      Params& P = cur[(size_t)m];
-      // the member's send counters at this step: those of the launch's start plus its send steps so far
-      uint64_t sent = 0;
-      for (int q = 0; q < P.nSteps; q++) sent += P.step[q].send ? 1 : 0;
-      P.step[P.nSteps++] = s;
-      if (rd[(size_t)m].end) seen[(size_t)m].push_back(rd[(size_t)m]);
-      if (rd2[(size_t)m].end) seen[(size_t)m].push_back(rd2[(size_t)m]);
-      if (wr[(size_t)m].end) seen[(size_t)m].push_back(wr[(size_t)m]);
-      if constexpr (std::is_same<Params, LLStepsParams>::value) {
-        if (s.send && rule)
-          for (int j = 0; j < P.nSend; j++) {
-            const uint64_t ss = P.sendStep[j] + sent;
-            if (((uint32_t)ss & rule->cleanMask) == rule->cleanMask) {
-              P.cleanLast |= 1u << j;
-              P.cleanStep[j] = ss;
-              cleans = true;
-            }
-          }
-      }
-    }
-    inLaunch++;
-    if (cleans) {
-      cut();
-      inLaunch = 0;
-    }
-  }
-  if (inLaunch) cut();
-  const size_t nLaunches = table.size() / (size_t)nMembers;
-
-  // The dry run: every launch must finish with what it and the launches before it produce, because the
-  // next one starts only behind it on the stream. Connections whose FIFO is some member's send FIFO and
-  // another's receive FIFO are internal: their data and credit counters are walked here; the others are
-  // taken as always ready (their peer runs elsewhere).
-  struct Link {
-    uint64_t sent, read;
-  };
-  std::vector<Link> links;
-  std::vector<int> sendLink((size_t)nMembers * MP, -1), recvLink((size_t)nMembers * MP, -1);
-  const Params* first = table.data();  // the first launch's blocks: the connections at the call's counters
-  for (int m = 0; m < nMembers; m++)
-    for (int j = 0; j < first[m].nSend; j++)
-      for (int r = 0; r < nMembers && sendLink[(size_t)m * MP + j] < 0; r++)
-        for (int i = 0; i < first[r].nRecv; i++)
-          if ((const void*)first[r].recvFifo[i] == (const void*)first[m].sendFifo[j] &&
-              recvLink[(size_t)r * MP + i] < 0) {
-            if (first[m].sendStep[j] < first[r].recvStep[i]) return nexrInvalidUsage;  // more read than sent
-            sendLink[(size_t)m * MP + j] = recvLink[(size_t)r * MP + i] = (int)links.size();
-            links.push_back(Link{first[m].sendStep[j], first[r].recvStep[i]});
-            break;
-          }
-  std::vector<int> pos((size_t)nMembers);
-  for (size_t l = 0; l < nLaunches; l++) {
-    const Params* L = &table[l * (size_t)nMembers];
-    std::fill(pos.begin(), pos.end(), 0);
-    for (bool progress = true; progress;) {
-      progress = false;
-      for (int m = 0; m < nMembers; m++) {
-        while (pos[(size_t)m] < L[m].nSteps) {
-          const nexrLLStep& s = L[m].step[pos[(size_t)m]];
-          bool ready = true;
-          for (int i = 0; s.recv && i < L[m].nRecv; i++) {  // the line flags: the sender has written the step
-            const int id = recvLink[(size_t)m * MP + i];
-            if (id >= 0 && links[(size_t)id].sent < links[(size_t)id].read + adv) ready = false;
-          }
-          for (int j = 0; s.send && j < L[m].nSend; j++) {  // waitSend: the step nSlots back has been read
-            const int id = sendLink[(size_t)m * MP + j];
-            if (id >= 0 && links[(size_t)id].sent + adv > links[(size_t)id].read + nSlots) ready = false;
-          }
-          if (!ready) break;
-          for (int i = 0; s.recv && i < L[m].nRecv; i++)
-            if (recvLink[(size_t)m * MP + i] >= 0) links[(size_t)recvLink[(size_t)m * MP + i]].read += adv;
-          for (int j = 0; s.send && j < L[m].nSend; j++)
-            if (sendLink[(size_t)m * MP + j] >= 0) links[(size_t)sendLink[(size_t)m * MP + j]].sent += adv;
-          pos[(size_t)m]++;
-          progress = true;
-        }
-      }
-    }
-    for (int m = 0; m < nMembers; m++)
-      if (pos[(size_t)m] < L[m].nSteps) return nexrInvalidUsage;  // this launch would wait for a later one
-  }
-
-  // One region of the workspace per launch: a table is never written while a queued launch may read it.
-  if (workspaceBytes / sizeof(Params) / (size_t)nMembers < nLaunches) return nexrInvalidArgument;
-
-  // Co-residency: all nMembers * G workgroups at once, or a poll could wait for a workgroup that has no CU.
-  int64_t resident = 0;
-  const nexrResult_t occ = residentFn(&resident);
-  if (occ != nexrSuccess) return occ;
-  if ((int64_t)nMembers * G > resident) return nexrInvalidUsage;
-
-  // Pageable source: the runtime has staged it when the call returns, so `table` may go out of scope.
-  NEXR_HIP(hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(Params), hipMemcpyHostToDevice,
-                          (hipStream_t)stream));
-  for (size_t l = 0; l < nLaunches; l++) NEXR_HIP(launchFn((const Params*)workspace + l * (size_t)nMembers));
-  return nexrSuccess;
-}
-}  // extern "C++"
-
-// The host side of both group calls: the argument checks, the launch cuts, the dry run, the workspace and
-// residency checks, the one copy of the tables and the launches. rule == nullptr: LL128 steps
-// (nexrReduceCopyLL128StepsGroup), which have no cleaning steps (so no cut behind one), slots counted in
-// 2 KiB slices and a kernel (and so an occupancy) of their own; everything else is the same code.
-nexrResult_t llStepsGroup(int nMembers, const nexrLLConnSet* conns, const nexrLLStep* const* steps, const int* nSteps,
-                          int datatype, int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rule, uint32_t* status,
-                          uint32_t timeoutUs, void* workspace, size_t workspaceBytes, nexrStream_t stream) {
-  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
-  const bool ll128 = rule == nullptr;
-  if (nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || !conns || !steps || !nSteps) return nexrInvalidArgument;
-  int maxSteps = 0;
-  for (int m = 0; m < nMembers; m++) {
-    const nexrResult_t valid = llStepsValidate(&conns[m], steps[m], nSteps[m], datatype, devRedOp, redOpArg, rule);
-    if (valid != nexrSuccess) return valid;
-    // one G (a workgroup per line tile of a slot) and one credit window serve the launch
-    if (conns[m].slotBytes != conns[0].slotBytes || conns[m].nSlots != conns[0].nSlots) return nexrInvalidArgument;
-    maxSteps = std::max(maxSteps, nSteps[m]);
-  }
-  if (maxSteps == 0) return nexrSuccess;
-  if (!workspace || ((uintptr_t)workspace & 7)) return nexrInvalidArgument;
-  const size_t esz = typeSize(datatype);
-  const uint64_t nSlots = conns[0].nSlots;
-  int srcIsInput = 1, postOp = 1, firstWins = 0;
-  llSemantics(&datatype, &devRedOp, &srcIsInput, &postOp, &firstWins);
-
-  // The launches. A cut applies to every member at the same step index: before a step that would be a
-  // member's 97th of the launch or that conflicts with user bytes the member touched earlier in it
-  // (rangesConflict), and behind a step that cleans on any member (the kernel cleans behind a member's
-  // last step). Entry (launch l, member m) of the table is that member's parameter block of launch l.
-  std::vector<LLStepsParams> cur((size_t)nMembers);
-  for (int m = 0; m < nMembers; m++) {
-    const nexrLLConnSet& cs = conns[m];
-    LLStepsParams& P = cur[(size_t)m];
-    memset(&P, 0, sizeof(P));
-    P.input = (const char*)cs.input;
-    P.output = (char*)cs.output;
-    for (int i = 0; i < MP; i++) {
-      P.recvFifo[i] = (const char*)cs.recvFifo[i];
-      P.recvHead[i] = cs.recvHead[i];
-      P.sendFifo[i] = (char*)cs.sendFifo[i];
-      P.sendHead[i] = cs.sendHead[i];
-      P.recvStep[i] = cs.recvStep[i];
-      P.sendStep[i] = cs.sendStep[i];
-    }
-    P.slotBytes = cs.slotBytes;
-    P.redArg = redOpArg;
-    P.status = status;
-    P.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;
-    P.nRecv = cs.nRecv;
-    P.nSend = cs.nSend;
-    P.nSlots = (int)cs.nSlots;
-    P.firstWins = firstWins;
-    P.flagMask = rule && rule->flagMax ? rule->flagMax - 1 : 0xffffffffu;
-  }
-  // (a workgroup per tile of a slot: kLLTileLines 16-byte lines, or kLL128TileUnits 16-byte wire units)
-  const uint64_t tileUnits = ll128 ? kLL128TileUnits : kLLTileLines;
-  const uint64_t slotTiles = (conns[0].slotBytes / 16 + tileUnits - 1) / tileUnits;
-  const int G = (int)(slotTiles < 1 ? 1 : slotTiles > (uint64_t)kLLStepsMaxGrid ? kLLStepsMaxGrid : slotTiles);
-  return stepsGroupPlan(
-      nMembers, cur, steps, nSteps, maxSteps, esz, 1, nSlots, rule, G,
-      [&](int64_t* resident) { return llGroupResident(ll128, datatype, devRedOp, resident); },
-      [&](const LLStepsParams* entries) {
-        return ll128 ? launch_ll128_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream)
-                     : launch_ll_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
-      },
-      [](int, const nexrLLStep&) { return UserRange{0, 0, false}; }, workspace, workspaceBytes, stream);
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrReduceCopyLLStepsGroup(int nMembers, const nexrLLConnSet* conns,
-                                                 const nexrLLStep* const* steps, const int* nSteps, int datatype,
-                                                 int devRedOp, uint64_t redOpArg, const nexrLLFlagRule* rulePtr,
-                                                 uint32_t* status, uint32_t timeoutUs, void* workspace,
-                                                 size_t workspaceBytes, nexrStream_t stream) {
-  const nexrLLFlagRule rule = rulePtr ? *rulePtr : nexrLLFlagRule{0u, 0x7ffffff8u};  // NULL: the production rule
-  return llStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, &rule, status, timeoutUs,
-                      workspace, workspaceBytes, stream);
-}
-
-NEXR_API nexrResult_t nexrReduceCopyLL128StepsGroup(int nMembers, const nexrLLConnSet* conns,
-                                                    const nexrLLStep* const* steps, const int* nSteps, int datatype,
-                                                    int devRedOp, uint64_t redOpArg, uint32_t* status,
-                                                    uint32_t timeoutUs, void* workspace, size_t workspaceBytes,
-                                                    nexrStream_t stream) {
-  return llStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, nullptr, status, timeoutUs,
-                      workspace, workspaceBytes, stream);
-}
-
-// ---- nexrReduceCopySimpleStepsGroup: SIMPLE step lists of several Primitives in one launch ------------
-NEXR_API nexrResult_t nexrSimpleGroupWorkspaceBytes(int nMembers, size_t* bytes) {
-  if (!bytes || nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS) return nexrInvalidArgument;
-  *bytes = (size_t)nMembers * sizeof(SimpleStepsParams) * NEXR_LL_GROUP_LAUNCHES;
-  return nexrSuccess;
-}
-
-namespace {
-// Workgroups of the SIMPLE group kernel the current device keeps resident, as llGroupResident. The
-// hardware admits 256-thread workgroups by their scalar registers too, and for kernels that use more than
-// 80 of them one fewer per CU than the occupancy query says; a surplus workgroup would queue until a
-// resident one exits, which a poll may be waiting for. So one is taken off the query's answer.
-// Test hook: NEXR_TEST_SIMPLE_GROUP_RESIDENT=k makes the next calls take k as that number (read per call).
-// direct: the kernel variant of nexrReduceCopySimpleStepsGroupDirect (the one that is launched is queried).
-nexrResult_t simpleGroupResident(bool direct, int dt, int op, int64_t* resident) {
-  if (const char* e = getenv("NEXR_TEST_SIMPLE_GROUP_RESIDENT"))
-    if (*e) {
-      *resident = strtoll(e, nullptr, 10);
-      return nexrSuccess;
-    }
-  constexpr int kDevs = 16;
-  static std::atomic<int64_t> cache[2][kDevs][nexrNumTypes][nexrNumDevRedOps];  // [FIFO-only, direct]
-  int dev = 0;
-  NEXR_HIP(hipGetDevice(&dev));
-  const bool cached = dev >= 0 && dev < kDevs;
-  if (cached) {
-    const int64_t v = cache[direct][dev][dt][op].load(std::memory_order_relaxed);
-    if (v > 0) {
-      *resident = v;
-      return nexrSuccess;
-    }
-  }
-  int cus = 0, blocks = 0;
-  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  NEXR_HIP(direct ? simple_group_direct_blocks_per_cu(dt, op, &blocks) : simple_group_blocks_per_cu(dt, op, &blocks));
-  if (blocks > 8) blocks = 8;
-  if (blocks > 1) blocks--;
-  *resident = (int64_t)blocks * cus;
-  if (cached && *resident > 0) cache[direct][dev][dt][op].store(*resident, std::memory_order_relaxed);
-  return nexrSuccess;
-}
-
-// The host side of both SIMPLE group calls. direct == nullptr: nexrReduceCopySimpleStepsGroup, the FIFO-only
-// kernels and their table entry; else one nexrSimpleDirectSet per member, the direct kernels and theirs.
-nexrResult_t simpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns, const nexrLLStep* const* steps,
-                              const int* nSteps, int datatype, int devRedOp, uint64_t redOpArg,
-                              int workgroupsPerMember, const nexrSimpleDirectSet* direct, uint32_t* status,
-                              uint32_t timeoutUs, void* workspace, size_t workspaceBytes, nexrStream_t stream) {
-  constexpr int MP = NEXR_LL_STEPS_MAX_PEERS;
-  if (nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS || !conns || !steps || !nSteps) return nexrInvalidArgument;
-  if (workgroupsPerMember < 0 || workgroupsPerMember > NEXR_SIMPLE_GROUP_MAX_GRID) return nexrInvalidArgument;
-  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
-    return nexrInvalidArgument;
-  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    if ((int8_t)divisor == 0) return nexrInvalidArgument;
-  }
-  const size_t esz = typeSize(datatype);
-  int maxSteps = 0;
-  for (int m = 0; m < nMembers; m++) {
-    const nexrSimpleConnSet& cs = conns[m];
-    if (nSteps[m] < 0 || (nSteps[m] > 0 && !steps[m])) return nexrInvalidArgument;
-    if (cs.nRecv < 0 || cs.nRecv > MP || cs.nSend < 0 || cs.nSend > MP) return nexrInvalidArgument;
-    if (cs.slotBytes == 0 || cs.slotBytes % 16 || cs.nSlots == 0 || cs.nSlots > (uint32_t)INT_MAX)
-      return nexrInvalidArgument;
-    if (cs.stepPerSlice < 1 || cs.nSlots % cs.stepPerSlice) return nexrInvalidArgument;
-    // one G, one credit window and one slice size serve the launch
-    if (cs.slotBytes != conns[0].slotBytes || cs.nSlots != conns[0].nSlots || cs.stepPerSlice != conns[0].stepPerSlice)
-      return nexrInvalidArgument;
-    for (int i = 0; i < cs.nRecv; i++)
-      if (!cs.recvFifo[i] || ((uintptr_t)cs.recvFifo[i] & 15) || !cs.recvTail[i] || ((uintptr_t)cs.recvTail[i] & 7) ||
-          !cs.recvHead[i] || ((uintptr_t)cs.recvHead[i] & 7) || cs.recvStep[i] % cs.stepPerSlice)
-        return nexrInvalidArgument;
-    for (int i = 0; i < cs.nSend; i++)
-      if (!cs.sendFifo[i] || ((uintptr_t)cs.sendFifo[i] & 15) || !cs.sendTail[i] || ((uintptr_t)cs.sendTail[i] & 7) ||
-          !cs.sendHead[i] || ((uintptr_t)cs.sendHead[i] & 7) || cs.sendStep[i] % cs.stepPerSlice)
-        return nexrInvalidArgument;
-    const uint64_t sliceBytes = cs.slotBytes * cs.stepPerSlice;
-    for (int k = 0; k < nSteps[m]; k++) {
-      const nexrLLStep& s = steps[m][k];
-      if (s.srcBuf < -1 || s.srcBuf > 1 || s.dstBuf < -1 || s.dstBuf > 1) return nexrInvalidArgument;
-      if ((s.recv && cs.nRecv == 0) || (s.send && cs.nSend == 0)) return nexrInvalidArgument;
-      if ((s.srcBuf == 0 && !cs.input) || (s.srcBuf == 1 && !cs.output) || (s.dstBuf == 0 && !cs.input) ||
-          (s.dstBuf == 1 && !cs.output))
-        return nexrInvalidArgument;
-      if (s.srcIx < 0 || s.dstIx < 0) return nexrInvalidArgument;
-      if (s.nElts == 0) continue;
-      if ((s.srcBuf < 0 && !s.recv) || (s.dstBuf < 0 && !s.send)) return nexrInvalidArgument;
-      if ((uint64_t)s.nElts * esz > sliceBytes) return nexrInvalidArgument;
-    }
-    maxSteps = std::max(maxSteps, nSteps[m]);
-  }
-  if (direct) {
-    // Only one receive may be direct (prims_simple.h:262), and its source is the member's output.
-    for (int m = 0; m < nMembers; m++) {
-      bool any = false;
-      for (int i = 0; i < MP; i++) any = any || direct[m].recvDirect[i] != 0;
-      if (any && (conns[m].nRecv != 1 || !direct[m].recvDirect[0] || !conns[m].output)) return nexrInvalidArgument;
-    }
-    // A connection between two members is direct on both ends or on neither, into the receiver's output.
-    for (int m = 0; m < nMembers; m++)
-      for (int j = 0; j < conns[m].nSend; j++)
-        for (int r = 0; r < nMembers; r++)
-          for (int i = 0; i < conns[r].nRecv; i++) {
-            if (conns[r].recvFifo[i] != conns[m].sendFifo[j]) continue;
-            const void* sd = direct[m].sendDirect[j];
-            if ((sd != nullptr) != (direct[r].recvDirect[i] != 0)) return nexrInvalidArgument;
-            if (sd && sd != conns[r].output) return nexrInvalidArgument;
-          }
-  }
-  if (maxSteps == 0) return nexrSuccess;
-  if (!workspace || ((uintptr_t)workspace & 7)) return nexrInvalidArgument;
-  const uint64_t sps = conns[0].stepPerSlice;
-  int srcIsInput = 1, postOp = 1, firstWins = 0;
-  llSemantics(&datatype, &devRedOp, &srcIsInput, &postOp, &firstWins);  // fork: the dispatch type; shipped: source 0
-  // A workgroup per 4 KiB tile of a full slice unless the caller says how many.
-  const uint64_t sliceTiles = (conns[0].slotBytes * sps + kSimpleTileBytes - 1) / kSimpleTileBytes;
-  const int G = workgroupsPerMember ? workgroupsPerMember
-                                    : (int)(sliceTiles > (uint64_t)kSimpleMaxGrid ? kSimpleMaxGrid : sliceTiles);
-  auto fill = [&](SimpleStepsParams& P, const nexrSimpleConnSet& cs) {
-    P.input = (const char*)cs.input;
-    P.output = (char*)cs.output;
-    for (int i = 0; i < MP; i++) {
-      P.recvFifo[i] = (const char*)cs.recvFifo[i];
-      P.recvTail[i] = cs.recvTail[i];
-      P.recvHead[i] = cs.recvHead[i];
-      P.sendFifo[i] = (char*)cs.sendFifo[i];
-      P.sendTail[i] = cs.sendTail[i];
-      P.sendHead[i] = cs.sendHead[i];
-      P.recvStep[i] = cs.recvStep[i];
-      P.sendStep[i] = cs.sendStep[i];
-    }
-    P.slotBytes = cs.slotBytes;
-    P.redArg = redOpArg;
-    P.status = status;
-    P.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;
-    P.nRecv = cs.nRecv;
-    P.nSend = cs.nSend;
-    P.nSlots = (int)cs.nSlots;
-    P.firstWins = firstWins;
-    P.stepPerSlice = (int)cs.stepPerSlice;
-  };
-  if (direct) {
-    std::vector<SimpleDirectParams> cur((size_t)nMembers);
-    for (int m = 0; m < nMembers; m++) {
-      SimpleDirectParams& P = cur[(size_t)m];
-      memset((void*)&P, 0, sizeof(P));
-      fill(P, conns[m]);
-      for (int j = 0; j < conns[m].nSend; j++) P.sendDirect[j] = (char*)direct[m].sendDirect[j];
-      P.recvDirect = direct[m].recvDirect[0] ? 1 : 0;
-    }
-    return stepsGroupPlan(
-        nMembers, cur, steps, nSteps, maxSteps, esz, sps, conns[0].nSlots, nullptr, G,
-        [&](int64_t* resident) { return simpleGroupResident(true, datatype, devRedOp, resident); },
-        [&](const SimpleDirectParams* entries) {
-          return launch_simple_group_direct(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
-        },
-        [&](int m, const nexrLLStep& st) {  // a direct source: the member's output at dstIx
-          UserRange rd{0, 0, false};
-          if (st.nElts && st.recv && (st.pad[0] & NEXR_SIMPLE_DIRECT_RECV) && direct[m].recvDirect[0]) {
-            rd.beg = (uintptr_t)conns[m].output + (uintptr_t)st.dstIx * esz;
-            rd.end = rd.beg + (uintptr_t)st.nElts * esz;
-          }
-          return rd;
-        },
-        workspace, workspaceBytes, stream);
-  }
-  std::vector<SimpleStepsParams> cur((size_t)nMembers);
-  for (int m = 0; m < nMembers; m++) {
-    memset(&cur[(size_t)m], 0, sizeof(SimpleStepsParams));
-    fill(cur[(size_t)m], conns[m]);
-  }
-  return stepsGroupPlan(
-      nMembers, cur, steps, nSteps, maxSteps, esz, sps, conns[0].nSlots, nullptr, G,
-      [&](int64_t* resident) { return simpleGroupResident(false, datatype, devRedOp, resident); },
-      [&](const SimpleStepsParams* entries) {
-        return launch_simple_group(datatype, devRedOp, entries, nMembers, G, (hipStream_t)stream);
-      },
-      [](int, const nexrLLStep&) { return UserRange{0, 0, false}; }, workspace, workspaceBytes, stream);
-}
-}  // namespace
-
-NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroup(int nMembers, const nexrSimpleConnSet* conns,
-                                                     const nexrLLStep* const* steps, const int* nSteps, int datatype,
-                                                     int devRedOp, uint64_t redOpArg, int workgroupsPerMember,
-                                                     uint32_t* status, uint32_t timeoutUs, void* workspace,
-                                                     size_t workspaceBytes, nexrStream_t stream) {
-  return simpleStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, workgroupsPerMember, nullptr,
-                          status, timeoutUs, workspace, workspaceBytes, stream);
-}
-
-NEXR_API nexrResult_t nexrSimpleGroupDirectWorkspaceBytes(int nMembers, size_t* bytes) {
-  if (!bytes || nMembers < 1 || nMembers > NEXR_LL_GROUP_MAX_MEMBERS) return nexrInvalidArgument;
-  *bytes = (size_t)nMembers * sizeof(SimpleDirectParams) * NEXR_LL_GROUP_LAUNCHES;
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrReduceCopySimpleStepsGroupDirect(int nMembers, const nexrSimpleConnSet* conns,
-                                                           const nexrLLStep* const* steps, const int* nSteps,
-                                                           int datatype, int devRedOp, uint64_t redOpArg,
-                                                           int workgroupsPerMember, const nexrSimpleDirectSet* direct,
-                                                           uint32_t* status, uint32_t timeoutUs, void* workspace,
-                                                           size_t workspaceBytes, nexrStream_t stream) {
-  return simpleStepsGroup(nMembers, conns, steps, nSteps, datatype, devRedOp, redOpArg, workgroupsPerMember, direct,
-                          status, timeoutUs, workspace, workspaceBytes, stream);
-}
-
-NEXR_API nexrResult_t nexrLLCleanSlot(int nSend, void* const* sendLines, const uint32_t* sendFlags, size_t firstLine,
-                                      size_t slotLines, nexrStream_t stream) {
-  if (nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;
-  if (nSend && (!sendLines || !sendFlags)) return nexrInvalidArgument;
-  LLCleanParams a;
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < nSend; i++) {
-    if (!sendLines[i] || ((uintptr_t)sendLines[i] & 15)) return nexrInvalidArgument;
-    a.send[i] = (char*)sendLines[i];
-    a.flag[i] = sendFlags[i];
-  }
-  if (nSend == 0 || firstLine >= slotLines) return nexrSuccess;
-  a.firstLine = firstLine;
-  a.slotLines = slotLines;
-  a.nSend = nSend;
-  // One workgroup per line tile from the first one that holds a clean line (the kernel skips those before it).
-  const uint64_t slotTiles = (slotLines + kLLTileLines - 1) / kLLTileLines;
-  uint64_t grid = slotTiles - firstLine / kLLTileLines;
-  if (grid > 1024) grid = 1024;
-  NEXR_HIP(launch_ll_clean(a, (int)grid, (hipStream_t)stream));
-  return nexrSuccess;
-}
-
-NEXR_API nexrResult_t nexrReduceCopyLL128(const void* src, int srcIsInput, int nRecv, const void* const* recvWire,
-                                          const uint64_t* recvFlags, void* dst, int nSend, void* const* sendWire,
-                                          const uint64_t* sendFlags, size_t nElts, int datatype, int devRedOp,
-                                          uint64_t redOpArg, int postOp, uint32_t* status, uint32_t timeoutUs,
-                                          nexrStream_t stream) {
-  if (nRecv < 0 || nRecv > NEXR_MAX_SRCS || nSend < 0 || nSend > NEXR_MAX_DSTS) return nexrInvalidArgument;
-  if ((!src && nRecv == 0) || (!dst && nSend == 0)) return nexrInvalidArgument;
-  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
-    return nexrInvalidArgument;
-  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    if ((int8_t)divisor == 0) return nexrInvalidArgument;
-  }
-  if ((nRecv && (!recvWire || !recvFlags)) || (nSend && (!sendWire || !sendFlags))) return nexrInvalidArgument;
-  if (nElts == 0) return nexrSuccess;
-  LL128Params a;
-  memset(&a, 0, sizeof(a));
-  for (int i = 0; i < nRecv; i++) {
-    if (!recvWire[i] || ((uintptr_t)recvWire[i] & 15)) return nexrInvalidArgument;
-    a.recv[i] = (const char*)recvWire[i];
-    a.recvFlag[i] = recvFlags[i];
-  }
-  for (int i = 0; i < nSend; i++) {
-    if (!sendWire[i] || ((uintptr_t)sendWire[i] & 15)) return nexrInvalidArgument;
-    a.send[i] = (char*)sendWire[i];
-    a.sendFlag[i] = sendFlags[i];
-  }
-  a.src = (const char*)src;
-  a.dst = (char*)dst;
-  a.nElts = nElts;
-  a.redArg = redOpArg;
-  a.status = status;
-  a.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;
-  a.nRecv = nRecv;
-  a.nSend = nSend;
-  a.srcIsInput = srcIsInput ? 1 : 0;
-  a.postOp = postOp ? 1 : 0;
-  llSemantics(&datatype, &devRedOp, &a.srcIsInput, &a.postOp, &a.firstWins);
-  const uint64_t nUnits = (nElts * typeSize(datatype) + kLL128SliceData - 1) / kLL128SliceData * 128;
-  uint64_t grid = (nUnits + kLL128TileUnits - 1) / kLL128TileUnits;
-  if (grid > (1u << 20)) grid = 1u << 20;
-  NEXR_HIP(launch_ll128(datatype, a, devRedOp, (int)grid, (hipStream_t)stream));
-  return nexrSuccess;
 }
 
 NEXR_API nexrResult_t nexrSetSemantics(int mode) {

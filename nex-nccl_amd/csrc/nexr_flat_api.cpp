@@ -290,16 +290,7 @@ namespace {
 // The rank count, datatype and op that a flat reduction takes.
 nexrResult_t flatOpCheck(int nRanks, int datatype, int devRedOp, uint64_t redOpArg) {
   if (!flatRanksOk(nRanks)) return nexrInvalidArgument;
-  if (datatype < 0 || datatype >= nexrNumTypes || datatype == nexrFloat8e4m3 || datatype == nexrFloat8e5m2)
-    return nexrInvalidArgument;
-  if (devRedOp < 0 || devRedOp >= nexrNumDevRedOps) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && !isInteger(datatype)) return nexrInvalidArgument;
-  if (devRedOp == nexrDevSumPostDiv && (redOpArg & 1) != 0 && typeSize(datatype) == 1) {  // as validate()
-    uint32_t divisor = (uint32_t)(redOpArg >> 1);
-    if (divisor == 0) divisor = 1;
-    if ((int8_t)divisor == 0) return nexrInvalidArgument;
-  }
-  return nexrSuccess;
+  return typeOpOk(datatype, devRedOp, redOpArg) ? nexrSuccess : nexrInvalidArgument;
 }
 
 // What the semantics make of a checked call: the dispatch and the fields that flat_fold reads (FlatParams' names).
@@ -1579,31 +1570,9 @@ namespace {
 // workgroups of kernels with many scalar registers; a surplus team would queue behind teams that poll it).
 // Test hook: NEXR_TEST_SYM_LL_RESIDENT=k makes the next calls take k as that number (read per call).
 nexrResult_t symLLResident(int coll, int dt, int64_t* resident) {
-  if (const char* e = getenv("NEXR_TEST_SYM_LL_RESIDENT"))
-    if (*e) {
-      *resident = strtoll(e, nullptr, 10);
-      return nexrSuccess;
-    }
-  constexpr int kDevs = 16;
-  static std::atomic<int64_t> cache[3][kDevs][nexrNumTypes];
-  int dev = 0;
-  NEXR_HIP(hipGetDevice(&dev));
-  const bool cached = dev >= 0 && dev < kDevs;
-  if (cached) {
-    const int64_t v = cache[coll][dev][dt].load(std::memory_order_relaxed);
-    if (v > 0) {
-      *resident = v;
-      return nexrSuccess;
-    }
-  }
-  int cus = 0, blocks = 0;
-  NEXR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  NEXR_HIP(sym_ll_blocks_per_cu(coll, dt, &blocks));
-  if (blocks > 4) blocks = 4;
-  if (blocks > 1) blocks--;
-  *resident = (int64_t)blocks * cus;
-  if (cached && *resident > 0) cache[coll][dev][dt].store(*resident, std::memory_order_relaxed);
-  return nexrSuccess;
+  static ResidentSlot cache[3][nexrNumTypes];
+  return residentWorkgroups(
+      ResidentLookup{"NEXR_TEST_SYM_LL_RESIDENT", &cache[coll][dt], sym_ll_blocks_per_cu, coll, dt, 4, true}, resident);
 }
 
 // The host side of the three calls. coll: 0 all-reduce (count elements per buffer), 1 reduce-scatter (count
@@ -1637,7 +1606,7 @@ nexrResult_t symLL(int coll, int nRanks, const void* const* inputs, void* const*
   if ((int64_t)nRanks * B > resident) return nexrInvalidUsage;
   p.nBytes = (uint64_t)count * esz;
   p.status = status;
-  p.timeoutTicks = (uint64_t)(timeoutUs ? timeoutUs : 1000000u) * 100u;  // s_memrealtime: 100 MHz
+  p.timeoutTicks = pollTicks(timeoutUs);
   p.nRanks = nRanks;
   p.nBlocks = B;
   p.firstWins = semantics() == nexrSemanticsShipped;  // SKIP_COMP: every add returns its first operand

@@ -1,10 +1,12 @@
 // nexr_host.h — what the host translation units of libnexr.so share (nexr_api.cpp defines it all, nexr_flat_api.cpp
-// uses it). Declarations only: everything with state (the registration cache, the staging pool, the counters, the
-// last HIP error) keeps its one definition in nexr_api.cpp.
+// and nexr_steps_api.cpp use it). Declarations only: everything with state (the registration cache, the staging
+// pool, the counters, the last HIP error) keeps its one definition in nexr_api.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <atomic>
 
 #include "nexr_internal.h"
 
@@ -21,6 +23,28 @@ nexrResult_t hipFail(hipError_t e);
 size_t typeSize(int dt);  // 0: not a datatype
 bool isInteger(int dt);
 long envLong(const char* name, long dflt);
+
+// The datatype, device op and SumPostDiv divisor that every reduce-copy entry takes.
+bool typeOpOk(int datatype, int devRedOp, uint64_t redOpArg);
+// The ticks a kernel polls before it gives up: timeoutUs, or one second for 0.
+uint64_t pollTicks(uint32_t timeoutUs);
+
+// Workgroups of one kernel the current device keeps resident (blocks per CU x CUs). The caller names the kernel
+// and holds what is known about it: the cache slot of that kernel (a function-local static of the caller), the
+// occupancy query with its two arguments, the cap on the query's answer per CU (0: none) and whether one is
+// taken off it. hook: an environment variable that, when set, is taken as the answer; read per call (tests set
+// it between calls), before any HIP call.
+constexpr int kResidentDevs = 16;
+using ResidentSlot = std::atomic<int64_t>[kResidentDevs];
+struct ResidentLookup {
+  const char* hook;
+  ResidentSlot* slot;
+  hipError_t (*blocksPerCu)(int a, int b, int* blocks);
+  int a, b;
+  int capPerCu;
+  bool lessOne;
+};
+nexrResult_t residentWorkgroups(const ResidentLookup& k, int64_t* resident);
 
 int semantics();  // nexrSetSemantics / NEXR_SEMANTICS
 void llSemantics(int* dt, int* op, int* srcIsInput, int* postOp, int* firstWins);

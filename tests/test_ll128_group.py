@@ -181,3 +181,55 @@ def test_set_ll_group_still_needs_device_memory(nexr, oracle):
                 comm.set_ll_group(on)
             assert e.value.code == nexr.Result.InvalidUsage
         assert comm.queued() == 0
+
+
+def _launch_count(call, region):
+    """The launches a group call would make, read without a device: with the residency hook at 0 a workspace of
+    k regions gives the workspace's 4 while k is below the count and the residency refusal's 5 from k on."""
+    for k in range(0, 10):
+        code = call(ws_bytes=k * region)
+        if code == 5:
+            return k
+        assert code == 4, (k, code)
+    raise AssertionError("more than 9 launches")
+
+
+def _copy(nexr, src_buf, src_ix, dst_buf, dst_ix, n=64):
+    return nexr.ll_step(src_buf, src_ix, dst_buf, dst_ix, n)
+
+
+def _cut_cases(nexr):
+    """(name, members, launches). The cuts fall before a member's 97th step of a launch, before a step that
+    touches user bytes the member touched earlier in the launch at another position (a write, or a read of written
+    bytes), at the same step index for every member; the members here have no connections, so the dry run passes."""
+    same = _copy(nexr, 0, 0, 1, 0)                       # reads input[0, 64), writes output[0, 64)
+    back = _copy(nexr, 1, 0, 0, 0)                       # reads output[0, 64), writes input[0, 64)
+    return [
+        ("96 steps", [([], [], [same] * 96)], 1),
+        ("97 steps", [([], [], [same] * 97)], 2),
+        ("193 steps", [([], [], [same] * 193)], 3),
+        ("unequal members", [([], [], [same] * 100), ([], [], [same] * 3)], 2),
+        ("unequal members, both short", [([], [], [same] * 96), ([], [], [same] * 3)], 1),
+        # output[1, 65) is written after output[0, 64) was read: another position, one cut
+        ("write of a read range, shifted", [([], [], [back, _copy(nexr, 0, 0, 1, 1)])], 2),
+        # the same range at the same position: the same lanes, in order, no cut
+        ("write of a read range, in place", [([], [], [back, _copy(nexr, 0, 0, 1, 0)])], 1),
+        # a conflict on one member cuts every member at that step index
+        ("a conflict on the second member", [([], [], [same] * 2), ([], [], [back, _copy(nexr, 0, 0, 1, 1)])], 2),
+    ]
+
+
+@pytest.mark.parametrize("case", range(8))
+def test_launch_counts_follow_the_cut_rules(nexr, monkeypatch, case):
+    monkeypatch.setenv("NEXR_TEST_LL_GROUP_RESIDENT", "0")
+    name, members, want = _cut_cases(nexr)[case]
+    region = nexr.ll_group_workspace_bytes(len(members), 1)
+    assert _launch_count(lambda ws_bytes: _call(nexr, members, ws_bytes=ws_bytes), region) == want, name
+
+
+def test_no_send_step_cleans_under_64_bit_flags(nexr, monkeypatch):
+    """Send counters at which the LL test rule would clean (0x78 ..) cut nothing here."""
+    monkeypatch.setenv("NEXR_TEST_LL_GROUP_RESIDENT", "0")
+    members = [([], [(X_FIFO, X_HEAD, 0x77)], [nexr.ll_step(0, 0, -1, 0, 64, send=True)] * 4)]
+    region = nexr.ll_group_workspace_bytes(1, 1)
+    assert _launch_count(lambda ws_bytes: _call(nexr, members, ws_bytes=ws_bytes), region) == 1

@@ -258,3 +258,82 @@ def test_set_simple_group_needs_simple_thread_ranks_in_device_memory(nexr, oracl
                 comm.set_simple_group(on)
             assert e.value.code == nexr.Result.InvalidUsage
         assert comm.queued() == 0
+
+
+def _launch_count(call, region):
+    """The launches a group call would make, read without a device: with the residency hook at 0 a workspace of
+    k regions gives the workspace's 4 while k is below the count and the residency refusal's 5 from k on."""
+    for k in range(0, 10):
+        code = call(ws_bytes=k * region)
+        if code == 5:
+            return k
+        assert code == 4, (k, code)
+    raise AssertionError("more than 9 launches")
+
+
+def _copy(nexr, src_buf, src_ix, dst_buf, dst_ix, n=64):
+    return nexr.ll_step(src_buf, src_ix, dst_buf, dst_ix, n)
+
+
+def _cut_cases(nexr):
+    """(name, members, launches). The cuts fall before a member's 97th step of a launch, before a step that
+    touches user bytes the member touched earlier in the launch at another position (a write, or a read of written
+    bytes), at the same step index for every member; the members here have no connections, so the dry run passes."""
+    same = _copy(nexr, 0, 0, 1, 0)                       # reads input[0, 64), writes output[0, 64)
+    back = _copy(nexr, 1, 0, 0, 0)                       # reads output[0, 64), writes input[0, 64)
+    return [
+        ("96 steps", [([], [], [same] * 96)], 1),
+        ("97 steps", [([], [], [same] * 97)], 2),
+        ("193 steps", [([], [], [same] * 193)], 3),
+        ("unequal members", [([], [], [same] * 100), ([], [], [same] * 3)], 2),
+        ("unequal members, both short", [([], [], [same] * 96), ([], [], [same] * 3)], 1),
+        # output[1, 65) is written after output[0, 64) was read: another position, one cut
+        ("write of a read range, shifted", [([], [], [back, _copy(nexr, 0, 0, 1, 1)])], 2),
+        # the same range at the same position: the same lanes, in order, no cut
+        ("write of a read range, in place", [([], [], [back, _copy(nexr, 0, 0, 1, 0)])], 1),
+        # a conflict on one member cuts every member at that step index
+        ("a conflict on the second member", [([], [], [same] * 2), ([], [], [back, _copy(nexr, 0, 0, 1, 1)])], 2),
+    ]
+
+
+@pytest.mark.parametrize("case", range(8))
+def test_launch_counts_follow_the_cut_rules(nexr, monkeypatch, case):
+    monkeypatch.setenv("NEXR_TEST_SIMPLE_GROUP_RESIDENT", "0")
+    name, members, want = _cut_cases(nexr)[case]
+    region = nexr.simple_group_workspace_bytes(len(members), 1)
+    assert _launch_count(lambda ws_bytes: _call(nexr, members, ws_bytes=ws_bytes), region) == want, name
+
+
+def _call_direct(nexr, members, direct, ws_bytes):
+    L = nexr.lib()
+    sets = [nexr.simple_conn_set(0x10000 * (m + 1), 0x20000000 + 0x10000 * m, r, s, SLOT, 8, 2)
+            for m, (r, s, _steps) in enumerate(members)]
+    cs = (nexr.SimpleConnSet * len(sets))(*sets)
+    arrs = [(nexr.LLStep * len(st))(*st) for _r, _s, st in members]
+    ptrs = (ctypes.POINTER(nexr.LLStep) * len(arrs))(*[ctypes.cast(a, ctypes.POINTER(nexr.LLStep)) for a in arrs])
+    counts = (ctypes.c_int * len(members))(*[len(st) for _r, _s, st in members])
+    ds = (nexr.SimpleDirectSet * len(direct))(*direct) if direct else None
+    return L.nexrReduceCopySimpleStepsGroupDirect(len(members), cs, ptrs, counts, F32, 0, 0, 0, ds, None, 0,
+                                                  ctypes.c_void_p(WS), ws_bytes, None)
+
+
+@pytest.mark.parametrize("recv_ix, permit, is_direct, want", [
+    (0, True, True, 2),    # the direct source output[0, 64) against the earlier write of output[1, 65): one cut
+    (1, True, True, 1),    # the direct source is the range that was written, at the same position
+    (0, False, True, 1),   # the record does not permit a direct receive: it reads the slot
+    (0, True, False, 1),   # the connection is not direct
+])
+def test_launch_counts_with_a_direct_receive(nexr, monkeypatch, recv_ix, permit, is_direct, want):
+    """A direct receive reads the member's output at dstIx: a further range for the cuts. The first record writes
+    output[1, 65); the second receives (one-ended connection) into input[recv_ix, recv_ix + 64), so its own user
+    ranges conflict with nothing: only the direct source can."""
+    monkeypatch.setenv("NEXR_TEST_SIMPLE_GROUP_RESIDENT", "0")
+    steps = [_copy(nexr, 0, recv_ix, 1, 1),
+             nexr.ll_step(-1, 0, 0, recv_ix, 64, recv=True, direct=nexr.SIMPLE_DIRECT_RECV if permit else 0)]
+    members = [([_conn(X)], [], steps)]
+    direct = [nexr.simple_direct_set((), (1,) if is_direct else ())]
+    region = nexr.simple_group_direct_workspace_bytes(1, 1)
+    assert _launch_count(lambda ws_bytes: _call_direct(nexr, members, direct, ws_bytes), region) == want
+    # without direct sets the call is nexrReduceCopySimpleStepsGroup: its regions, and no direct source
+    region = nexr.simple_group_workspace_bytes(1, 1)
+    assert _launch_count(lambda ws_bytes: _call_direct(nexr, members, None, ws_bytes), region) == 1
